@@ -28,6 +28,10 @@ planes -> fp64 / fp32, and float64 planes as the converter stores them).  Every 
 time of the dominant kernel on torch's stream vs the algorithmic bytes of SURVEY 8d) and `cpu_baseline` (the NumPy /
 SciPy oracle with the reference's pass structure on a bounded slice, host cores, timed before HIP is initialised).
 The headline line also carries the other lines' key figures as flat `also_*` strings.
+
+`--dump-outputs DIR` writes what the headline's timed path handed out in its last pass, per tile, as DIR/<name>.npy: a
+fixed, seeded sample of Sv and of the MVBS (the same positions in every run) and the MVBS coordinates whole, under 64 MB
+in all; NaN / inf entries (empty MVBS bins, padded pings) are written as 0 and marked in DIR/<name>_nonfinite.npy.  The inputs are seeded: two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -95,6 +99,10 @@ def parse():
     ap.add_argument("--read-lag", type=int, default=1,
                     help="cfg5: the result of a tile is read after this many further tiles have been launched")
     ap.add_argument("--out", default=None, help="also append every JSON line to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="cfg5: write what the timed path handed out in its last step, per tile, to DIR/<name>.npy -- a "
+                         "fixed, seeded sample of Sv and of the MVBS, the MVBS coordinates whole (at most 64 MB in all); NaN / inf "
+                         "entries are written as 0 and marked in DIR/<name>_nonfinite.npy")
     return ap.parse_args()
 
 
@@ -244,6 +252,39 @@ def measured_traffic(key):
         return None, f"unreadable profiles/hbm_traffic.json: {ex!r}"[:100]
 
 
+DUMP_BYTES = 56 << 20  # --dump-outputs: the samples of all tiles with their masks (the coordinates stay well under 8 MB)
+DUMP_SEED = 20260505
+
+
+def dump_sample(shape, k, device):
+    """A fixed, seeded sample of ``k`` positions of an array of this shape (every position when it has no more), sorted,
+    as one index tensor per dimension on ``device``: the same positions for the same shape in every run and build."""
+    import torch
+
+    n = int(np.prod(shape))
+    flat = np.arange(n) if n <= k else np.sort(np.random.default_rng([DUMP_SEED, *shape]).choice(n, size=k, replace=False))
+    return tuple(torch.from_numpy(np.ascontiguousarray(i, dtype=np.int64)).to(device) for i in np.unravel_index(flat, shape))
+
+
+def write_dump(dirname, arrays, limit=64_000_000):
+    """``arrays``: name -> device tensor or host array (float32 / float64).  Every file holds finite numbers only: an
+    array goes out as DIR/<name>.npy with its NaN / inf entries set to 0, and DIR/<name>_nonfinite.npy (float32, same
+    length) says which those were -- 0 finite, 1 NaN, 2 +inf, -2 -inf (an empty MVBS bin, a padded ping's Sv are NaN).
+    Both files are written for every array, so that two runs always write the same set of files."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        bad = ~np.isfinite(a)
+        out[name] = np.where(bad, 0, a).astype(a.dtype)
+        out[name + "_nonfinite"] = np.where(np.isnan(a), 1, np.where(bad, 2 * np.sign(a), 0)).astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= limit, f"--dump-outputs: {total} B"
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 class Ctx:
     """What every run function needs."""
 
@@ -256,6 +297,7 @@ class Ctx:
         self.torch, self.dist, self.ops, self.sharding, self.synth = torch, dist, ops, sharding, synth
         self.dtype = args.dtype
         self.cache = {}
+        self.dump_dir = None  # (--dump-outputs: set for the line whose outputs are written)
 
     @property
     def dt(self):
@@ -873,11 +915,14 @@ class Cfg5:
         d["backscatter_r"] = ep.DeviceArray(self.tiles[i]["backscatter_r"])
         return ep.echodata.from_ek60_arrays(d, source_file=f"synthetic_ek60_tile{self.gtiles[i]:02d}.raw").to_device()
 
-    def api_layout(self, offset_ns, lag=1):
+    def api_layout(self, offset_ns, lag=1, dump_k=None, dump_after=None):
         """(one_pass, finish, state): one pass = every resident tile through the product entry points -- world 1: the
         reference's two calls; world > 1: sharding.compute_Sv_MVBS on the tile as this rank's shard of dataset j.  The
         result of a tile is READ (the deferred MVBS dataset assembled: three doubles come back from the GPU) after the
-        next ``lag`` tiles have been launched, then dropped (its Sv array goes back to the allocator)."""
+        next ``lag`` tiles have been launched, then dropped (its Sv array goes back to the allocator).  ``dump_k`` =
+        (k Sv, k MVBS): the results read from the ``dump_after``-th on leave a seeded sample of k positions of their Sv
+        and of their MVBS, and the MVBS coordinates, in ``state["dump"]`` (name -> array) -- gathered on the caller's
+        stream, no wait for the GPU; the next launch is ordered after it by the pipeline."""
         import logging
 
         import echopype_amd as ep
@@ -907,8 +952,25 @@ class Cfg5:
         # messages; no wait for the GPU on the deferred routes) -- what has to stay under the kernel's ~9 ms per tile for
         # the GPU to run back to back, and the per-call cost that decides the scaling at N = 8 (one tile per rank and pass)
         state = {"last": None, "n_read": 0, "host_s": 0.0, "calls": 0, "timing": False, "timers": [], "pipe": None,
-                 "launched": 0}
+                 "launched": 0, "dump": {}, "index": {}}
         T = len(eds)
+        t0 = np.datetime64(ctx.synth.T0, "ns")
+
+        def capture(ds, mv):
+            g = self.gtiles[state["n_read"] % T]  # (results come out in launch order: launch i is tile i % T)
+            for name, arr, k in (("sv", ds["Sv"].data, dump_k[0]), ("mvbs", mv["Sv"].data, dump_k[1])):
+                key = (arr.shape, k)
+                if key not in state["index"]:  # (built at the first result read: in the warm-up)
+                    state["index"][key] = dump_sample(arr.shape, k, torch.device("cuda", torch.cuda.current_device()))
+                if state["n_read"] >= dump_after:
+                    state["dump"][f"{name}_sample_tile{g:02d}"] = arr.tensor[state["index"][key]]
+            if state["n_read"] >= dump_after:
+                for c, da in mv.coords.items():
+                    v = np.asarray(da.values)
+                    if v.dtype.kind == "M":  # (ns since the synthetic survey's origin: exact in float64)
+                        v = (v.astype("datetime64[ns]") - t0).astype(np.int64).astype(np.float64)
+                    if v.dtype.kind == "f":
+                        state["dump"][f"mvbs_{c}_tile{g:02d}"] = v.copy()
 
         def launch(i):
             # the HIP-event bracket goes round the tiles from pass to pass: roofline.kernel_ms is the mean over ALL tiles
@@ -931,6 +993,8 @@ class Cfg5:
         def read(item):
             ds, mv = item
             state["last"] = (tuple(mv["Sv"].shape),)
+            if dump_k:
+                capture(ds, mv)
             state["n_read"] += 1
 
         def one_pass(timer):
@@ -1047,9 +1111,18 @@ def run_cfg5(ctx, cpu, variant=""):
     ctx.free()
     # (c) the product entry points on the same tiles, same 10-s offset: the headline
     lag = max(1, args.read_lag)
-    pass_c, finish_c, state, eds = job.api_layout(10_000_000_000, lag=lag)
+    dump_k = None
+    if ctx.dump_dir:  # (the sample budget is shared by the tiles of every rank)
+        per = DUMP_BYTES // (job.n_tiles * ((8 if ctx.dtype == "float64" else 4) + 4))  # (+ 4 B: the mask entry)
+        dump_k = (per // 3, per - per // 3)
+    T = len(job.tiles)
+    pass_c, finish_c, state, eds = job.api_layout(10_000_000_000, lag=lag, dump_k=dump_k,
+                                                  dump_after=T * passes * (steps + args.warmup) - T)  # the last pass
     elapsed, region_ms = ctx.timed(pass_c, passes, finish=finish_c, timers_of=lambda: state["timers"])
-    assert state["n_read"] == len(job.tiles) * passes * (steps + args.warmup)  # every result was read
+    assert state["n_read"] == T * passes * (steps + args.warmup)  # every result was read
+    if ctx.dump_dir:
+        assert len(state["dump"]) >= 2 * T, sorted(state["dump"])
+        write_dump(ctx.dump_dir, state["dump"])
     if world == 1 and not getattr(args, "sharded_at_1", False):
         route = "compute_Sv -> compute_MVBS('1m','20s') per tile"
         coll = "none at 1 rank"
@@ -1164,6 +1237,9 @@ def main():
         todo = args.workload.split(",")  # (several lines in one process, in this order: "cfg5:one,cfg5")
     else:
         todo = ["cfg5"] if args.only_headline else list(DEFAULT_LINES)
+    dump_line = max((i for i, s in enumerate(todo) if s.partition(":")[0] == "cfg5"), default=None)
+    if args.dump_outputs and dump_line is None:
+        sys.exit("--dump-outputs writes the cfg5 headline's outputs: --workload has no cfg5 line")
 
     def kind_of(w):
         if w == "api:chain":
@@ -1179,7 +1255,6 @@ def main():
                 cpu[kind] = (cpu_baseline_bb() if kind == "bb" else
                              cpu_baseline_ek60(chain=kind == "chain", multicore=kind == "ek60"))
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # (RCCL across processes needs dmabuf IPC on this host driver)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # (echopype_amd sets it too: the pipeline's two streams need queues of their own)
     import torch
     import torch.distributed as dist
 
@@ -1209,6 +1284,7 @@ def main():
         if w == "cfg5":
             ctx.cache.clear()
             ctx.free()
+            ctx.dump_dir = args.dump_outputs if i == dump_line else None
             out = run_cfg5(ctx, cpu.get("ek60"), variant)
         elif w == "api":
             out = run_api(ctx, cpu.get("chain" if variant == "chain" else "ek60"), variant)

@@ -7,15 +7,9 @@ range_sample) arrays go through a C ABI (include/echopype_amd.h, loaded with cty
 HIP kernels.  There is no CPU fallback: importing the package loads libechopype_amd.so and fails
 loudly if it has not been built (``python echopype_amd/build.py``).
 """
-import os as _os
-
-# The HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) when it initialises;
-# streams that share a queue run one after the other.  ``pipeline`` puts consecutive files on two side streams next to
-# the upload / download streams and the caller's own -- with four queues two of them can end up on ONE queue (measured,
-# round 6: the headline's side-by-side launches then serialise, 0.67 instead of 0.72 of the roofline).  Eight queues, unless
-# the caller has said otherwise; it has to be in the environment before the first HIP call of the process.
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
+# The HIP runtime maps a process's streams onto a fixed number of hardware queues (GPU_MAX_HW_QUEUES) when it
+# initialises; streams that share a queue run one after the other.  The package leaves that number to the runtime and the
+# user: ``pipeline`` keeps only side streams it has seen running side by side (``pipeline._runs_beside``).
 from . import _lib  # noqa: F401,E402  (loads the HIP library; raises if missing)
 from . import calibrate, clean, commongrid, consolidate, mask, ops, pipeline, synth, utils  # noqa: F401,E402
 from .echodata import EchoData  # noqa: F401,E402

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's OWN functions, executed from /root/reference over oracle/xr_shim.py, on the inputs the reference's
 OWN tests build, held to the expectations written in those test files (authoring container only: needs
-/root/reference; run by tests/test_reference_kats_over_shim.py when it is there).
+/root/reference; tests/test_reference_kats_over_shim.py holds the numbers it stores with --write, below).
 
 The golden generators (oracle/gen_*goldens.py) run the same reference code over the same stand-in for xarray; this
 script closes the loop "stand-in + reference code == numbers the reference's maintainers wrote down":
@@ -17,7 +17,13 @@ script closes the loop "stand-in + reference code == numbers the reference's mai
   calibrate/env_params.py::harmonize_env_param_time (+ utils/align.py::align_to_ping_time)
                                               tests/calibrate/test_env_params.py:29-126 (scalar, one timestamp, identical
                                               axis, the 0.5 and [0.5, 2880.5] interpolations)
-Exit status 0 = every expectation met."""
+Exit status 0 = every expectation met.
+
+    python oracle/check_reference_kats.py --write tests/golden/ref_kat_goldens.npz
+
+also stores the inputs and what the reference's functions returned on them, so that
+tests/test_reference_kats_over_shim.py can hold those numbers to the same expectations, and this tree's oracle to those
+numbers, where the reference is not at hand."""
 import logging
 import os
 import sys
@@ -34,6 +40,7 @@ from gen_maskapi_goldens import load_clean_api  # noqa: E402  (stub modules + th
 
 DA, DS = xr_shim.DataArray, xr_shim.Dataset
 DIMS = ["channel", "ping_time", "range_sample"]
+OUT = {}  # name -> array: the inputs and the reference's outputs of every check (--write)
 
 
 def check_remove_background_noise(api):
@@ -53,13 +60,18 @@ def check_remove_background_noise(api):
         ds["sound_absorption"] = 0.001
         return ds
 
-    out = api.remove_background_noise(dataset(np.array([data]), 10), ping_num=2, range_sample_num=5, SNR_threshold="0dB")
+    ds = dataset(np.array([data]), 10)
+    out = api.remove_background_noise(ds, ping_num=2, range_sample_num=5, SNR_threshold="0dB")
     sc = out["Sv_corrected"].transpose(*DIMS).data
+    OUT.update(noise_toy_Sv=ds["Sv"].data, noise_toy_echo_range=ds["echo_range"].data, noise_toy_Sv_corrected=sc)
     assert np.isnan(sc[0, 0, 30]) and np.isnan(sc[0, 0, 60])
     np.random.seed(1)
     data = np.random.normal(loc=-100, scale=2, size=(nchan, npings, nrange))
-    out = api.remove_background_noise(dataset(data, 3), ping_num=2, range_sample_num=5, SNR_threshold="0dB")
+    ds = dataset(data, 3)
+    out = api.remove_background_noise(ds, ping_num=2, range_sample_num=5, SNR_threshold="0dB")
     null = np.isnan(out["Sv_corrected"].transpose(*DIMS).data)
+    OUT.update(noise_seed1_Sv=ds["Sv"].data, noise_seed1_echo_range=ds["echo_range"].data,
+               noise_seed1_Sv_corrected=out["Sv_corrected"].transpose(*DIMS).data)
     assert np.count_nonzero(null[0, :, :50]) == 6, np.count_nonzero(null[0, :, :50])
     return "remove_background_noise: noise points NaN; 6 of the first 50 range samples removed on the seed-1 data"
 
@@ -79,6 +91,7 @@ def check_index_binning():
     ds["frequency_nominal"] = DA(np.array([38e3, 120e3]), {"channel": chans}, ["channel"])
     out = cg_api.compute_MVBS_index_binning(ds, range_sample_num=rsn, ping_num=ping_num)
     got = out["Sv"].transpose(*DIMS).data
+    OUT.update(ixbin_Sv=sv, ixbin_echo_range=ds["echo_range"].data, ixbin_Sv_MVBS=got)
     shape = np.ceil((nchan, npings / ping_num, nrange / rsn)).astype(int)
     assert np.all(got.shape == shape), (got.shape, shape)
     # the test's expectation, evaluated with NumPy alone: pad to whole blocks with NaN, nanmean per block
@@ -118,12 +131,14 @@ def check_vend_cal_params_power():
         ([[64, nan, 128, 512], [512, 1024, 256, nan]], ["chA", "chB"], [[10, nan, 20, 40], [130, 140, 120, nan]]),
         ([[512, 1024, 256, nan], [64, nan, 128, 512]], ["chB", "chA"], [[130, 140, 120, nan], [10, nan, 20, 40]]),
     ]
-    for tdn, chans, exp in cases:
+    for i, (tdn, chans, exp) in enumerate(cases):
         beam = DS(coords={"ping_time": np.array([1, 2, 3, 4]), "channel": np.array(chans)})
         beam["transmit_duration_nominal"] = DA(np.array(tdn, dtype=float).T, {"ping_time": np.array([1, 2, 3, 4]),
                                                                            "channel": np.array(chans)}, ["ping_time", "channel"])
         out = cp.get_vend_cal_params_power(beam, vend, "sa_correction")
         got = out.transpose("ping_time", "channel")
+        OUT[f"vend_case{i}_transmit_duration_nominal"] = np.array(tdn, dtype=float)
+        OUT[f"vend_case{i}_sa_correction"] = got.data.astype(float).T
         assert list(got.coords["channel"]) == chans, (list(got.coords["channel"]), chans)
         np.testing.assert_allclose(got.data.astype(float), np.array(exp, dtype=float).T, equal_nan=True)
         assert "pulse_length_bin" not in got.coords
@@ -159,11 +174,13 @@ def check_harmonize_env_param_time():
     q = np.array(["2017-06-20T01:00:15"], dtype="datetime64[ns]")
     new = h(p=p, ping_time=DA(q, {"ping_time": q}, ["ping_time"]))
     assert (np.asarray(new.coords["ping_time"]) == q).all() and new.data == 0.5
+    OUT["env_interp_one"] = np.asarray(new.data, dtype=float)
     time1 = np.arange("2017-06-20T01:00:00", "2017-06-22T01:00:31", np.timedelta64(30, "s"), dtype="datetime64[ns]")
     p = DA(np.arange(len(time1)), {"time1": time1}, ["time1"])
     q = np.array(["2017-06-20T01:00:15", "2017-06-21T01:00:15"], dtype="datetime64[ns]")
     new = h(p=p, ping_time=DA(q, {"ping_time": q}, ["ping_time"]))
     assert np.array_equal(np.asarray(new.coords["ping_time"]), q) and (new.data == [0.5, 2880.5]).all(), new.data
+    OUT["env_interp_two"] = np.asarray(new.data, dtype=float)
     return "harmonize_env_param_time: scalar, one timestamp, identical axis, 0.5 and [0.5, 2880.5]"
 
 
@@ -174,6 +191,8 @@ def main():
              check_harmonize_env_param_time()]
     for ln in lines:
         print("ok  ", ln)
+    if "--write" in sys.argv:
+        np.savez_compressed(sys.argv[sys.argv.index("--write") + 1], **{k: np.asarray(v) for k, v in OUT.items()})
     return 0
 
 

@@ -182,3 +182,60 @@ def test_sharded_route_on_a_one_rank_rccl_group_prints_its_host_cost():
     _check_line(d, want_cpu=False)
     assert d["n_gpus"] == 1 and "sharding.compute_Sv_MVBS" in d["config"]["route"]
     assert 0 < d["config"]["host_ms_per_call"] < 50 and d["config"]["allreduce_bytes"] > 0
+
+
+def test_dump_sample_is_fixed_by_the_shape():
+    """--dump-outputs: the sampled positions depend on the array's shape alone (two builds compare output for output)."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.dump_sample((4, 1000, 300), 5000, "cpu")
+    b = bench.dump_sample((4, 1000, 300), 5000, "cpu")
+    assert all(x.equal(y) for x, y in zip(a, b)) and len(a) == 3
+    flat = (a[0] * 1000 + a[1]) * 300 + a[2]
+    assert flat.unique().numel() == 5000 and bool((flat[1:] > flat[:-1]).all())
+    whole = bench.dump_sample((2, 3), 10, "cpu")
+    assert [x.tolist() for x in whole] == [[0, 0, 0, 1, 1, 1], [0, 1, 2, 0, 1, 2]]
+
+
+def test_write_dump_keeps_every_file_finite_and_marks_what_was_not(tmp_path):
+    """--dump-outputs: NaN / inf go out as 0 with a mask beside them (0 finite, 1 NaN, 2 +inf, -2 -inf); the mask is
+    written for a finite array too, so that every run writes the same files."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    bench.write_dump(str(tmp_path), {"a": np.array([1.5, np.nan, np.inf, -np.inf, -2.0]),
+                                     "b": np.array([3.0, 4.0], dtype=np.float32)})
+    assert sorted(os.listdir(tmp_path)) == ["a.npy", "a_nonfinite.npy", "b.npy", "b_nonfinite.npy"]
+    a, am = np.load(tmp_path / "a.npy"), np.load(tmp_path / "a_nonfinite.npy")
+    assert a.dtype == np.float64 and a.tolist() == [1.5, 0.0, 0.0, 0.0, -2.0]
+    assert am.dtype == np.float32 and am.tolist() == [0, 1, 2, -2, 0]
+    assert np.load(tmp_path / "b.npy").dtype == np.float32 and np.load(tmp_path / "b_nonfinite.npy").tolist() == [0, 0]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_steps_results(tmp_path):
+    """`--dump-outputs DIR`: per tile, a seeded sample of Sv and of the MVBS and the MVBS coordinates, float32 / float64,
+    under 64 MB in all; the MVBS sample is the MVBS the line's last tile handed out."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--only-headline", "--no-cpu-baseline", "--steps", "2",
+                        "--warmup", "1", "--pings-total", "200000", "--dump-outputs", str(tmp_path)], capture_output=True,
+                       text=True, cwd=ROOT, check=True)
+    d = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    files = sorted(os.listdir(tmp_path))
+    tiles = int(d["config"]["tiles"].split(" x ")[0])
+    for name in ("sv_sample", "mvbs_sample", "mvbs_ping_time", "mvbs_echo_range"):
+        assert [f for f in files if f.startswith(name + "_tile")] == \
+            sorted(f"{name}_tile{g:02d}{m}.npy" for g in range(tiles) for m in ("", "_nonfinite")), files
+    arrays = {f: np.load(os.path.join(tmp_path, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64_000_000
+    mv = arrays[f"mvbs_sample_tile{tiles - 1:02d}.npy"]
+    mask = arrays[f"mvbs_sample_tile{tiles - 1:02d}_nonfinite.npy"]
+    assert mv.ndim == 1 and mv.size > 0 and mask.shape == mv.shape and (mask == 0).any()
+    assert set(np.unique(mask).tolist()) <= {-2.0, 0.0, 1.0, 2.0} and (mv[mask != 0] == 0).all()
+    assert arrays["mvbs_echo_range_tile00.npy"].size == d["config"]["mvbs_shape_last_tile"][2]
