@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("ECHOPYPE_AMD_LIB") or os.path.join(_HERE, "lib", "lib
 
 EPA_OK, EPA_EINVAL, EPA_EHIP, EPA_ENOMEM, EPA_EUNSUPPORTED = range(5)
 F32, F64 = 0, 1
+I8 = 2  # EPA_I8: int8 electrical-angle steps (epa_splitbeam_power only)
 CAL_SV, CAL_TS = 0, 1
 SONAR_EK60, SONAR_EK80 = 0, 1
 PM_SCALAR, PM_CHANNEL, PM_CHANNEL_PING, PM_PULSE_TABLE = range(4)
@@ -130,6 +131,10 @@ SIGNATURES = {
                             _vp, _vp, _vp, _vp, _i, _vp],
     "epa_geodesic_steps": [_vp, _vp, _i, _vp, _vp],
     "epa_nasc": [_vp, _vp, _i, _i, _i, _vp, _i, _d, _i, _u, _vp, _vp, _vp, _vp, _i, _vp],
+    "epa_splitbeam_power": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp],
+    "epa_splitbeam_complex": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp],
+    "epa_splitbeam_complex_fft": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i,
+                                  _vp, _vp],
     "epa_pool_sv_value": [_vp, _vp, _vp, _i, _i, _i, _d, _i, _d, _d, _d, _i, _d, _vp, _vp, _vp, _i, _vp],
 }
 

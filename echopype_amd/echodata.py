@@ -104,6 +104,27 @@ def _time1(ping_time):
     return np.asarray(ping_time, dtype="datetime64[ns]")
 
 
+_ANGLE_PLANES = ("angle_alongship", "angle_athwartship")
+_ANGLE_PARAMS = ("angle_sensitivity_alongship", "angle_sensitivity_athwartship", "angle_offset_alongship",
+                 "angle_offset_athwartship")
+
+
+def _add_split_beam(beam, d, params=True):
+    """Optional split-beam variables of the converters (convert/set_groups_ek60.py, set_groups_ek80.py): the
+    electrical angle planes (channel, ping_time, range_sample) -- int8 steps as parsed, or float once NaN-padded --,
+    ``beam_type`` (channel,) and (EK60) the angle parameters per channel.  Nothing is added for keys ``d`` lacks."""
+    dims3 = ("channel", "ping_time", "range_sample")
+    for k in _ANGLE_PLANES:
+        if d.get(k) is not None:
+            beam[k] = (dims3, np.asarray(d[k]))
+    if d.get("beam_type") is not None:
+        beam["beam_type"] = (("channel",), np.asarray(d["beam_type"], dtype=np.int64))
+    if params:
+        for k in _ANGLE_PARAMS:
+            if d.get(k) is not None:
+                beam[k] = (("channel",), np.asarray(d[k], dtype=np.float64))
+
+
 def from_ek60_arrays(d, source_file="synthetic_ek60.raw"):
     """Build an EK60 EchoData from the arrays of :func:`echopype_amd.synth.ek60_numpy`, with the
     variable names / dims the converter writes (convert/set_groups_ek60.py:88-152,578-667,728-787)."""
@@ -116,6 +137,7 @@ def from_ek60_arrays(d, source_file="synthetic_ek60.raw"):
         beam[k] = (("channel", "ping_time"), np.asarray(d[k], dtype=np.float64))
     beam["frequency_nominal"] = (("channel",), np.asarray(d["frequency_nominal"], dtype=np.float64))
     beam["equivalent_beam_angle"] = (("channel",), np.asarray(d["equivalent_beam_angle"], dtype=np.float64))
+    _add_split_beam(beam, d)
     K = d["pulse_length"].shape[1]
     vend = Dataset(coords={"channel": ch, "pulse_length_bin": np.arange(K)})
     for k in ("pulse_length", "gain_correction", "sa_correction"):
@@ -157,6 +179,7 @@ def from_ek80_arrays(d, filters, encode="complex", source_file="synthetic_ek80.r
         beam[k_out] = (("channel",), np.asarray(d[k_in], float))
     beam["angle_sensitivity_alongship"] = (("channel",), np.full(C, 23.0))
     beam["angle_sensitivity_athwartship"] = (("channel",), np.full(C, 23.0))
+    _add_split_beam(beam, d, params=False)
     nw, npc = filters["wbt_fil"].size, filters["pc_fil"].size
     vend = Dataset(coords={"channel": ch, "pulse_length_bin": np.arange(5), "WBT_filter_n": np.arange(nw + 3),
                            "PC_filter_n": np.arange(npc + 2)})

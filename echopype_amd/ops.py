@@ -708,6 +708,84 @@ def sv_complex(re, im, ccoef, *, replica=None, replica_off=None, max_taps=0, cal
     return dict(out=out, echo_range=rng, prx=prx, range_stats=stats)
 
 
+
+# ---- split-beam angles (consolidate.add_splitbeam_angle) ---------------------------------------------------------------
+SPLITBEAM_PARAMS = ("angle_sensitivity_alongship", "angle_sensitivity_athwartship", "angle_offset_alongship",
+                    "angle_offset_athwartship")
+SPLITBEAM_BEAM_TYPES = (1, 17, 49, 65, 81)
+
+
+def _angle_params(params, C, P):
+    """The four angle parameters (f64 device tensors of shape (), (C,) or (C, P), in SPLITBEAM_PARAMS order) as the C
+    ABI takes them: a host array of device pointers, one of epa_param_mode, and the tensors to keep alive."""
+    if len(params) != 4:
+        raise ValueError("four angle parameters: sensitivity along / athwart, offset along / athwart")
+    keep = [t.to(torch.float64).contiguous() for t in params]
+    ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in keep])
+    modes = (ctypes.c_int * 4)(*[_mode_of(t, C, P) for t in keep])
+    for t in keep:
+        _p(t)  # (device and contiguous)
+    return ptrs, modes, keep
+
+
+def splitbeam_power(along, athw, params, *, dtype=torch.float64):
+    """Split-beam angles of power/angle samples -> (theta, phi) (C, P, S).  ``along`` / ``athw``: the electrical angle
+    planes, int8 steps as a file stores them or float32 / float64 (NaN padding stays NaN); ``params`` as
+    _angle_params."""
+    C, P, S = along.shape
+    if athw.shape != along.shape or athw.dtype != along.dtype:
+        raise ValueError("angle_alongship / angle_athwartship: same shape and dtype")
+    codes = {torch.int8: _lib.I8, torch.float32: _lib.F32, torch.float64: _lib.F64}
+    if along.dtype not in codes:
+        raise ValueError(f"angle planes must be int8, float32 or float64 (got {along.dtype})")
+    ptrs, modes, keep = _angle_params(params, C, P)
+    theta = torch.empty((C, P, S), dtype=dtype, device=along.device)
+    phi = torch.empty_like(theta)
+    call("epa_splitbeam_power", _p(along), _p(athw), codes[along.dtype], ptrs, modes, C, P, S, _p(theta), _p(phi),
+         _DT[dtype], _stream())
+    return theta, phi
+
+
+def splitbeam_uses_fft(replica, max_taps, method="auto"):
+    """The form splitbeam_complex picks: the rule of sv_complex_uses_fft."""
+    return sv_complex_uses_fft(replica, max_taps, method)
+
+
+def splitbeam_complex(re, im, beam_type, params, *, replica=None, replica_off=None, max_taps=0, replica_id=None,
+                      dtype=torch.float64, method="auto", fft_dtype=None):
+    """Split-beam angles of complex samples -> (theta, phi) (C, P, S).  ``re`` / ``im`` (C, P, S, B), B = 3 or 4;
+    ``beam_type``: host sequence of C ints (1, 17, 49, 65, 81; -1 = skip the channel: NaN rows).  With ``replica`` /
+    ``replica_off`` (as sv_complex, ``replica_id`` too) the sector combinations are pulse-compressed first: "direct",
+    "fft" or "auto" (fft for replicas of 16 .. 1024 taps).  ``fft_dtype``: arithmetic of the transform, default
+    float64 whatever ``dtype`` is -- a phase needs the weak samples right, and complex64 butterflies err by ~3e-7 of
+    the tile's strongest echo (~1e-2 deg at 1e-3 of a ping's RMS); float32 on request."""
+    C, P, S, B = re.shape
+    if re.dtype != im.dtype or re.dtype not in _DT or im.shape != re.shape:
+        raise ValueError("backscatter_r / backscatter_i must both be float32 or float64 of one shape")
+    if method not in ("auto", "direct", "fft"):
+        raise ValueError("method must be 'auto', 'direct' or 'fft'")
+    bt = np.ascontiguousarray(np.asarray(beam_type, dtype=np.int32).reshape(-1))
+    if bt.size != C:
+        raise ValueError(f"beam_type: {C} values expected, got {bt.size}")
+    if replica_id is not None and (replica is None or tuple(replica_id.shape) != (C, P) or replica_id.dtype != torch.int32):
+        raise ValueError("replica_id: int32 (C, P) next to replica / replica_off")
+    n_rep = 0 if replica is None else (C if replica_id is None else int(replica_off.numel()) - 1)
+    ptrs, modes, keep = _angle_params(params, C, P)
+    dev = re.device
+    theta = torch.empty((C, P, S), dtype=dtype, device=dev)
+    phi = torch.empty_like(theta)
+    bt_p = bt.ctypes.data_as(ctypes.c_void_p)
+    if splitbeam_uses_fft(replica, max_taps, method):
+        ws = torch.empty(768 + 3 * n_rep * _lib.EK80_NFFT, dtype=torch.float64, device=dev)  # EPA_SPLITBEAM_FFT_WS_DOUBLES
+        fdt = torch_dtype(fft_dtype) if fft_dtype is not None else torch.float64
+        call("epa_splitbeam_complex_fft", _p(re), _p(im), _DT[re.dtype], bt_p, ptrs, modes, _p(replica),
+             _p(replica_off), _p(replica_id), n_rep, int(max_taps), C, P, S, B, _p(theta), _p(phi), _DT[dtype],
+             _DT[fdt], _p(ws), _stream())
+    else:
+        call("epa_splitbeam_complex", _p(re), _p(im), _DT[re.dtype], bt_p, ptrs, modes, _p(replica), _p(replica_off),
+             _p(replica_id), n_rep, int(max_taps), C, P, S, B, _p(theta), _p(phi), _DT[dtype], _stream())
+    return theta, phi
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

@@ -212,6 +212,102 @@ def ek80_numpy(C=2, P=16, S=1024, B=4, seed=20260504, waveform="BB", replicas=No
     return d
 
 
+
+# ---------------------------------------------------------------------------------------- split-beam angles
+# (consolidate.add_splitbeam_angle; new generators with their own seeds: the ones above are untouched)
+def splitbeam_sector_phases(e_along, e_athw, beam_type):
+    """Complex sector values (..., 4) whose combinations (consolidate/split_beam_angle.py:34-118) give the electrical
+    angles ``e_along`` / ``e_athw`` (degrees, arrays of one shape) exactly in exact arithmetic:
+      beam_type 1:  b_k = exp(i (s_k a + t_k b) / 2) with s = (-1, -1, 1, 1) (aft / fore), t = (1, -1, -1, 1)
+                    (star / port): fore conj(aft) = 4 cos^2(b/2) e^{ia}, star conj(port) = 4 cos^2(a/2) e^{ib};
+      17:           star = e^{-i fac1}, port = e^{-i fac2}, fore = 1 with fac1 = (sqrt3 a - b)/2, fac2 = (sqrt3 a + b)/2;
+      49/65/81:     the same three combinations, each written as (sector + centre) around a centre element q.
+    Unit magnitudes; the caller scales them."""
+    a, b = np.deg2rad(np.asarray(e_along, float)), np.deg2rad(np.asarray(e_athw, float))
+    out = np.zeros(a.shape + (4,), dtype=np.complex128)
+    if beam_type == 1:
+        for k, (sk, tk) in enumerate(((-1, 1), (-1, -1), (1, -1), (1, 1))):
+            out[..., k] = np.exp(0.5j * (sk * a + tk * b))
+        return out
+    fac1, fac2 = (np.sqrt(3) * a - b) / 2, (np.sqrt(3) * a + b) / 2
+    star, port, fore = np.exp(-1j * fac1), np.exp(-1j * fac2), np.ones_like(a, dtype=np.complex128)
+    if beam_type == 17:
+        out[..., 0], out[..., 1], out[..., 2] = star, port, fore
+        return out
+    q = 0.3 * np.exp(0.7j) * np.ones_like(a)  # the centre element
+    out[..., 0], out[..., 1], out[..., 2], out[..., 3] = star - q, port - q, fore - q, q
+    return out
+
+
+def ek80_splitbeam_numpy(C=2, P=8, S=600, B=4, beam_type=1, seed=20261015, waveform="BB", sens=(23.0, 21.5),
+                         offset=(0.05, -0.03)):
+    """An EK80 complex data set whose samples are a split-beam target of KNOWN angles: ``ek80_numpy``'s dictionary
+    (its own stream, unchanged) with the samples replaced by sector values of splitbeam_sector_phases -- a physical
+    alongship / athwartship angle per (channel, ping, sample) drawn in +-(150 / sens) degrees, magnitudes in
+    [0.5, 1.5) -- plus ``beam_type`` and the angle parameters.  Returns (d, theta, phi) with the angles the samples
+    encode, float64 (C, P, S).  ``beam_type``: one int for every channel, or a sequence of C."""
+    d = ek80_numpy(C=C, P=P, S=S, B=B, seed=seed, waveform=waveform)
+    rng = np.random.default_rng(seed + 7)
+    bts = np.broadcast_to(np.asarray(beam_type), (C,)).astype(np.int64)
+    sens_al = np.broadcast_to(np.asarray(sens[0], float), (C,)).copy()
+    sens_at = np.broadcast_to(np.asarray(sens[1], float), (C,)).copy()
+    off_al = np.broadcast_to(np.asarray(offset[0], float), (C,)).copy()
+    off_at = np.broadcast_to(np.asarray(offset[1], float), (C,)).copy()
+    theta = np.empty((C, P, S))
+    phi = np.empty((C, P, S))
+    x = np.empty((C, P, S, B), dtype=np.complex128)
+    for c in range(C):
+        lim = 150.0 / max(sens_al[c], sens_at[c])
+        theta[c] = rng.uniform(-lim, lim, (P, S))
+        phi[c] = rng.uniform(-lim, lim, (P, S))
+        e_al, e_at = (theta[c] + off_al[c]) * sens_al[c], (phi[c] + off_at[c]) * sens_at[c]
+        if bts[c] != 1:  # three-sector types: theta / phi come from fac1 +- fac2, keep both inside (-180, 180)
+            e_al = e_al * 0.5
+            e_at = e_at * 0.5
+            theta[c], phi[c] = e_al / sens_al[c] - off_al[c], e_at / sens_at[c] - off_at[c]
+        sec = splitbeam_sector_phases(e_al, e_at, int(bts[c]) if bts[c] in (1, 17, 49, 65, 81) else 1)
+        amp = 0.5 + rng.random((P, S, 1))
+        x[c] = (amp * sec)[..., :B]
+    d["backscatter_r"] = np.ascontiguousarray(x.real)
+    d["backscatter_i"] = np.ascontiguousarray(x.imag)
+    d["beam_type"] = bts
+    d["angle_sensitivity_alongship"], d["angle_sensitivity_athwartship"] = sens_al, sens_at
+    d["angle_offset_alongship"], d["angle_offset_athwartship"] = off_al, off_at
+    return d, theta, phi
+
+
+def splitbeam_nan_pad(d, pings, tail, single_sector=None):
+    """NaN-padded short pings (the last ``tail`` samples of ``pings``, every sector, as the converter pads them) and,
+    optionally, ``single_sector`` = (c, p, s, b): one sector NaN at one sample (re and im).  In place; returns d."""
+    for k in ("backscatter_r", "backscatter_i"):
+        d[k][:, list(pings), d[k].shape[2] - tail:, :] = np.nan
+        if single_sector is not None:
+            c, p, s_, b = single_sector
+            d[k][c, p, s_, b] = np.nan
+    return d
+
+
+def ek60_splitbeam_numpy(C=2, P=40, S=400, seed=20261016, nan_pad=False, sens=(21.9, 23.1), offset=(0.02, -0.07)):
+    """``ek60_numpy`` (its own stream, unchanged) plus split-beam angle planes: int8 electrical-angle steps as parsed
+    (convert/utils/ek_raw_parsers.py:1705-1743), or -- ``nan_pad`` -- float32 planes whose short pings end in NaN (what
+    a NaN-padded file holds, convert/parse_base.py:688); ``beam_type`` 1 and the angle parameters per channel."""
+    d = ek60_numpy(C, P, S, seed=seed)
+    rng = np.random.default_rng(seed + 11)
+    for k in ("angle_alongship", "angle_athwartship"):
+        a = rng.integers(-128, 128, (C, P, S)).astype(np.int8)
+        if nan_pad:
+            a = a.astype(np.float32)
+            short = rng.random(P) < 0.2
+            short[0] = True
+            a[:, short, S - S // 7:] = np.nan
+        d[k] = a
+    d["beam_type"] = np.ones(C, dtype=np.int64)
+    d["angle_sensitivity_alongship"] = np.broadcast_to(np.asarray(sens[0], float), (C,)).copy()
+    d["angle_sensitivity_athwartship"] = np.broadcast_to(np.asarray(sens[1], float), (C,)).copy()
+    d["angle_offset_alongship"] = np.broadcast_to(np.asarray(offset[0], float), (C,)).copy()
+    d["angle_offset_athwartship"] = np.broadcast_to(np.asarray(offset[1], float), (C,)).copy()
+    return d
+
 # ---------------------------------------------------------------------------------------- AZFP
 def azfp_numpy(C=4, P=60, S=500, seed=20260507):
     rng = np.random.default_rng(seed)

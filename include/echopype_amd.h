@@ -441,6 +441,42 @@ int epa_sv_complex_fft_indexed(const void* re, const void* im, int in_dtype, con
                                void* range_out, void* prx_out, int out_dtype, int fft_dtype, double* workspace,
                                double* range_stats_out, epa_stream_t stream);
 
+/* ---- split-beam angles: consolidate.add_splitbeam_angle (consolidate/split_beam_angle.py) ----------------
+ * Outputs theta (angle_alongship) and phi (angle_athwartship), [C*P*S] of out_dtype each.  The angle parameters
+ * come as HOST arrays of 4 DEVICE pointers (f64) + their epa_param_mode (scalar, [C] or [C*P]), in the order
+ * angle_sensitivity_alongship, angle_sensitivity_athwartship, angle_offset_alongship, angle_offset_athwartship. */
+#define EPA_I8 2 /* in_dtype of epa_splitbeam_power only: the int8 electrical-angle steps a file stores */
+
+/* Power/angle samples (split_beam_angle.py:121-171): theta = (180/128) * angle_alongship / sensitivity - offset,
+ * phi likewise.  along / athw: [C*P*S] of in_dtype EPA_I8, EPA_F32 or EPA_F64 (NaN padding stays NaN). */
+int epa_splitbeam_power(const void* along, const void* athw, int in_dtype, const double* const* params_host,
+                        const int* modes_host, int C, int P, int S, void* theta, void* phi, int out_dtype,
+                        epa_stream_t stream);
+
+/* Complex samples (split_beam_angle.py:34-118, 174-270): re / im [C*P*S*B] (beam innermost, B = 3 or 4) of
+ * in_dtype F32 / F64.  beam_type_host: HOST [C] int32 -- 1, 17, 49, 65 or 81, or -1 for a channel to skip (its rows
+ * are NaN); C <= 64.  Types 1 / 49 / 65 / 81 need B = 4.
+ * replica / replica_off NULL: no pulse compression (CW; BB without pulse compression) -- a streaming kernel.
+ * Otherwise the combinations of the zero-filled sectors are matched-filtered with the replica (interleaved complex64;
+ * replica_off [n_replicas + 1] in complex elements; replica_id optional [C*P] int32 as in epa_sv_complex_indexed, -1
+ * = no replica: NaN) in the direct form; an angle is NaN where any sector its beam type uses is NaN at the sample.
+ * Computed in out_dtype arithmetic. */
+int epa_splitbeam_complex(const void* re, const void* im, int in_dtype, const int32_t* beam_type_host,
+                          const double* const* params_host, const int* modes_host, const float* replica,
+                          const int32_t* replica_off, const int32_t* replica_id, int n_replicas, int max_taps, int C,
+                          int P, int S, int B, void* theta, void* phi, int out_dtype, epa_stream_t stream);
+
+/* The same with pulse compression through the LDS-resident 2048-point FFT per tile (as epa_sv_complex_fft): replicas
+ * of 1 .. EPA_EK80_NFFT/2 taps.  fft_dtype: arithmetic of the transform.  workspace: f64
+ * [EPA_SPLITBEAM_FFT_WS_DOUBLES(n)] with n = n_replicas when replica_id is given, C otherwise (twiddles and the
+ * replica spectra; rebuilt by every call). */
+#define EPA_SPLITBEAM_FFT_WS_DOUBLES(n) (768 + 3 * (size_t)(n) * EPA_EK80_NFFT)
+int epa_splitbeam_complex_fft(const void* re, const void* im, int in_dtype, const int32_t* beam_type_host,
+                              const double* const* params_host, const int* modes_host, const float* replica,
+                              const int32_t* replica_off, const int32_t* replica_id, int n_replicas, int max_taps,
+                              int C, int P, int S, int B, void* theta, void* phi, int out_dtype, int fft_dtype,
+                              double* workspace, epa_stream_t stream);
+
 /* epa_sv_complex on CW samples (no replica) with {nanmin, nanmax, NaN count} of the echo_range as a by-product
  * (range_stats_out f64 [3]; merged through 1024 slots of f64 atomics in workspace, f64
  * [EPA_SV_COMPLEX_CW_STATS_WS_DOUBLES]); range_out may be NULL: the statistics are then those of the array
