@@ -35,6 +35,7 @@ CCP = ("sample_interval", "tau_nominal", "transmit_power", "sound_speed", "absor
        "beamwidth_athwartship")  # enum epa_ccoef_param
 EK80_NFFT = 2048
 APPLY_MASKS_WS_DOUBLES = 131072  # EPA_APPLY_MASKS_WS_DOUBLES
+SEAFLOOR_STATE_WORDS = 16  # EPA_SEAFLOOR_STATE_WORDS
 
 
 class EpaError(RuntimeError):
@@ -136,6 +137,12 @@ SIGNATURES = {
     "epa_splitbeam_complex_fft": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i,
                                   _vp, _vp],
     "epa_pool_sv_value": [_vp, _vp, _vp, _i, _i, _i, _d, _i, _d, _d, _d, _i, _d, _vp, _vp, _vp, _i, _vp],
+    "epa_seafloor_depth_uniform": [_vp, _i, _i64, _i64, _vp, _vp],
+    "epa_seafloor_basic": [_vp, _i, _i64, _i64, _i64, _d, _d, _vp, _d, _vp, _vp],
+    "epa_seafloor_angle_mask": [_vp, _vp, _i, _i64, _i64, _i64, _i64, _i, _i, _d, _d, _vp, _vp, _vp, _vp],
+    "epa_seafloor_median": [_vp, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    "epa_seafloor_components": [_vp, _i, _i64, _i64, _i64, _i64, _d, _vp, _vp, _vp, _vp],
+    "epa_seafloor_bottom": [_vp, _vp, _i64, _i64, _i64, _vp, _d, _vp, _i, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

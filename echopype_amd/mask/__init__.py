@@ -1,3 +1,3 @@
-from .api import apply_mask  # noqa: F401
+from .api import METHODS_BOTTOM, apply_mask, detect_seafloor  # noqa: F401
 
-__all__ = ["apply_mask"]
+__all__ = ["apply_mask", "detect_seafloor", "METHODS_BOTTOM"]

@@ -184,3 +184,26 @@ def apply_mask(source_ds, mask, var_name="Sv", fill_value=np.nan, storage_option
     prov["mask_function"] = "mask.apply_mask"
     output_ds.attrs.update(prov)
     return insert_processing_level(output_ds, "L3*", input_ds=source_ds)
+
+
+# ---- seafloor detection (reference: mask/api.py:866-945) ------------------------------------------------------------
+from .seafloor_detection.bottom_basic import bottom_basic  # noqa: E402
+from .seafloor_detection.bottom_blackwell import bottom_blackwell  # noqa: E402
+
+# Registry of supported methods for bottom detection
+METHODS_BOTTOM = {
+    "basic": bottom_basic,
+    "blackwell": bottom_blackwell,
+}
+
+
+def detect_seafloor(ds, method, params):
+    """Dispatch seafloor detection to a chosen method and return a 1-D bottom line (``bottom_depth`` per
+    ``ping_time``, data on the device).  ``method``: ``"basic"`` (threshold-only) or ``"blackwell"`` (Sv + split-beam
+    angles); ``params``: that method's keyword arguments, omitted ones take its defaults (see
+    seafloor_detection.bottom_basic / bottom_blackwell).  Sharded datasets are not supported.
+
+    Raises ValueError if ``method`` is not supported."""
+    if method not in METHODS_BOTTOM:
+        raise ValueError(f"Unsupported bottom detection method: {method}")
+    return METHODS_BOTTOM[method](ds, **params)

@@ -786,6 +786,76 @@ def splitbeam_complex(re, im, beam_type, params, *, replica=None, replica_off=No
              _p(replica_id), n_rep, int(max_taps), C, P, S, B, _p(theta), _p(phi), _DT[dtype], _stream())
     return theta, phi
 
+# ---- seafloor detection (mask.detect_seafloor) ------------------------------------------------------------------------
+def _plane_dtype(t, what):
+    if t.dim() != 2 or t.dtype not in _DT:
+        raise ValueError(f"{what}: a (ping_time, range_sample) float32 / float64 plane expected, got {tuple(t.shape)} "
+                         f"{t.dtype}")
+    return _DT[t.dtype]
+
+
+def seafloor_state(device):
+    """The zeroed u64 state words of one Blackwell call (int64 tensor of EPA_SEAFLOOR_STATE_WORDS)."""
+    return torch.zeros(_lib.SEAFLOOR_STATE_WORDS, dtype=torch.int64, device=device)
+
+
+def seafloor_depth_uniform(depth):
+    """-> int32 device tensor (1,): the pings of ``depth`` (P, S) whose grid differs from ping 0 (utils._check_inputs)."""
+    bad = torch.zeros(1, dtype=torch.int32, device=depth.device)
+    P, S = depth.shape
+    call("epa_seafloor_depth_uniform", _p(depth), _plane_dtype(depth, "depth"), P, S, _p(bad), _stream())
+    return bad
+
+
+def seafloor_basic(sv, skip, tmin, tmax, depth0, offset):
+    """bottom_basic on one channel: ``sv`` (P, S), ``depth0`` f64 (S,) -> f64 (P,) bottom depths."""
+    P, S = sv.shape
+    out = torch.empty(P, dtype=torch.float64, device=sv.device)
+    call("epa_seafloor_basic", _p(sv), _plane_dtype(sv, "Sv"), P, S, int(skip), float(tmin), float(tmax),
+         _p(depth0), float(offset), _p(out), _stream())
+    return out
+
+
+def seafloor_angle_mask(theta, phi, r0, R, wtheta, wphi, ttheta, tphi, state):
+    """The Blackwell angle mask of the crop [r0, r0 + R) -> u8 (P, R); adds the masked count to ``state[0]``."""
+    P, S = theta.shape
+    if phi.shape != theta.shape or phi.dtype != theta.dtype:
+        raise ValueError("angle_alongship / angle_athwartship: same shape and dtype")
+    work = torch.empty(2 * P * R, dtype=torch.float64, device=theta.device)
+    mask = torch.empty((P, R), dtype=torch.uint8, device=theta.device)
+    call("epa_seafloor_angle_mask", _p(theta), _p(phi), _plane_dtype(theta, "angles"), P, S, int(r0), int(R),
+         int(wtheta), int(wphi), float(ttheta), float(tphi), _p(work), _p(mask), _p(state), _stream())
+    return mask
+
+
+def seafloor_median(sv, r0, R, mask, state):
+    """Radix-select the one or two middle values of the non-NaN ``sv`` crop under ``mask`` into ``state``."""
+    P, S = sv.shape
+    hist = torch.empty(512, dtype=torch.int64, device=sv.device)
+    call("epa_seafloor_median", _p(sv), _plane_dtype(sv, "Sv"), P, S, int(r0), int(R), _p(mask), _p(state), _p(hist),
+         _stream())
+
+
+def seafloor_components(sv, r0, R, threshold, mask, state):
+    """8-connected components of the ``sv`` crop above ``threshold``; marks the roots of those meeting the angle mask
+    (bit 1 of ``mask``) -> int64 (P, R) roots, -1 for background."""
+    P, S = sv.shape
+    parent = torch.empty((P, R), dtype=torch.int64, device=sv.device)
+    call("epa_seafloor_components", _p(sv), _plane_dtype(sv, "Sv"), P, S, int(r0), int(R), float(threshold),
+         _p(mask), _p(parent), _p(state), _stream())
+    return parent
+
+
+def seafloor_bottom(parent, mask, P, r0, depth0, offset, dtype):
+    """Per ping: depth0 of the first kept crop sample minus ``offset`` (depth0[0] - offset without one; ``parent`` None:
+    nothing is kept) -> (P,) of ``dtype``."""
+    out = torch.empty(P, dtype=dtype, device=depth0.device)
+    R = 0 if parent is None else parent.shape[1]
+    call("epa_seafloor_bottom", _p(parent), _p(mask), P, R, int(r0), _p(depth0), float(offset), _p(out), _DT[dtype],
+         _stream())
+    return out
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

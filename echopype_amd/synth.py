@@ -327,3 +327,78 @@ def azfp_numpy(C=4, P=60, S=500, seed=20260507):
         temperature=np.full(P, 8.5), salinity=29.6, pressure=60.0,
         ping_time=T0 + (p * 3_000_000_000).astype("timedelta64[ns]"),
     )
+
+
+# ------------------------------------------------------------------------------------- seafloor scenes (mask.detect_seafloor)
+def seafloor_scene(P=120, S=160, seed=20261017, dtype=np.float64, dz=0.5, band_top=110, slope=-0.1, thickness=6,
+                   band_angle=(8.0, -6.0), noise_angle=2.0, nan_pad=True):
+    """One channel's (ping_time, range_sample) planes of a seabed scene -> dict sv, theta, phi, depth (P, S):
+    - a sloped bottom band (Sv about -25 dB) whose angles are coherent (``band_angle`` + small noise);
+    - a fish school above it (bright Sv, zero-mean noisy angles);
+    - a chain of single pixels linked only diagonally, from the band's top up to a bright patch far above it (kept only
+      under 8-connectivity: the angle mask reaches neither the patch nor the chain's upper part);
+    - a bright patch that touches nothing;
+    - NaN padding at the end of every seventh ping (Sv and angles; depth stays uniform).
+    Background Sv about -90 dB, angles zero-mean with ``noise_angle`` spread.  ``band_top`` / ``slope``: first band
+    sample of ping 0 and its drift in samples per ping."""
+    rng = np.random.default_rng(seed)
+    sv = -90.0 + 3.0 * rng.standard_normal((P, S))
+    theta = noise_angle * rng.standard_normal((P, S))
+    phi = noise_angle * rng.standard_normal((P, S))
+    top = np.clip(np.round(band_top + slope * np.arange(P)).astype(int), 0, S - thickness)
+    for p in range(P):
+        b = slice(top[p], top[p] + thickness)
+        sv[p, b] = -25.0 + rng.standard_normal(thickness)
+        theta[p, b] = band_angle[0] + 0.05 * rng.standard_normal(thickness)
+        phi[p, b] = band_angle[1] + 0.05 * rng.standard_normal(thickness)
+    # fish school: pings P/8 .. 3P/8, samples S/8 .. S/4
+    sv[P // 8:3 * P // 8, S // 8:S // 4] = -45.0 + 2.0 * rng.standard_normal((3 * P // 8 - P // 8, S // 4 - S // 8))
+    # diagonal chain up and forward from the band top at ping pc, then a 3 x 3 patch at its end
+    pc = P // 2
+    n_chain = min(40, top[pc] - 8, P - pc - 6)
+    for j in range(1, n_chain + 1):
+        sv[pc + j, top[pc] - j] = -30.0
+        # keep the chain diagonal-only: its 4-neighbours off the band are background
+        for (a, b) in ((pc + j - 1, top[pc] - j), (pc + j, top[pc] - j + 1)):
+            if b < top[a]:
+                sv[a, b] = -90.0
+    pe, re = pc + n_chain, top[pc] - n_chain
+    sv[pe + 1:pe + 4, re - 3:re] = -30.0  # the patch: diagonal to the chain's last pixel (pe, re)
+    sv[pe + 1:pe + 4, re] = -90.0
+    sv[pe, re - 3:re] = -90.0
+    # a patch that touches nothing, high above the band
+    q = 3 * P // 4
+    sv[q:q + 4, S // 16:S // 16 + 4] = -28.0
+    depth = np.tile(np.arange(S) * dz, (P, 1))
+    if nan_pad:
+        for p in range(3, P, 7):
+            sv[p, S - S // 9:] = np.nan
+            theta[p, S - S // 9:] = np.nan
+            phi[p, S - S // 9:] = np.nan
+    return {"sv": sv.astype(dtype), "theta": theta.astype(dtype), "phi": phi.astype(dtype), "depth": depth.astype(dtype),
+            "top": top}
+
+
+def ek60_seafloor_numpy(C=2, P=96, S=400, seed=20261018, band_top=300, slope=-0.5, thickness=8):
+    """``ek60_splitbeam_numpy`` (its own streams, unchanged) with a seabed written into the raw samples of every
+    channel: a sloped band of strong power whose int8 electrical-angle steps are coherent (+40 / -30 steps), over
+    the generator's noise (random steps elsewhere).  For the whole chain from_ek60_arrays -> compute_Sv -> add_depth
+    -> add_splitbeam_angle -> detect_seafloor."""
+    d = ek60_splitbeam_numpy(C, P, S, seed=seed)
+    # the operator's sound speed held for the whole file: the depth grid is the same in every ping (the detectors
+    # refuse a grid that varies)
+    d["sound_speed_indicative"] = np.repeat(d["sound_speed_indicative"][:, :1], P, axis=1)
+    rng = np.random.default_rng(seed + 5)
+    top = np.clip(np.round(band_top + slope * np.arange(P)).astype(int), 0, S - thickness)
+    power = np.array(d["backscatter_r"], copy=True)
+    al = np.array(d["angle_alongship"], copy=True)
+    at = np.array(d["angle_athwartship"], copy=True)
+    hi = float(np.nanmax(power)) + 30.0
+    for p in range(P):
+        b = slice(top[p], top[p] + thickness)
+        power[:, p, b] = (hi + rng.standard_normal((C, thickness))).astype(power.dtype)
+        al[:, p, b] = 40
+        at[:, p, b] = -30
+    d["backscatter_r"], d["angle_alongship"], d["angle_athwartship"] = power, al, at
+    d["seafloor_top"] = top
+    return d

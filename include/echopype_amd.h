@@ -659,6 +659,48 @@ int epa_sv_denoise_mvbs(const float* raw, const double* coef, const double* alph
                         void* sv_noise_out, void* sv_corrected_out, void* range_out, void* mvbs_out,
                         void* sum_out, uint32_t* cnt_out, double* minmax_out, int dtype, epa_stream_t stream);
 
+/* ---- seafloor detection: mask.detect_seafloor (mask/seafloor_detection/) -----------------------------------------
+ * One channel's (ping, range) planes: sv / theta / phi / depth are [P*S] of dtype F32 / F64, row by ping.  A crop is
+ * the range samples [r0, r0 + R) of every ping.  depth0: f64 [S], the channel's depth at ping 0.  state: u64
+ * [EPA_SEAFLOOR_STATE_WORDS], zeroed by the caller: [0] pixels under the angle mask, [1] non-NaN Sv values under it,
+ * [6] / [7] the lower / upper middle of those values (f64 bits), [8] union-find loops that reached their bound
+ * (non-zero: the components are not to be trusted). */
+#define EPA_SEAFLOOR_STATE_WORDS 16
+
+/* utils.py:_check_inputs: *bad_pings (device int, zeroed by the caller) += the pings whose max over range of
+ * |depth - depth[ping 0]| (NaN skipped) is not < 1e-16 in the array's type, or is NaN. */
+int epa_seafloor_depth_uniform(const void* depth, int dtype, long long P, long long S, int* bad_pings,
+                               epa_stream_t stream);
+
+/* bottom_basic.py: out (f64 [P]) = depth0[s] - offset for the first s >= skip with tmin < sv < tmax (the bounds
+ * rounded to dtype first, as NumPy compares them), s = skip where no sample matches; 0 <= skip < S. */
+int epa_seafloor_basic(const void* sv, int dtype, long long P, long long S, long long skip, double tmin, double tmax,
+                       const double* depth0, double offset, double* out, epa_stream_t stream);
+
+/* bottom_blackwell.py, angle mask: mask (u8 [P*R]) = 1 where mean_w(theta)^2 > ttheta or mean_w(phi)^2 > tphi, the
+ * means over wtheta^2 / wphi^2 windows of convolve2d(..., "same", boundary="symm") on the crop; state[0] += the
+ * count.  work: f64 [2*P*R]. */
+int epa_seafloor_angle_mask(const void* theta, const void* phi, int dtype, long long P, long long S, long long r0,
+                            long long R, int wtheta, int wphi, double ttheta, double tphi, double* work,
+                            unsigned char* mask, unsigned long long* state, epa_stream_t stream);
+
+/* The one or two middle values of the non-NaN sv under mask (radix select on the crop): state[1], [6], [7].
+ * hist: u64 [512]. */
+int epa_seafloor_median(const void* sv, int dtype, long long P, long long S, long long r0, long long R,
+                        const unsigned char* mask, unsigned long long* state, unsigned long long* hist,
+                        epa_stream_t stream);
+
+/* 8-connected components of sv > threshold (threshold rounded to dtype) on the crop: parent (i64 [P*R]) = the root
+ * of each foreground pixel, -1 elsewhere; bit 1 of mask[root] set for every component with a pixel under the mask. */
+int epa_seafloor_components(const void* sv, int dtype, long long P, long long S, long long r0, long long R,
+                            double threshold, unsigned char* mask, long long* parent, unsigned long long* state,
+                            epa_stream_t stream);
+
+/* out [P] of out_dtype = depth0[r0 + i] - offset for the first crop sample i of each ping whose component is kept,
+ * depth0[0] - offset where there is none; parent == NULL: depth0[0] - offset for every ping. */
+int epa_seafloor_bottom(const long long* parent, const unsigned char* mask, long long P, long long R, long long r0,
+                        const double* depth0, double offset, void* out, int out_dtype, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
