@@ -23,6 +23,7 @@ __all__ = [
     "range_azfp",
     "tvg_range_ek",
     "cal_power_ek",
+    "cal_power_ek_terms",
     "cal_complex_ek80",
     "cal_azfp",
     "b_theta_phi_m",
@@ -161,6 +162,57 @@ def cal_power_ek(
         else:
             raise ValueError(cal_type)
     return out.astype(np.float64), R
+
+
+def cal_power_ek_terms(
+    backscatter_r,
+    *,
+    sonar,
+    cal_type,
+    sample_interval,
+    sound_speed,
+    absorption,
+    transmit_power,
+    tau_nominal,
+    gain,
+    sa_correction,
+    psi,
+    f_nominal,
+    tau_eff,
+    gpt=None,
+):
+    """The terms ``cal_power_ek`` adds, returned separately (float64; same arguments).
+
+    out = raw + spreading + absorb + const  with  spreading = nspread*log10(R'), absorb = 2*alpha*R',
+    const = -CSv - 2*sa_correction (Sv) or -CSp (TS); R' <= 0 -> NaN in spreading and absorb.  ``k`` = the range of
+    one sample (range.py:138, sample_interval * sound_speed / 2) as (C, P, 1), ``nspread`` = 20 (Sv) or 40 (TS).
+    For error models that weigh each term's size: ``cal_power_ek`` itself is unchanged."""
+    C, P, S = backscatter_r.shape
+    cw = _cp(sound_speed, C, P)
+    R = range_ek(backscatter_r, sample_interval, sound_speed)
+    wavelength = cw / _cp(f_nominal, C, P)
+    Rt = tvg_range_ek(R, sonar, sample_interval, sound_speed, tau_nominal, gpt)
+    nspread = {"Sv": 20.0, "TS": 40.0}[cal_type]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        Rt = np.where(Rt > 0, Rt, np.nan)
+        spreading = nspread * np.log10(Rt)
+        absorb = 2 * _cp(absorption, C, P) * Rt
+        if cal_type == "Sv":
+            const = -(
+                10 * np.log10(_cp(transmit_power, C, P))
+                + 2 * _cp(gain, C, P)
+                + _cp(psi, C, P)
+                + 10 * np.log10(wavelength**2 * _cp(tau_eff, C, P) * cw / (32 * np.pi**2))
+            ) - 2 * _cp(sa_correction, C, P)
+        else:
+            const = -(
+                10 * np.log10(_cp(transmit_power, C, P))
+                + 2 * _cp(gain, C, P)
+                + 10 * np.log10(wavelength**2 / (16 * np.pi**2))
+            )
+    k = _cp(sample_interval, C, P) * cw / 2
+    return {"raw": np.asarray(backscatter_r, np.float64), "spreading": spreading, "absorb": absorb,
+            "const": np.broadcast_to(const, (C, P, S)), "Rt": Rt, "k": k, "nspread": nspread}
 
 
 def b_theta_phi_m(off_along, off_athwart, bw_along, bw_athwart):

@@ -7,6 +7,17 @@ from oracle import ek80 as oek
 from oracle import uwa as ouwa
 
 
+def ek60_kw(d, cal_type="Sv"):
+    """The keyword arguments ``ek60`` passes to ``cal_power_ek`` (Environment group values, table-looked-up gain)."""
+    g = ocal.vend_cal_params_power(d["transmit_duration_nominal"], d["pulse_length"], d["gain_correction"])
+    sa = ocal.vend_cal_params_power(d["transmit_duration_nominal"], d["pulse_length"], d["sa_correction"])
+    return dict(sonar="EK60", cal_type=cal_type, sample_interval=d["sample_interval"],
+                sound_speed=d["sound_speed_indicative"], absorption=d["absorption_indicative"],
+                transmit_power=d["transmit_power"], tau_nominal=d["transmit_duration_nominal"], gain=g,
+                sa_correction=sa, psi=d["equivalent_beam_angle"], f_nominal=d["frequency_nominal"],
+                tau_eff=d["transmit_duration_nominal"][:, 0])
+
+
 def ek60(d, cal_type="Sv", env=None, gain=None):
     """compute_Sv/compute_TS on an EK60 file: env from the Environment group unless T,S,P,pH are
     all user-supplied (env_params.py:270-340); gain/sa by pulse-length lookup unless given."""

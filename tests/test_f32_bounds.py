@@ -1,0 +1,345 @@
+"""CPU self-test of the float32 error bounds of tests/f32_bounds.py.
+
+Soundness: a NumPy float32 emulation of each kernel's operation order stays within its bound on random and adversarial
+inputs.  An fma is emulated as the float64 product-sum rounded once to float32; that double rounding is off from a true
+fma by at most 2^-53 relative, which the bounds' float64 slack absorbs.  Order-free sums are emulated in several orders.
+Sharpness: each perturbation the float32 bar of 1e-3 could not see FAILS the new check and still PASSES the old bar."""
+import warnings
+
+import numpy as np
+import pytest
+
+import f32_bounds as fb
+from echopype_amd import synth
+from oracle import calibrate as ocal
+from oracle import clean as oclean
+
+f32 = np.float32
+
+
+def _old_ok(got, exp):
+    got, exp = np.asarray(got, np.float64), np.asarray(exp, np.float64)
+    f = np.isfinite(exp)
+    return bool(np.all(np.abs(got[f] - exp[f]) / np.maximum(np.abs(exp[f]), 1.0) <= fb.OLD_RTOL))
+
+
+def _new_ok(got, exp, bound):
+    """False only when the check fails on the bound itself (NaN pattern, a missing bound or the old bar re-raise)."""
+    try:
+        fb.assert_f32_close(got, exp, bound)
+        return True
+    except AssertionError as e:
+        if "dB > bound" in str(e):
+            return False
+        raise
+
+
+def _ek60_case(C=2, P=12, S=3000, cal_type="Sv", si_scale=1.0, seed=5):
+    d = synth.ek60_numpy(C, P, S, seed=seed)
+    d["sample_interval"] = d["sample_interval"] * si_scale
+    gain = ocal.vend_cal_params_power(d["transmit_duration_nominal"], d["pulse_length"], d["gain_correction"])
+    sa = ocal.vend_cal_params_power(d["transmit_duration_nominal"], d["pulse_length"], d["sa_correction"])
+    kw = dict(sonar="EK60", cal_type=cal_type, sample_interval=d["sample_interval"],
+              sound_speed=d["sound_speed_indicative"], absorption=d["absorption_indicative"],
+              transmit_power=d["transmit_power"], tau_nominal=d["transmit_duration_nominal"], gain=gain,
+              sa_correction=sa, psi=d["equivalent_beam_angle"], f_nominal=d["frequency_nominal"],
+              tau_eff=d["transmit_duration_nominal"][:, 0])
+    return d, kw
+
+
+def _emulate_cal_power(raw, kw):
+    """cal_power_sample<float> (csrc/sample_math.h:62-75) over the row constants power_coef_ek_kernel computes in
+    double (csrc/power_coef.hip:51-92), EK60 (d = 2, g = 1)."""
+    C, P, S = raw.shape
+    terms = ocal.cal_power_ek_terms(raw.astype(np.float64), **kw)
+    si = np.broadcast_to(np.asarray(kw["sample_interval"], np.float64).reshape(C, -1), (C, P))[:, :, None]
+    cw = np.broadcast_to(np.asarray(kw["sound_speed"], np.float64).reshape(C, -1), (C, P))[:, :, None]
+    k = si * cw / 2
+    shift = 2 * si * cw / 2
+    A = terms["const"][:, :, :1]
+    n = terms["nspread"]
+    A0 = (A + n * np.log10(k)).astype(f32)
+    alpha2 = (2 * np.broadcast_to(np.asarray(kw["absorption"], np.float64).reshape(C, -1), (C, P))[:, :, None]).astype(f32)
+    s = np.arange(S, dtype=np.float64)[None, None, :]
+    R = (s * si) * (cw / 2)
+    rtd = R - shift
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nL = (f32(n) * np.log10((s - 2.0).astype(f32))).astype(f32)
+        a = (raw.astype(np.float64) + nL.astype(np.float64)).astype(f32)                            # fma(g, raw, nL)
+        b = (alpha2.astype(np.float64) * rtd.astype(f32) + A0.astype(np.float64)).astype(f32)        # fma(a2, rt, A0)
+        out = (a + b).astype(f32)
+    out = np.where(rtd > 0, out, np.nan)
+    return out, terms
+
+
+@pytest.mark.parametrize("cal_type", ["Sv", "TS"])
+@pytest.mark.parametrize("si_scale", [1.0, 40.0])     # 40 x: 3000 samples reach ~4.4 km
+def test_sv_power_emulation_within_bound(cal_type, si_scale):
+    d, kw = _ek60_case(cal_type=cal_type, si_scale=si_scale)
+    raw = d["backscatter_r"].copy()
+    raw[0, 0, :] = np.float32(60.0)          # strong targets: positive dB, where the old bar is absolute
+    raw[1, 1, ::7] = np.float32(-150.0)
+    out, terms = _emulate_cal_power(raw, kw)
+    exp, _ = ocal.cal_power_ek(raw.astype(np.float64), **kw)
+    exp = np.where(np.isnan(raw), np.nan, exp)
+    b = fb.sv_power_bound(terms, exp)
+    err, ratio = fb.assert_f32_close(np.where(np.isnan(raw), np.nan, out), exp, b, f"emulated {cal_type}")
+    assert 0 < ratio <= 1.0
+
+
+def _emulate_mean(sv32, labels, nbins, order):
+    """lin = exp10f(v * 0.1f) (rounded float64 10^x: 0.5 ulp), float32 sums in the given member order, s / n,
+    10 * log10f."""
+    v = sv32.ravel()
+    lab = labels.ravel()
+    use = (lab >= 0) & ~np.isnan(v)
+    arg = (v.astype(np.float64) * np.float64(f32(0.1))).astype(f32)
+    lin = (10.0 ** arg.astype(np.float64)).astype(f32)
+    idx = np.flatnonzero(use)
+    if order == "reverse":
+        idx = idx[::-1]
+    elif order == "random":
+        idx = np.random.default_rng(1).permutation(idx)
+    s = np.zeros(nbins, f32)
+    n = np.zeros(nbins, np.int64)
+    if order == "pairwise":  # tree: sort by bin, sum each bin pairwise in float32
+        for bi in np.unique(lab[idx]):
+            m = lin[idx[lab[idx] == bi]].astype(f32)
+            while m.size > 1:
+                if m.size % 2:
+                    m = np.append(m, f32(0))
+                m = (m[0::2] + m[1::2]).astype(f32)
+            s[bi] = m[0]
+            n[bi] = int((lab[idx] == bi).sum())
+    else:
+        for i in idx:  # float32 accumulation, one term at a time
+            s[lab[i]] = f32(s[lab[i]] + lin[i])
+            n[lab[i]] += 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = (s / n.astype(f32)).astype(f32)
+        out = (f32(10) * np.log10(mean)).astype(f32)
+    return np.where(n > 0, out, np.nan)
+
+
+@pytest.mark.parametrize("field", ["random", "spike60", "constant", "deep"])
+@pytest.mark.parametrize("order", ["forward", "reverse", "random", "pairwise"])
+def test_bin_mean_emulation_within_bound(field, order):
+    rng = np.random.default_rng(7)
+    C, P, S = 1, 8, 2500
+    if field == "random":
+        sv = rng.uniform(-120, 10, (C, P, S))
+    elif field == "spike60":
+        sv = np.full((C, P, S), -90.0)
+        sv[:, :, ::500] = -30.0                      # 60 dB above the rest of its bin
+    elif field == "constant":
+        sv = np.full((C, P, S), -63.3)
+    else:
+        sv = rng.uniform(-330, -300, (C, P, S))     # 10^(Sv/10) near the float32 normal floor
+    sv32 = sv.astype(f32)
+    lab, nb = fb.labels_index(C, P, S, 4, 500)      # 2000-sample bins
+    got = _emulate_mean(sv32, lab, nb, order)
+    with np.errstate(divide="ignore"):
+        exp = np.array([10 * np.log10(np.mean(10.0 ** (sv32.astype(np.float64).ravel()[lab.ravel() == i] / 10)))
+                        for i in range(nb)])
+    b = fb.mvbs_bound(sv32.astype(np.float64), lab, nb, exp)
+    fb.assert_f32_close(got, exp, b, f"bin mean {field} {order}")
+    if field == "constant":  # the known answer
+        assert np.all(np.abs(got - float(sv32[0, 0, 0])) <= b)
+
+
+def test_gamma_is_order_free_and_grows_with_n():
+    assert fb.gamma(0) == 0.0
+    assert fb.gamma(10**6 - 1) > 1000 * fb.gamma(999)
+    assert np.isinf(fb.gamma(2**25))
+
+
+def _noise_case():
+    d, kw = _ek60_case(C=2, P=40, S=400)
+    sv, er = ocal.cal_power_ek(d["backscatter_r"], **kw)
+    sv = sv.astype(f32).astype(np.float64)       # the float32 values a kernel reads
+    er = er.astype(f32).astype(np.float64)
+    alpha = d["absorption_indicative"]
+    return sv, er, alpha
+
+
+def test_noise_removal_emulation_within_bound():
+    sv, er, alpha = _noise_case()
+    C, P, S = sv.shape
+    nb = np.array([[-140.0, -138.3], [-141.1, -139.9]])                     # the noise per 20-ping block
+    a2 = 2 * np.asarray(alpha, np.float64)[:, :, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tl = 20 * np.log10(np.where(er >= 1, er, 1)) + a2 * er
+        sn_exp = nb[:, np.arange(P) // 20][:, :, None] + tl
+        # place samples just above the threshold: cancellation
+        sv[0, 3, 100:110] = sn_exp[0, 3, 100:110] + 3.0 + np.array([0.1, -0.1, 1e-3, -1e-3, 1e-5, -1e-5, -2.99, -2.99,
+                                                                    0.5, 6.0])
+        sv = sv.astype(f32).astype(np.float64)
+        lin_exp = 10 ** (sv / 10) - 10 ** (sn_exp / 10)
+        corr = 10 * np.log10(np.where(lin_exp > 0, lin_exp, np.nan))
+        corr_exp = np.where(corr - sn_exp > 3.0, corr, np.nan)
+        # emulation (noise_apply.hip:58-63)
+        x = er.astype(f32)
+        tlf = (f32(20) * np.log10(np.where(x >= 1, x, f32(1))).astype(f32)).astype(f32)
+        tlf = (tlf.astype(np.float64) + a2.astype(f32).astype(np.float64) * x).astype(f32)
+        snf = (nb[:, np.arange(P) // 20][:, :, None].astype(f32) + tlf).astype(f32)
+
+        def lin(v):
+            return (10.0 ** (v.astype(np.float64) * np.float64(f32(0.1))).astype(f32).astype(np.float64)).astype(f32)
+
+        linf = (lin(sv.astype(f32)) - lin(snf)).astype(f32)
+        cf = np.where(linf > 0, (f32(10) * np.log10(linf)).astype(f32), np.nan).astype(f32)
+        cf = np.where(cf - snf > f32(3.0), cf, np.nan)
+    b_sn, b_c = fb.noise_bounds(sv, er, a2, nb, np.zeros_like(nb), 20, sn_exp, lin_exp)
+    fb.assert_f32_close(snf, sn_exp, b_sn, "emulated Sv_noise")
+    keep_g, keep_e = ~np.isnan(cf), ~np.isnan(corr_exp)
+    margin = corr - sn_exp - 3.0
+    fb.check_decisions(keep_g, keep_e, margin, b_c + b_sn + fb.U * np.abs(corr - sn_exp))
+    both = keep_g & keep_e
+    fb.assert_f32_close(np.where(both, cf, np.nan), np.where(both, corr_exp, np.nan), b_c, "emulated Sv_corrected")
+    # the condition number shows: 3 dB above the noise costs a factor 2, 0.01 dB (index 106) a factor ~430
+    kappa = 10 ** (sv / 10) / lin_exp
+    assert kappa[0, 3, 106] > 400 and b_c[0, 3, 106] > 100 * b_c[0, 3, 109]
+
+
+def test_cw_complex_emulation_within_bound():
+    rng = np.random.default_rng(3)
+    C, P, S, B = 1, 3, 2000, 4
+    re = (rng.standard_normal((C, P, S, B)) * 1e-3).astype(f32)
+    im = (rng.standard_normal((C, P, S, B)) * 1e-3).astype(f32)
+    re[0, 0, :50] = np.array([1e-2, -1e-2 + 1e-7, 1e-6, 0], f32)            # sectors that nearly cancel
+    im[0, 0, :50] = np.array([1e-2, -1e-2, 0, 1e-8], f32)
+    pscale, alpha2, A, shift, si, cw, n = 4 / 8 * 1.3, 0.02, 150.0, 0.5, 2e-4, 1500.0, 20.0
+    s = np.arange(S, dtype=np.float64)[None, None, :]
+    R = (s * si) * (cw / 2)
+    Rt = np.where(R - shift > 0, R - shift, np.nan)
+    x = re.astype(np.float64) + 1j * im.astype(np.float64)
+    prx = pscale * np.abs(x.mean(-1)) ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        exp = 10 * np.log10(prx) + n * np.log10(Rt) + alpha2 * Rt + A
+        sr = np.zeros((C, P, S), f32)
+        si_ = np.zeros((C, P, S), f32)
+        for b in range(B):
+            sr = (sr + re[..., b]).astype(f32)
+            si_ = (si_ + im[..., b]).astype(f32)
+        invn = f32(1) / f32(B)
+        mr, mi = (sr * invn).astype(f32), (si_ * invn).astype(f32)
+        q = (mr.astype(np.float64) * mr + (mi * mi).astype(f32)).astype(f32)
+        pf = (f32(pscale) * q).astype(f32)
+        rt = (R.astype(f32) - f32(shift)).astype(f32)
+        rt = np.where(rt > 0, rt, np.nan).astype(f32)
+        val = (f32(10) * np.log10(pf)).astype(f32) + (f32(n) * np.log10(rt)).astype(f32)
+        val = val.astype(f32)
+        val = (val + (f32(alpha2) * rt).astype(f32)).astype(f32)
+        val = (val + f32(A)).astype(f32)
+    val = np.where(np.isnan(Rt), np.nan, val)
+    b = fb.cw_complex_bound(re.astype(np.float64), im.astype(np.float64), prx, exp, Rt, R, shift, alpha2,
+                            np.full(exp.shape, A), n)
+    fb.assert_f32_close(val, exp, b, "emulated CW")
+    assert b[0, 0, 10] > 100 * np.nanmedian(b)        # the cancelling sectors carry the condition number
+
+
+# ---------------------------------------------------------------------------------------------------- sharpness
+def _sv_oracle_and_bound(cal_type="Sv"):
+    d, kw = _ek60_case(cal_type=cal_type)
+    raw = d["backscatter_r"].astype(np.float64)
+    exp, _ = ocal.cal_power_ek(raw, **kw)
+    terms = ocal.cal_power_ek_terms(raw, **kw)
+    return exp, terms, fb.sv_power_bound(terms, exp)
+
+
+def _assert_sharp(bad, exp, bound):
+    # perturbed where |exp| >= 50 dB (the Sv / TS of real data): closer to 0 dB the old bar is 1e-3 dB absolute
+    bad = np.where(np.abs(exp) >= 50, bad, exp)
+    assert _old_ok(bad, exp), "the perturbation must pass the old 1e-3 bar"
+    assert not _new_ok(bad, exp, bound), "the perturbation must fail the derived bound"
+
+
+def test_sharp_absorption_at_previous_sample():
+    exp, terms, b = _sv_oracle_and_bound()
+    bad = exp - terms["absorb"] + terms["absorb"] * (terms["Rt"] - terms["k"]) / terms["Rt"]
+    _assert_sharp(bad, exp, b)
+
+
+def test_sharp_range_one_sample_beyond_50m():
+    exp, terms, b = _sv_oracle_and_bound()
+    Rt, k, n = terms["Rt"], terms["k"], terms["nspread"]
+    far = Rt > 50
+    with np.errstate(invalid="ignore"):
+        moved = exp - terms["spreading"] - terms["absorb"] + n * np.log10(Rt + k) + terms["absorb"] * (Rt + k) / Rt
+    _assert_sharp(np.where(far, moved, exp), exp, b)
+
+
+def test_sharp_constant_offset():
+    exp, terms, b = _sv_oracle_and_bound("TS")
+    _assert_sharp(exp + 0.01, exp, b)
+
+
+def test_sharp_linear_power_times_1_plus_1e_3():
+    exp, terms, b = _sv_oracle_and_bound()
+    _assert_sharp(exp + 10 * np.log10(1 + 1e-3), exp, b)
+
+
+def test_sharp_bin_drops_one_sample():
+    rng = np.random.default_rng(11)
+    C, P, S = 1, 1, 400
+    sv = (-70 + rng.normal(0, 0.3, (C, P, S))).astype(f32).astype(np.float64)   # non-flat field, 20-sample bins
+    lab, nb = fb.labels_index(C, P, S, 1, 20)
+    L = 10 ** (sv.ravel() / 10)
+    exp = 10 * np.log10(np.bincount(lab.ravel(), L) / np.bincount(lab.ravel()))
+    drop = L.reshape(nb, 20)[:, :-1]                                           # the last sample of every bin lost
+    bad = 10 * np.log10(drop.mean(1))
+    _assert_sharp(bad, exp, fb.mvbs_bound(sv, lab, nb, exp))
+
+
+def test_sharp_noise_flip_half_a_db_from_threshold():
+    rng = np.random.default_rng(2)
+    sv, er, alpha = _noise_case()
+    exp_n, exp_c = oclean.remove_background_noise(sv, er, alpha, 20, 50, SNR_threshold="3.0dB")
+    with np.errstate(invalid="ignore"):
+        margin = (10 * np.log10(np.maximum(10 ** (sv / 10) - 10 ** (exp_n / 10), 1e-300))) - exp_n - 3.0
+    keep = ~np.isnan(exp_c)
+    cand = np.flatnonzero(np.isfinite(margin) & (np.abs(np.abs(margin) - 0.5) < 0.05))
+    assert cand.size
+    flipped = keep.copy().ravel()
+    i = rng.choice(cand)
+    flipped[i] = ~flipped[i]
+    flipped = flipped.reshape(keep.shape)
+    assert (flipped != keep).mean() < 1e-3                                      # the old fraction limit passes
+    # the derived bound of the compared quantity corr - Sv_noise, as the GPU tests compute it
+    C, P, S = sv.shape
+    a2 = 2 * np.asarray(alpha, np.float64)[:, :, None]
+    with np.errstate(invalid="ignore", divide="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        tl = 20 * np.log10(np.where(er >= 1, er, 1)) + a2 * er
+        blocks = 10 * np.log10(oclean.coarsen_mean(10 ** ((sv - tl) / 10), 20, 50))
+        nb_exp = np.nanmin(blocks, axis=2)
+        b_nb = fb.noise_estimate_bound(sv, er, a2, 20, 50, blocks)
+        lin_exp = 10 ** (sv / 10) - 10 ** (exp_n / 10)
+        b_sn, b_c = fb.noise_bounds(sv, er, a2, nb_exp, b_nb, 20, exp_n, lin_exp)
+        corr = 10 * np.log10(np.where(lin_exp > 0, lin_exp, np.nan))
+    bound = b_c + b_sn + fb.U * np.abs(corr - exp_n)
+    assert np.isfinite(bound.ravel()[i]) and bound.ravel()[i] < 0.5
+    fb.check_decisions(keep, keep, margin, bound)                               # no flip: passes
+    with pytest.raises(AssertionError, match="outside the bound"):
+        fb.check_decisions(flipped, keep, margin, bound)
+
+
+def test_old_bar_is_implied():
+    exp = np.array([-70.0, 0.5, 30.0])
+    with pytest.raises(AssertionError, match="old bar"):
+        fb.assert_f32_close(exp + np.array([0.0, 0.0, 0.04]), exp, np.array([1.0, 1.0, 1.0]))
+
+
+def test_power_terms_add_up_to_the_oracle():
+    """cal_power_ek_terms returns the terms cal_power_ek adds: their sum is its output (a drift would skew every Sv
+    bound)."""
+    for cal_type in ("Sv", "TS"):
+        d, kw = _ek60_case(cal_type=cal_type)
+        raw = d["backscatter_r"].astype(np.float64)
+        exp, _ = ocal.cal_power_ek(raw, **kw)
+        t = ocal.cal_power_ek_terms(raw, **kw)
+        tot = t["raw"] + t["spreading"] + t["absorb"] + t["const"]
+        np.testing.assert_array_equal(np.isnan(tot), np.isnan(exp))
+        f = np.isfinite(exp)
+        assert np.max(np.abs(tot[f] - exp[f])) <= 1e-12
+        assert t["nspread"] == (20.0 if cal_type == "Sv" else 40.0)

@@ -9,7 +9,9 @@ import logging
 import numpy as np
 import pytest
 
+import f32_bounds as fb
 import oracle_chain as oc
+from oracle import calibrate as ocal
 from oracle import commongrid as ogrid
 
 pytestmark = pytest.mark.gpu
@@ -90,6 +92,18 @@ def test_three_calls_one_pass(ep, dtype, rtol, downward):
         ok = np.isfinite(got) & np.isfinite(exp)
         assert ok.mean() > 0.9 * np.isfinite(exp).mean()
         np.testing.assert_allclose(got[ok], exp[ok], rtol=rtol, atol=2e-2)
+        # ... and under the derived bounds of tests/f32_bounds.py: K1's float32 Sv against the oracle, and the MVBS
+        # against the oracle run on exactly the float32 Sv and depth the binning kernel read (bin membership decided
+        # on the same float32 depth: every bin, no "where the bins agree")
+        kw = oc.ek60_kw(d, "Sv")
+        sv32, d32 = ds["Sv"].values.astype(np.float64), ds["depth"].values.astype(np.float64)
+        fb.assert_f32_close(sv32, sv, fb.sv_power_bound(ocal.cal_power_ek_terms(d["backscatter_r"], **kw), sv),
+                            "float32 Sv")
+        t_edges = ogrid.ping_edges(d["ping_time"], "10s")
+        exp32, _, r32 = ogrid.compute_MVBS(sv32, d32, d["ping_time"], "2m", "10s")
+        np.testing.assert_array_equal(r32, r_left)
+        lab, nb = fb.labels_range(d32, d["ping_time"], t_edges, np.append(r32, r32[-1] + 2.0))
+        fb.assert_f32_close(got, exp32, fb.mvbs_bound(sv32, lab, nb, exp32), "float32 MVBS on the float32 depth")
     np.testing.assert_array_equal(mv["depth"].values, r_left)
     np.testing.assert_array_equal(mv["ping_time"].values, t_left)
 
