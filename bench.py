@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- range-samples/s through compute_Sv -> compute_MVBS on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME[:VARIANT]] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--workload NAME[:VARIANT]] ...
+
+A plain run does what the headline needs and nothing more: it sets up the resident tiles, warms up, times the K steps,
+writes --dump-outputs if asked, and prints the headline line.  Everything else the benchmark measures takes --full.
 
 ONE workload carries the 1 -> 8 GPU curve: BASELINE configs[4], the metric's own volume -- EK60 CW 4 ch x 2 M pings x
 4096 range (32.8 G samples) as eight resident tiles ("files") of 250 000 pings, dealt to the N ranks round-robin (STRONG
@@ -13,20 +16,20 @@ same pass on one rank's shard with the cut time bins summed over the ranks (ONE 
 dataset: epa_edge_pack -> all_reduce -> epa_edge_finalize_mvbs) and nanmax(echo_range) all-reduced in HBM.  The calls
 do not wait for the GPU (uploads on a side stream, the MVBS dataset assembled on first use); the bench reads each
 result once the NEXT tile has been launched, as a pipeline writing results out would.  The ping-time origin sits 10 s
-off the 20-s bin grid, so every tile edge cuts a time bin.  Beside it, from the same invocation: the ops-level harness
-(kernels called directly on preallocated buffers, all cut bins of a rank's tiles exchanged) as config.ops_level_ms_per_pass
-(its bin-aligned layout is timed as a check and not printed).
+off the 20-s bin grid, so every tile edge cuts a time bin.  With --full, beside it from the same invocation: the ops-level
+harness (kernels called directly on preallocated buffers, all cut bins of a rank's tiles exchanged, timed in runs of its
+own) as config.ops_level_ms_per_pass (its bin-aligned layout is timed as a check and not printed).
 
 A STEP is `passes_per_step` back-to-back passes of the hot path over the resident volume (so that the driver's 20 steps
 are a ~2 s region); `value` = samples processed by all ranks in the K timed steps / max-over-ranks wall time.
 
-N = 1 prints, before the headline, one JSON line per single-GPU configuration of BASELINE.json (skipped with
+With --full, N = 1 prints, before the headline, one JSON line per single-GPU configuration of BASELINE.json (skipped with
 --only-headline or an explicit --workload): cfg3 = configs[2] (compute_Sv -> remove_background_noise -> compute_MVBS;
 SURVEY 8d recipe: a new sound speed at every ping; then the every-2000-pings variant and fp32), cfg2 = configs[1] (fp64,
 fp32), the reference's own two API calls on the cfg2 volume and its THREE calls of the cfg3 chain (api:chain), cfg4 = configs[3] (EK80 BB pulse compression + Sv, float32
 planes -> fp64 / fp32, and float64 planes as the converter stores them).  Every line carries `roofline` (HIP-event
-time of the dominant kernel on torch's stream vs the algorithmic bytes of SURVEY 8d) and `cpu_baseline` (the NumPy /
-SciPy oracle with the reference's pass structure on a bounded slice, host cores, timed before HIP is initialised).
+time of the dominant kernel on torch's stream vs the algorithmic bytes of SURVEY 8d); with --full also `cpu_baseline` (the
+NumPy / SciPy oracle with the reference's pass structure on a bounded slice, host cores, timed before HIP is initialised).
 The headline line also carries the other lines' key figures as flat `also_*` strings.
 
 `--dump-outputs DIR` writes what the headline's timed path handed out in its last pass, per tile, as DIR/<name>.npy: a
@@ -66,11 +69,14 @@ TILE_PINGS = 250_000
 DT = {"f32": "float32", "f64": "float64", "sv32": "float32", "int16f32": "float32"}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the CPU baselines, the ops-level harness beside cfg5 "
+                         "and, at N = 1 without --workload / --only-headline, every other single-GPU line")
     ap.add_argument("--passes", type=int, default=None, help="passes over the volume per step (default: per workload)")
     ap.add_argument("--ss-every", type=int, default=1,
                     help="EK60 volumes: the recorded sound speed changes every this many pings (1 = SURVEY 8d's recipe: "
@@ -78,7 +84,7 @@ def parse():
     ap.add_argument("--workload", default=None,
                     help="one line only: cfg2 | cfg3 | cfg4 | cfg5 | api | small | cfg4small, optionally with a variant "
                          "(:f32, :ss2000, :planes64, :int16, :sv, :sv32)")
-    ap.add_argument("--only-headline", action="store_true", help="N=1: skip the other single-GPU lines")
+    ap.add_argument("--only-headline", action="store_true", help="N=1 with --full: skip the other single-GPU lines")
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--chain-outputs", default="all", choices=["all", "corrected"],
@@ -103,7 +109,7 @@ def parse():
                     help="cfg5: write what the timed path handed out in its last step, per tile, to DIR/<name>.npy -- a "
                          "fixed, seeded sample of Sv and of the MVBS, the MVBS coordinates whole (at most 64 MB in all); NaN / inf "
                          "entries are written as 0 and marked in DIR/<name>_nonfinite.npy")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 # ---------------------------------------------------------------------------------------- CPU baselines
@@ -1081,8 +1087,8 @@ def ranks_info(ctx):
 
 
 def run_cfg5(ctx, cpu, variant=""):
-    """The headline: the eight tiles through the product entry points (api_layout); beside it the ops-level harness on
-    the same resident tiles, with and without cut bins.  N = 1: the tiles -- independent datasets -- are dealt to
+    """The headline: the eight tiles through the product entry points (api_layout); beside it, with --full, the ops-level
+    harness on the same resident tiles, with and without cut bins.  N = 1: the tiles -- independent datasets -- are dealt to
     ``--tile-streams`` HIP streams by the package's own loop, ``echopype_amd.pipeline.run`` (default 2: the kernel of a tile
     runs beside the next tile's; ``cfg5:one`` = the caller's stream, a launch at a time); N > 1 and --sharded-at-1 alike:
     a rank's consecutive shards alternate between the streams, the collectives are issued in item order.  N = 1: Sv of the tiles goes to one reused buffer (ops level) /
@@ -1095,20 +1101,23 @@ def run_cfg5(ctx, cpu, variant=""):
     job = Cfg5(ctx, C, P_total, S, tile_pings=args.tile_pings, ss_every=args.ss_every)
     passes = ctx.passes("cfg5")
     steps = args.steps
-    # (a) ops level, bin-aligned layout: no bin is shared, no data collective
-    _, plan_a, mv_a, pass_a = job.layout(0)
-    assert not plan_a.shared
-    el_a, km_a = ctx.timed(pass_a, passes)
-    del mv_a, pass_a
-    # (b) ops level, ping times 10 s off the grid: every tile edge cuts a bin -> edge exchange on the timed path
-    _, plan_b, mv_b, pass_b = job.layout(10_000_000_000)
-    single = world == 1 and len(job.spans) == 1
-    assert plan_b.shared or single
-    el_b, km_b = (ctx.timed(pass_b, passes) if not single else (el_a, km_a))
-    edges_b, bytes_b = len(plan_b.edges), plan_b.nbytes
-    del mv_b, pass_b, plan_b
-    job.sv = None
-    ctx.free()
+    ops_level = {}  # (--full: the kernels called directly on preallocated buffers, all cut bins of a rank's tiles exchanged)
+    if args.full:
+        # (a) ops level, bin-aligned layout: no bin is shared, no data collective
+        _, plan_a, mv_a, pass_a = job.layout(0)
+        assert not plan_a.shared
+        el_a, km_a = ctx.timed(pass_a, passes)
+        del mv_a, pass_a
+        # (b) ops level, ping times 10 s off the grid: every tile edge cuts a bin -> edge exchange on the timed path
+        _, plan_b, mv_b, pass_b = job.layout(10_000_000_000)
+        single = world == 1 and len(job.spans) == 1
+        assert plan_b.shared or single
+        el_b, km_b = (ctx.timed(pass_b, passes) if not single else (el_a, km_a))
+        ops_level = {"ops_level_ms_per_pass": el_b / steps / passes * 1e3, "ops_level_kernel_ms": km_b,
+                     "ops_level_edge_bins": len(plan_b.edges), "allreduce_bytes": plan_b.nbytes}
+        del mv_b, pass_b, plan_b
+        job.sv = None
+        ctx.free()
     # (c) the product entry points on the same tiles, same 10-s offset: the headline
     lag = max(1, args.read_lag)
     dump_k = None
@@ -1130,7 +1139,6 @@ def run_cfg5(ctx, cpu, variant=""):
         route = "sharding.compute_Sv_MVBS(echodata_shard, shard=MVBSShard()) per tile"
         coll = (f"per dataset of {world} tiles: cut bins all_reduce(SUM) + range max all_reduce(MAX) in HBM over "
                 f"{args.backend}; control scalars over gloo")
-    # (ops_level_*: the kernels called directly on preallocated buffers, all cut bins of a rank's tiles exchanged)
     host_ms = state["host_s"] / max(1, state["calls"]) * 1e3
     if world > 1:  # the slowest rank's figure
         t = ctx.torch.tensor([host_ms], dtype=ctx.torch.float64)
@@ -1138,10 +1146,7 @@ def run_cfg5(ctx, cpu, variant=""):
         host_ms = float(t.item())
     cfg = {"tiles": f"{job.n_tiles} x {job.tile_p} pings over {world} rank(s)",
            "route": route, "collective": coll, "results_read": f"{lag} tile(s) late", "host_ms_per_call": host_ms,
-           "mvbs_shape_last_tile": list(state["last"][0]),
-           "ops_level_ms_per_pass": el_b / steps / passes * 1e3, "ops_level_kernel_ms": km_b,
-           "ops_level_edge_bins": edges_b, "allreduce_bytes": bytes_b,
-           "ranks": ranks_info(ctx)}
+           "mvbs_shape_last_tile": list(state["last"][0]), **ops_level, "ranks": ranks_info(ctx)}
     n_first = C * (job.spans[0][1] - job.spans[0][0]) * S if job.spans else 0
     bps = BYTES_PER_SAMPLE[ctx.dtype]
     del eds, pass_c, finish_c
@@ -1220,6 +1225,17 @@ def summary(out):
     return (f"{g:.0f}" if g >= 100 else f"{g:.1f}") + f" f{out['roofline']['frac']:.3f}"
 
 
+def lines_of(args, world):
+    """The lines a run prints, in this order (the headline last): a plain run, the headline alone."""
+    if world > 1:
+        if (args.workload or "cfg5") != "cfg5":
+            sys.exit("N > 1 runs the ping-sharded cfg5 workload")
+        return ["cfg5"]
+    if args.workload:
+        return args.workload.split(",")  # (several lines in one process, in this order: "cfg5:one,cfg5")
+    return list(DEFAULT_LINES) if args.full and not args.only_headline else ["cfg5"]
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1229,14 +1245,7 @@ def main():
         sys.exit(relaunch(args))
     if args.single_device:
         local_rank = 0
-    if world > 1:
-        todo = [args.workload or "cfg5"]
-        if todo != ["cfg5"]:
-            sys.exit("N > 1 runs the ping-sharded cfg5 workload")
-    elif args.workload:
-        todo = args.workload.split(",")  # (several lines in one process, in this order: "cfg5:one,cfg5")
-    else:
-        todo = ["cfg5"] if args.only_headline else list(DEFAULT_LINES)
+    todo = lines_of(args, world)
     dump_line = max((i for i, s in enumerate(todo) if s.partition(":")[0] == "cfg5"), default=None)
     if args.dump_outputs and dump_line is None:
         sys.exit("--dump-outputs writes the cfg5 headline's outputs: --workload has no cfg5 line")
@@ -1246,9 +1255,9 @@ def main():
             return "chain"
         return {"cfg3": "chain", "cfg4": "bb", "cfg4small": "bb"}.get(w.partition(":")[0], "ek60")
 
-    # CPU baselines first (rank 0): they fork worker processes, which must happen before HIP is initialised
+    # CPU baselines first (--full, rank 0): they fork worker processes, which must happen before HIP is initialised
     cpu = {}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         for w in todo:
             kind = kind_of(w)
             if kind not in cpu:

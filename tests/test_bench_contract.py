@@ -129,7 +129,7 @@ def test_fit_bounds_a_line_by_dropping_optional_keys_in_order():
 def test_live_headline_line():
     """The N = 1 headline at a reduced ping count (the full volume is the bench's own business and
     tests/test_gpu_fullsize_cfg5.py's): same code path, tiles, straddling layout and exchange."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--only-headline", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--only-headline", "--no-cpu-baseline",
                           "--steps", "3", "--warmup", "1", "--pings-total", "400000"], capture_output=True, text=True,
                          cwd=ROOT, check=True)
     lines = [x for x in out.stdout.splitlines() if x.startswith("{")]
@@ -144,10 +144,39 @@ def test_live_headline_line():
 
 
 @pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone():
+    """Without --full a run sets up, warms up, times its steps and prints the headline line: no CPU baseline, no other
+    line and no ops-level harness beside it."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+                          "--pings-total", "200000"], capture_output=True, text=True, cwd=ROOT, check=True)
+    lines = [x for x in out.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    _check_line(d, want_cpu=False)
+    assert "cpu_baseline" not in d and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "strong"
+    assert d["config"]["workload"].startswith("cfg5") and "compute_Sv -> compute_MVBS" in d["config"]["route"]
+    assert not [k for k in d["config"] if k.startswith(("ops_level_", "allreduce_", "also_"))], d["config"]
+    assert d["config"]["host_ms_per_call"] > 0 and d["config"]["ranks"]["devices"] == ["0:cuda0"]
+
+
+def test_full_adds_the_lines_a_plain_run_leaves_out():
+    """A plain run prints the headline alone; --full adds every other single-GPU line before it unless --only-headline
+    says otherwise; --workload picks the lines either way."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert not bench.parse([]).full and bench.lines_of(bench.parse([]), 1) == ["cfg5"]
+    assert bench.lines_of(bench.parse(["--full"]), 1) == bench.DEFAULT_LINES and bench.DEFAULT_LINES[-1] == "cfg5"
+    assert bench.lines_of(bench.parse(["--full", "--only-headline"]), 1) == ["cfg5"]
+    assert bench.lines_of(bench.parse(["--workload", "cfg2,cfg5"]), 1) == ["cfg2", "cfg5"]
+    assert bench.lines_of(bench.parse(["--full"]), 2) == ["cfg5"]
+
+
+@pytest.mark.gpu
 def test_gloo_two_ranks_print_the_same_workload_with_a_cpu_baseline():
     """`--gpus 2 --backend gloo --single-device` (two processes on cuda:0) and `--gpus 1` print the same workload up to
     the split, each with roofline + cpu_baseline (the N > 1 line used to come without one)."""
-    common = ["--steps", "2", "--warmup", "1", "--pings-total", "200000", "--workload", "cfg5"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--pings-total", "200000", "--workload", "cfg5"]
     outs = []
     for extra in ([], ["--gpus", "2", "--backend", "gloo", "--single-device"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *common, *extra], capture_output=True,
@@ -173,9 +202,9 @@ def test_gloo_two_ranks_print_the_same_workload_with_a_cpu_baseline():
 def test_sharded_route_on_a_one_rank_rccl_group_prints_its_host_cost():
     """`--sharded-at-1`: the SHARDED entry points per tile on a one-rank RCCL group (every collective of the N > 1 route
     executes, as an identity) -- the line carries the host time per call next to the N = 1 figures."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--only-headline", "--no-cpu-baseline", "--steps", "2",
-                        "--warmup", "1", "--pings-total", "200000", "--sharded-at-1"], capture_output=True, text=True,
-                       cwd=ROOT, check=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--only-headline", "--no-cpu-baseline",
+                        "--steps", "2", "--warmup", "1", "--pings-total", "200000", "--sharded-at-1"], capture_output=True,
+                       text=True, cwd=ROOT, check=True)
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
