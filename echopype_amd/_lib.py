@@ -36,6 +36,8 @@ CCP = ("sample_interval", "tau_nominal", "transmit_power", "sound_speed", "absor
 EK80_NFFT = 2048
 APPLY_MASKS_WS_DOUBLES = 131072  # EPA_APPLY_MASKS_WS_DOUBLES
 SEAFLOOR_STATE_WORDS = 16  # EPA_SEAFLOOR_STATE_WORDS
+SHOAL_STATE_WORDS = 8  # EPA_SHOAL_STATE_WORDS
+SHOAL_QUEUE_BOXES = 4096  # EPA_SHOAL_QUEUE_BOXES
 
 
 class EpaError(RuntimeError):
@@ -143,6 +145,11 @@ SIGNATURES = {
     "epa_seafloor_median": [_vp, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "epa_seafloor_components": [_vp, _i, _i64, _i64, _i64, _i64, _d, _vp, _vp, _vp, _vp],
     "epa_seafloor_bottom": [_vp, _vp, _i64, _i64, _i64, _vp, _d, _vp, _i, _vp],
+    "epa_shoal_threshold_fill": [_vp, _i, _i64, _i64, _d, _i64, _i64, _vp, _vp],
+    "epa_shoal_label": [_vp, _i64, _i64, _i, _vp, _vp, _vp, _i64, _vp, _vp],
+    "epa_shoal_weill_filter": [_vp, _i64, _i64, _vp, _vp, _i64, _d, _d, _vp, _vp, _vp],
+    "epa_shoal_echoview_link": [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _d, _d, _d, _d, _d, _d, _vp,
+                                _vp, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

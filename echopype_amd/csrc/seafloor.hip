@@ -29,8 +29,14 @@
 // another: nothing relies on all of them being resident.  Each retry loop has a bound (the pixel count: a correct run cannot reach it); a loop that
 // reaches it counts into an error word the host turns into an exception.
 #include "epa_internal.h"
+#include "union_find.h"
 
 namespace {
+
+using epa::uf::ld;
+using epa::uf::st;
+using epa::uf::uf_root;
+using epa::uf::uf_union;
 
 constexpr int kWaves = epa::kBlock / 64;
 constexpr int kMaxBlocks = 16384;
@@ -281,55 +287,6 @@ __global__ void sf_median_pick_kernel(const unsigned long long* __restrict__ his
 }
 
 // ---- blackwell: connected components of Sv > threshold (8-connectivity), kept where they meet the angle mask --------
-__device__ __forceinline__ long long ld(const long long* a) {
-  return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st(long long* a, long long v) {
-  __hip_atomic_store(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ long long uf_find(long long* par, long long x, long long bound, unsigned long long* err) {
-  for (long long steps = 0; steps <= bound; ++steps) {
-    const long long p = ld(par + x);
-    if (p == x) return x;
-    const long long g = ld(par + p);
-    if (g != p) st(par + x, g);  // path halving
-    x = g;
-  }
-  atomicAdd(err, 1ull);
-  return x;
-}
-
-// the root of x without writing anything (the compression pass: a halving store that lands after another thread has
-// stored its pixel's root would leave that pixel pointing at a non-root)
-__device__ long long uf_root(const long long* par, long long x, long long bound, unsigned long long* err) {
-  for (long long steps = 0; steps <= bound; ++steps) {
-    const long long p = ld(par + x);
-    if (p == x) return x;
-    x = p;
-  }
-  atomicAdd(err, 1ull);
-  return x;
-}
-
-__device__ void uf_union(long long* par, long long a, long long b, long long bound, unsigned long long* err) {
-  for (long long it = 0; it <= bound; ++it) {
-    a = uf_find(par, a, bound, err);
-    b = uf_find(par, b, bound, err);
-    if (a == b) return;
-    if (a < b) {
-      const long long t = a;
-      a = b;
-      b = t;
-    }
-    // link the larger root under the smaller one; a changed root means somebody linked it meanwhile: go on from there
-    const long long old = __hip_atomic_fetch_min(par + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == a) return;
-    a = old;
-  }
-  atomicAdd(err, 1ull);
-}
-
 template <typename T>
 __global__ __launch_bounds__(epa::kBlock) void sf_cc_init_kernel(const T* __restrict__ sv, long long P, long long S,
                                                                  long long r0, long long R, T thr,

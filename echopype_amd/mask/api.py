@@ -207,3 +207,26 @@ def detect_seafloor(ds, method, params):
     if method not in METHODS_BOTTOM:
         raise ValueError(f"Unsupported bottom detection method: {method}")
     return METHODS_BOTTOM[method](ds, **params)
+
+
+# ---- shoal detection (reference: mask/api.py:963-996) -----------------------------------------------------------------
+from .shoal_detection.shoal_echoview import shoal_echoview  # noqa: E402
+from .shoal_detection.shoal_weill import shoal_weill  # noqa: E402
+
+# Registry of supported methods for shoal detection
+METHODS_SHOAL = {
+    "echoview": shoal_echoview,
+    "weill": shoal_weill,
+}
+
+
+def detect_shoal(ds, method, params):
+    """Dispatch shoal detection to a chosen method and return a 2-D boolean mask (``ping_time`` x ``range_sample``,
+    True inside a shoal, data on the device).  ``method``: ``"weill"`` (threshold, gap filling, length filter) or
+    ``"echoview"`` (candidates, linking, minimum shoal size); ``params``: that method's keyword arguments (see
+    shoal_detection.shoal_weill / shoal_echoview).  One channel per call; sharded datasets are not supported.
+
+    Raises ValueError if ``method`` is not supported."""
+    if method not in METHODS_SHOAL:
+        raise ValueError(f"Unsupported shoal detection method: {method}")
+    return METHODS_SHOAL[method](ds, **params)

@@ -856,6 +856,71 @@ def seafloor_bottom(parent, mask, P, r0, depth0, offset, dtype):
     return out
 
 
+# ---- shoal detection (mask.detect_shoal) -----------------------------------------------------------------------------
+def shoal_table_capacity(P, S, connectivity):
+    """The most components a (P, S) plane can hold (the size of the component table of the shoal detectors)."""
+    return (P * S + 1) // 2 if connectivity == 4 else ((P + 1) // 2) * ((S + 1) // 2)
+
+
+def shoal_state(device):
+    """The zeroed u64 state words of one shoal call (int64 tensor of EPA_SHOAL_STATE_WORDS): [0] the error word."""
+    return torch.zeros(_lib.SHOAL_STATE_WORDS, dtype=torch.int64, device=device)
+
+
+def _gap(v, n):
+    """A gap length as given (``run <= v`` for an integer run) -> the integer the kernels compare with."""
+    v = float(v)
+    return 0 if not v >= 0 else int(min(np.floor(v), n))
+
+
+def shoal_threshold_fill(sv, thr, maxvgap=0, maxhgap=0):
+    """``sv > thr`` on a (P, S) plane, background runs of at most ``maxvgap`` samples (then ``maxhgap`` pings) between
+    foreground filled -> bool (P, S)."""
+    dt = _plane_dtype(sv, "Sv")
+    P, S = sv.shape
+    plane = torch.empty((P, S), dtype=torch.bool, device=sv.device)
+    call("epa_shoal_threshold_fill", _p(sv), dt, P, S, float(thr), _gap(maxvgap, S),
+         _gap(maxhgap, P), _p(plane), _stream())
+    return plane
+
+
+def shoal_label(plane, connectivity, state, with_groups=False):
+    """Connected components of a bool (P, S) plane -> (parent int64 (P, S): -(id + 2) on component id, -1 on
+    background; table: dict of the int32 tensors ``box`` (4, cap), ``flag`` (cap) and, ``with_groups``, ``group``
+    (cap))."""
+    P, S = plane.shape
+    cap = shoal_table_capacity(P, S, connectivity)
+    dev = plane.device
+    parent = torch.empty((P, S), dtype=torch.int64, device=dev)
+    table = {"box": torch.empty((4, cap), dtype=torch.int32, device=dev),
+             "flag": torch.empty(cap, dtype=torch.int32, device=dev), "cap": cap}
+    if with_groups:
+        table["group"] = torch.empty(cap, dtype=torch.int32, device=dev)
+    call("epa_shoal_label", _p(plane), P, S, int(connectivity), _p(parent), _p(table["box"]), _p(table["flag"]), cap,
+         _p(state), _stream())
+    return parent, table
+
+
+def shoal_weill_filter(plane, parent, table, minvlen, minhlen, state):
+    """In place: ``plane`` keeps the components whose extents are not below ``minvlen`` samples / ``minhlen`` pings."""
+    P, S = plane.shape
+    call("epa_shoal_weill_filter", _p(parent), P, S, _p(table["box"]), _p(table["flag"]), table["cap"],
+         float(minvlen), float(minhlen), _p(state), _p(plane), _stream())
+    return plane
+
+
+def shoal_echoview_link(plane, parent, table, idim, jdim, mincan, maxlink, minsho, state):
+    """In place: Echoview's candidate filter, linking and shoal filter on a labelled plane; ``idim`` / ``jdim`` f64
+    device vectors."""
+    P, S = plane.shape
+    queue = torch.empty(2 * _lib.SHOAL_QUEUE_BOXES, dtype=torch.int32, device=plane.device)
+    call("epa_shoal_echoview_link", _p(parent), P, S, _p(table["box"]), _p(table["group"]), _p(table["flag"]),
+         table["cap"], _p(idim), int(idim.numel()), _p(jdim), int(jdim.numel()), float(mincan[0]), float(mincan[1]),
+         float(maxlink[0]), float(maxlink[1]), float(minsho[0]), float(minsho[1]), _p(queue), _p(state), _p(plane),
+         _stream())
+    return plane
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

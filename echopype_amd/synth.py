@@ -402,3 +402,24 @@ def ek60_seafloor_numpy(C=2, P=96, S=400, seed=20261018, band_top=300, slope=-0.
     d["backscatter_r"], d["angle_alongship"], d["angle_athwartship"] = power, al, at
     d["seafloor_top"] = top
     return d
+
+
+def shoal_scene(P=90, S=120, seed=20261016, dtype=np.float64, schools=6, nan_frac=0.03, speckle=0.02):
+    """One channel's (ping_time, range_sample) Sv plane of a school scene:
+    - ``schools`` smooth blobs (Gaussian bumps of random centre and radii) reaching about -50 dB, with soft edges, so a
+      -70 dB threshold cuts ragged outlines with small satellites and holes;
+    - background about -85 dB with a spread of 4 dB, and ``speckle`` of the pixels raised to about -62 dB (single-pixel
+      candidates and short gaps inside the blobs' fringes);
+    - ``nan_frac`` of the pixels NaN."""
+    rng = np.random.default_rng(seed)
+    pp, ss = np.meshgrid(np.arange(P, dtype=np.float64), np.arange(S, dtype=np.float64), indexing="ij")
+    sv = -85.0 + 4.0 * rng.standard_normal((P, S))
+    for _ in range(schools):
+        cp, cs = rng.uniform(0, P), rng.uniform(0, S)
+        rp, rs = rng.uniform(0.03, 0.12) * P + 1.5, rng.uniform(0.03, 0.12) * S + 1.5
+        bump = np.exp(-0.5 * (((pp - cp) / rp) ** 2 + ((ss - cs) / rs) ** 2))
+        sv = np.maximum(sv, -95.0 + 45.0 * bump + 3.0 * rng.standard_normal((P, S)))
+    spk = rng.random((P, S)) < speckle
+    sv[spk] = -62.0 + 2.0 * rng.standard_normal(int(spk.sum()))
+    sv[rng.random((P, S)) < nan_frac] = np.nan
+    return sv.astype(dtype)

@@ -701,6 +701,43 @@ int epa_seafloor_components(const void* sv, int dtype, long long P, long long S,
 int epa_seafloor_bottom(const long long* parent, const unsigned char* mask, long long P, long long R, long long r0,
                         const double* depth0, double offset, void* out, int out_dtype, epa_stream_t stream);
 
+/* ---- shoal detection: mask.detect_shoal (mask/shoal_detection/) ---------------------------------------------------
+ * One (ping, range) plane, row by ping: sv is [P*S] of dtype F32 / F64; plane is u8 [P*S] (0 / 1: it is the boolean
+ * result in the end); parent is i64 [P*S].  The component table has cap entries, at least the
+ * most components the plane can hold ((P*S + 1) / 2 with connectivity 4, ceil(P/2) * ceil(S/2) with 8) and at most 0x70000000: box i32 [4*cap] (min sample, max sample, min ping, max ping, one plane each),
+ * flag i32 [cap], and for echoview group i32 [cap].  state: u64 [EPA_SHOAL_STATE_WORDS], zeroed by the caller:
+ * [0] union-find loops that reached their bound (non-zero: the result is not to be trusted), [1] components. */
+#define EPA_SHOAL_STATE_WORDS 8
+#define EPA_SHOAL_QUEUE_BOXES 4096
+
+/* plane = sv > thr (compared in f64: thr is not rounded to dtype; NaN background); then along range in every ping, runs of background of at
+ * most maxvgap samples with foreground on both sides become foreground; then, on that result, the same along pings
+ * at every sample with maxhgap. */
+int epa_shoal_threshold_fill(const void* sv, int dtype, long long P, long long S, double thr, long long maxvgap,
+                             long long maxhgap, unsigned char* plane, epa_stream_t stream);
+
+/* Connected components (connectivity 4 or 8) of the non-zero bytes of plane: parent = -(id + 2) on the pixels of
+ * component id (ids 0 .. state[1] - 1 in no particular order), -1 on background; box[.][id] its bounding box;
+ * flag[id] = 0. */
+int epa_shoal_label(const unsigned char* plane, long long P, long long S, int connectivity, long long* parent,
+                    int* box, int* flag, long long cap, unsigned long long* state, epa_stream_t stream);
+
+/* shoal_weill.py, size filter: plane = 1 on the pixels of the components whose extents (max - min + 1) are not below
+ * minvlen (samples) / minhlen (pings), 0 elsewhere.  parent / box / flag: of epa_shoal_label(..., 4, ...). */
+int epa_shoal_weill_filter(const long long* parent, long long P, long long S, const int* box, int* flag,
+                           long long cap, double minvlen, double minhlen, unsigned long long* state,
+                           unsigned char* plane, epa_stream_t stream);
+
+/* shoal_echoview.py after the labelling (parent / box / flag: of epa_shoal_label(..., 8, ...); box and flag are
+ * overwritten): candidates below mincan removed, the survivors linked through their boxes grown by maxlink + 1,
+ * groups below minsho removed; plane = 1 on what is left.  idim (f64 [ni], ni >= S + 1) and jdim (f64 [nj],
+ * nj >= P + 1) on the device, nondecreasing and finite.  queue: i32 [2 * EPA_SHOAL_QUEUE_BOXES]. */
+int epa_shoal_echoview_link(const long long* parent, long long P, long long S, int* box, int* group, int* flag,
+                            long long cap, const double* idim, long long ni, const double* jdim, long long nj,
+                            double mincan0, double mincan1, double maxlink0, double maxlink1, double minsho0,
+                            double minsho1, int* queue, unsigned long long* state, unsigned char* plane,
+                            epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
