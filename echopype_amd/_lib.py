@@ -150,6 +150,8 @@ SIGNATURES = {
     "epa_shoal_weill_filter": [_vp, _i64, _i64, _vp, _vp, _i64, _d, _d, _vp, _vp, _vp],
     "epa_shoal_echoview_link": [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _d, _d, _d, _d, _d, _d, _vp,
                                 _vp, _vp, _vp],
+    "epa_transient_fielding": [_vp, _i, _i, _i, _i, _vp, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp],
+    "epa_transient_matecho": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _d, _vp, _vp, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -19,6 +19,7 @@ from ..commongrid.api import _coef_rows, _dev, _full, _range_stats
 from ..commongrid.utils import _parse_x_bin
 from ..utils.prov import echopype_prov_attrs, insert_processing_level
 from ..xr_lite import DataArray, DeviceArray, LazyDeviceArray, from_xarray, xarray_io
+from .transient_noise import transient_noise_fielding, transient_noise_matecho
 from .utils import add_remove_background_noise_attrs, extract_dB
 
 
@@ -408,6 +409,23 @@ def mask_attenuated_signal(ds_Sv, upper_limit_sl="400.0m", lower_limit_sl="500.0
     else:
         mask = ops.attenuated_mask(sv_t, rg_t, upper, lower, num_side_pings, thr)
     return _mask_da(ds_Sv, mask)
+
+
+# ---- transient-noise detectors with a boolean VALID mask (api.py:514-655) -----------------------------------------
+METHODS_TRANSIENT = {
+    "fielding": transient_noise_fielding,
+    "matecho": transient_noise_matecho,
+}
+
+
+def detect_transient(ds, method, params):
+    """Dispatch transient-noise detection to ``method`` ("fielding" or "matecho") with the keyword arguments
+    ``params`` (omitted ones take the method's defaults) and return its boolean mask: dims and order of
+    ``ds[var_name]``, True = VALID (keep), False = transient noise; a ``torch.bool`` tensor on the device that
+    ``mask.apply_mask`` takes as it is.  See ``clean.transient_noise`` for the two methods."""
+    if method not in METHODS_TRANSIENT:
+        raise ValueError(f"Unsupported transient noise removal method: {method}")
+    return METHODS_TRANSIENT[method](ds, **params)
 
 
 # names used by older echopype releases (docs/source/whats-new.md:366)

@@ -12,45 +12,12 @@
 // Linear-domain sums are accumulated in double whatever the storage type; comparisons against the
 // thresholds are done in the storage type, as numpy does for the reference's arrays.
 #include "fast_math.h"
+#include "select.h"
 
 namespace {
 
 using epa::kBlock;
-
-// scipy.ndimage / dask_image mode="reflect":  d c b a | a b c d | d c b a   (period 2n)
-__device__ __forceinline__ int reflect_index(int i, int n) {
-  const int period = 2 * n;
-  i %= period;
-  if (i < 0) i += period;
-  return i < n ? i : period - 1 - i;
-}
-
-// ------------------------------------------------------------------------------------------------
-// workgroup reductions (256 threads = 4 wavefronts); every thread gets the result
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned block_sum(unsigned v, unsigned* sh4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh4[0] + sh4[1] + sh4[2] + sh4[3];
-}
-
-__device__ __forceinline__ unsigned long long block_min(unsigned long long v, unsigned long long* sh4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_down(v, o, 64);
-    v = w < v ? w : v;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  unsigned long long r = sh4[0];
-#pragma unroll
-  for (int i = 1; i < 4; ++i) r = sh4[i] < r ? sh4[i] : r;
-  return r;
-}
+using namespace epa::sel;  // reflect_index, block_sum / block_min, sort_key, Window, SelectScratch, window_median_lin
 
 // lexicographic (value, index) minimum -- np.argmin's "first occurrence of the minimum"
 __device__ __forceinline__ int block_argmin(double v, int idx, double* shv, int* shi) {
@@ -531,39 +498,8 @@ __global__ __launch_bounds__(kBlock) void box_ping_slide_kernel(const T* __restr
 // ------------------------------------------------------------------------------------------------
 // NaN-skipping median of the LINEAR values of a window, by radix selection on the dB values
 // (10^(x/10) is monotone, so the order statistics are those of x; an even count averages the two
-// middle values in the linear domain, as np.nanmedian(_log2lin(.)) does).
+// middle values in the linear domain, as np.nanmedian(_log2lin(.)) does): select.h.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long sort_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-}
-
-template <typename T>
-struct Window {
-  const T* base;  // channel base pointer
-  int S;          // row stride
-  int p_lo, np;   // pings p_lo .. p_lo+np-1
-  int s_lo, ns;   // samples s_lo .. s_lo+ns-1
-  int P, s0;      // reflect domain: pings [0,P), samples [s0,S)
-  bool reflect;
-  // calls f(value) for every element this thread owns
-  template <typename F>
-  __device__ __forceinline__ void for_each(F f) const {
-    const int ne = np * ns;
-    for (int i = threadIdx.x; i < ne; i += kBlock) {
-      const int ip = i / ns, is = i - ip * ns;
-      int p = p_lo + ip, s = s_lo + is;
-      if (reflect) {
-        p = reflect_index(p, P);
-        s = s0 + reflect_index(s - s0, S - s0);
-      }
-      f((double)base[(size_t)p * S + s]);
-    }
-  }
-};
 
 // Window by VALUE of the range variable (pool_Sv, clean/utils.py:86-92): in ping q_lo + j the
 // samples lo[j] .. hi[j]-1 (contiguous because the range variable increases along range_sample).
@@ -582,170 +518,6 @@ struct RaggedWindow {
   }
 };
 
-constexpr int kCandCap = 2048;  // candidates kept in LDS once the selected radix bucket is this small
-
-template <int CAP>
-struct SelectScratchT {
-  static constexpr int kCap = CAP;
-  unsigned hist[256];
-  unsigned u4[4];
-  unsigned long long q4[4];
-  unsigned digit, krem, bucket, ncand;
-  unsigned long long cand[CAP];
-};
-using SelectScratch = SelectScratchT<kCandCap>;
-
-// One 8-bit radix step of the selection: histogram of digit (key >> shift) & 255 over the keys that
-// `each` enumerates and that match `prefix` on the bits above the digit; picks the bucket holding
-// rank k.  Returns the total number of keys counted; updates prefix / k; *bucket = size of the bucket.
-template <typename Each, typename SC>
-__device__ __forceinline__ unsigned radix_step(Each each, SC* sc, int shift,
-                                               unsigned long long& prefix, unsigned& k, unsigned& bucket,
-                                               bool k_known, unsigned* total_out) {
-  __syncthreads();
-  sc->hist[threadIdx.x] = 0u;  // kBlock == 256
-  __syncthreads();
-  const unsigned long long hi_mask = shift == 56 ? 0ull : (~0ull << (shift + 8));
-  unsigned* hist = sc->hist;
-  const unsigned long long pre = prefix;
-  each([&](unsigned long long key) {
-    if ((key & hi_mask) == pre) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
-  });
-  __syncthreads();
-  if (!k_known) {  // first step: the histogram total is the number of valid values; k = lower median rank
-    const unsigned total = block_sum(sc->hist[threadIdx.x], sc->u4);
-    *total_out = total;
-    if (total == 0u) return 0u;
-    k = (total - 1u) / 2u;
-  }
-  if (threadIdx.x < 64) {
-    const unsigned l = threadIdx.x;
-    const unsigned h0 = sc->hist[4 * l], h1 = sc->hist[4 * l + 1], h2 = sc->hist[4 * l + 2],
-                   h3 = sc->hist[4 * l + 3];
-    const unsigned tot = h0 + h1 + h2 + h3;
-    unsigned incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(incl, o, 64);
-      if ((int)l >= o) incl += t;
-    }
-    const unsigned excl = incl - tot;
-    if (excl <= k && k < incl) {
-      unsigned r = k - excl, d;
-      if (r < h0) d = 0;
-      else if ((r -= h0) < h1) d = 1;
-      else if ((r -= h1) < h2) d = 2;
-      else { r -= h2; d = 3; }
-      sc->digit = 4 * l + d;
-      sc->krem = r;
-      sc->bucket = d == 0 ? h0 : (d == 1 ? h1 : (d == 2 ? h2 : h3));
-    }
-  }
-  __syncthreads();
-  prefix |= (unsigned long long)sc->digit << shift;
-  k = sc->krem;
-  bucket = sc->bucket;
-  return 1u;
-}
-
-// Returns the median of 10^(x/10) over the non-NaN x of the window; n_valid = their count (the
-// result is NaN when it is 0).  Must be called by all threads of the workgroup.
-// The window is swept from memory only until the bucket that holds the median has at most kCandCap
-// members (typically 2 sweeps for a 16 k-element block of dB values, 0 for a small window); those
-// candidates are then gathered into LDS in one more sweep and the remaining digits are resolved there.
-template <typename W, typename SC>
-__device__ double window_median_lin(const W& w, SC* sc, const double* exp2_tab,
-                                    unsigned& n_valid, int size_hint = 0x7fffffff) {
-  constexpr int kCandCap = SC::kCap;  // (shadows the default capacity)
-  auto each_global = [&](auto f) {
-    w.for_each([&](double v) {
-      if (v == v) f(sort_key(v));
-    });
-  };
-  unsigned long long prefix = 0ull;
-  unsigned k = 0u, bucket = 0xffffffffu, N = 0u;
-  bool k_known = false;
-  int shift = 64;  // bits [shift, 64) of the median's key are decided
-  if (size_hint > kCandCap) {
-    while (shift > 0 && bucket > (unsigned)kCandCap) {
-      shift -= 8;
-      if (!radix_step(each_global, sc, shift, prefix, k, bucket, k_known, &N)) {
-        n_valid = 0u;
-        return __builtin_nan("");
-      }
-      k_known = true;
-    }
-  }
-  unsigned long long key1, key2;
-  if (shift == 0) {
-    // resolved entirely from memory (a bucket of > kCandCap equal values): one more sweep for the even case
-    key1 = key2 = prefix;
-    if ((N & 1u) == 0u) {
-      unsigned le = 0;
-      unsigned long long gt = ~0ull;
-      each_global([&](unsigned long long key) {
-        if (key <= prefix) ++le;
-        else gt = key < gt ? key : gt;
-      });
-      const unsigned n_le = block_sum(le, sc->u4);
-      const unsigned long long min_gt = block_min(gt, sc->q4);
-      if (n_le < (N - 1u) / 2u + 2u) key2 = min_gt;
-    }
-  } else {
-    // gather the candidates (keys matching the decided bits) into LDS; remember the smallest key above them
-    const unsigned long long dmask = shift == 64 ? 0ull : (~0ull << shift);
-    __syncthreads();
-    if (threadIdx.x == 0) sc->ncand = 0u;
-    __syncthreads();
-    unsigned long long above = ~0ull;
-    unsigned* ncand = &sc->ncand;
-    unsigned long long* cand = sc->cand;
-    const unsigned long long pre = prefix;
-    each_global([&](unsigned long long key) {
-      const unsigned long long hi = key & dmask;
-      if (hi == pre) {
-        const unsigned at = atomicAdd(ncand, 1u);
-        if (at < (unsigned)kCandCap) cand[at] = key;
-      } else if (hi > pre) {
-        above = key < above ? key : above;
-      }
-    });
-    const unsigned long long min_above = block_min(above, sc->q4);  // (barriers inside publish cand / ncand)
-    const unsigned M = sc->ncand;
-    if (!k_known) {  // small window gathered whole: M is the number of valid values
-      N = M;
-      if (N == 0u) {
-        n_valid = 0u;
-        return __builtin_nan("");
-      }
-      k = (N - 1u) / 2u;
-    }
-    const unsigned r0 = k;  // rank of the median inside the candidate set
-    auto each_cand = [&](auto f) {
-      for (unsigned i = threadIdx.x; i < M; i += kBlock) f(cand[i]);
-    };
-    unsigned dummy;
-    while (shift > 0) {
-      shift -= 8;
-      radix_step(each_cand, sc, shift, prefix, k, bucket, true, &dummy);
-    }
-    key1 = key2 = prefix;
-    if ((N & 1u) == 0u) {
-      unsigned le = 0;
-      unsigned long long gt = ~0ull;
-      each_cand([&](unsigned long long key) {
-        if (key <= prefix) ++le;
-        else gt = key < gt ? key : gt;
-      });
-      const unsigned n_le = block_sum(le, sc->u4);
-      const unsigned long long min_gt = block_min(gt, sc->q4);
-      if (n_le < r0 + 2u) key2 = (min_gt != ~0ull) ? min_gt : min_above;
-    }
-  }
-  n_valid = N;
-  const double a = epa::lin_from_db(key_value(key1), exp2_tab);
-  return key1 == key2 ? a : (a + epa::lin_from_db(key_value(key2), exp2_tab)) * 0.5;
-}
 
 // pooled Sv with func = nanmedian: one workgroup per output sample (the reference warns that this
 // variant is "incredibly slow"; here it is exact and usable on subsets, O(window) per sample).

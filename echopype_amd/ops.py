@@ -921,6 +921,51 @@ def shoal_echoview_link(plane, parent, table, idim, jdim, mincan, maxlink, minsh
     return plane
 
 
+# ---- transient-noise detectors (clean.detect_transient) --------------------------------------------------------------
+def transient_fielding(sv, chan, n, thr0, thr1, maxts):
+    """Fielding's transient-noise mask of a (C, P, S) cube -> bool (C, P, S), True = valid.  ``chan``: host int (C, 4)
+    table of up, lw, rmin, sf per channel (``epa_transient_fielding``)."""
+    C, P, S = sv.shape
+    chan = np.ascontiguousarray(chan, dtype=np.int64).reshape(C, 4)
+    up, lw, rmin, sf = chan.T
+    if ((up < 0) | (up >= S) | (lw < 0) | (lw >= S) | (rmin < 0) | (rmin >= S) | (sf < 1)).any():
+        raise ValueError(f"transient_fielding: window rows outside [0, {S}): {chan.tolist()}")
+    chan[:, 3] = np.minimum(sf, 2 * S + 2)  # (a step beyond the column: no walk, a slice start below -S -- the same)
+    max_rows = int(max(np.max(np.maximum(lw - up, 0)), np.max(np.where(chan[:, 3] < up, chan[:, 3], 0))))
+    dev = sv.device
+    mask = torch.empty((C, P, S), dtype=torch.bool, device=dev)
+    todo = torch.empty(C * P, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    call("epa_transient_fielding", _p(sv), _DT[sv.dtype], C, P, S, _p(to_device_small(chan.astype(np.int32), device=dev)),
+         max_rows, int(n), float(thr0), float(thr1), float(maxts), _p(todo), _p(count), _p(mask), _stream())
+    return mask
+
+
+def transient_matecho(sv, range_rows, chan_i, chan_d, bottom, half_window, percentile, delta_db, extend_ping, min_window):
+    """Matecho's transient-noise mask of a (C, P, S) cube -> bool (C, P, S), True = valid.  Host tables: ``range_rows``
+    f64 (C, S), ``chan_i`` int (C, 2) = s_lo, s_top, ``chan_d`` f64 (C, 2) = r[1] - r[0], r[-1]; ``bottom``: f64 device
+    tensor (P,) or (C, P), or None (``epa_transient_matecho``)."""
+    C, P, S = sv.shape
+    chan_i = np.ascontiguousarray(chan_i, dtype=np.int32).reshape(C, 2)
+    if ((chan_i < 0) | (chan_i > S)).any() or (chan_i[:, 0] > chan_i[:, 1]).any():
+        raise ValueError(f"transient_matecho: window rows outside [0, {S}]: {chan_i.tolist()}")
+    dev = sv.device
+    if bottom is not None:
+        if bottom.dtype != torch.float64 or bottom.shape[-1] != P or bottom.numel() not in (P, C * P):
+            raise ValueError(f"transient_matecho: bottom must be float64 of shape ({P},) or ({C}, {P}), got "
+                             f"{bottom.dtype} {tuple(bottom.shape)}")
+    mask = torch.empty((C, P, S), dtype=torch.bool, device=dev)
+    s_hi = torch.empty(C * P, dtype=torch.int32, device=dev)
+    flag = torch.empty(C * P, dtype=torch.uint8, device=dev)
+    call("epa_transient_matecho", _p(sv), _DT[sv.dtype], C, P, S,
+         _p(to_device(np.ascontiguousarray(range_rows, dtype=np.float64).reshape(C, S), device=dev)),
+         _p(to_device_small(chan_i, device=dev)),
+         _p(to_device_small(np.ascontiguousarray(chan_d, dtype=np.float64).reshape(C, 2), device=dev)),
+         _p(bottom), 0 if bottom is None else bottom.numel() // P, int(half_window), float(percentile), float(delta_db),
+         int(extend_ping), float(min_window), _p(s_hi), _p(flag), _p(mask), _stream())
+    return mask
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

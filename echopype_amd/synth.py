@@ -423,3 +423,29 @@ def shoal_scene(P=90, S=120, seed=20261016, dtype=np.float64, schools=6, nan_fra
     sv[spk] = -62.0 + 2.0 * rng.standard_normal(int(spk.sum()))
     sv[rng.random((P, S)) < nan_frac] = np.nan
     return sv.astype(dtype)
+
+
+def transient_scene(P=200, S=300, seed=20261019, dtype=np.float64, dz=2.5, elevated=6, elevation=(6.0, 15.0),
+                    nan_frac=0.02, sigma=2.0, bottom_frac=(0.85, 0.97)):
+    """One channel's water column with transient noise, as a dict of NumPy arrays:
+    - ``Sv`` (P, S): a noisy background (-78 dB at the surface falling 6 dB to the last sample, spread ``sigma`` dB),
+      ``elevated`` pings raised by ``elevation[0] .. elevation[1]`` dB from a start row of their own (``tops``) down to
+      the end of the column, ``nan_frac`` of the samples NaN, and a seafloor echo of about -25 dB under ``bottom``;
+    - ``depth`` (S,): ``dz * arange(S)``, of ``dtype``;
+    - ``bottom`` (P,) float64: a line sloping from ``bottom_frac[0]`` to ``bottom_frac[1]`` of the last depth;
+    - ``pings`` / ``tops`` / ``gains``: the elevated pings, their start rows and elevations."""
+    rng = np.random.default_rng(seed)
+    depth = dz * np.arange(S, dtype=np.float64)
+    sv = -78.0 - 6.0 * (np.arange(S) / max(S - 1, 1))[None, :] + sigma * rng.standard_normal((P, S))
+    k = min(int(elevated), P)
+    pings = np.sort(rng.choice(P, size=k, replace=False))
+    tops = rng.integers(S // 8, max(S // 8 + 1, (3 * S) // 5), size=k)
+    gains = rng.uniform(elevation[0], elevation[1], size=k)
+    for j, t, e in zip(pings, tops, gains):
+        sv[j, t:] += e
+    bottom = np.linspace(bottom_frac[0], bottom_frac[1], P) * (depth[-1] if S else 0.0)
+    under = depth[None, :] >= bottom[:, None]
+    sv[under] = -25.0 + 1.5 * rng.standard_normal(int(under.sum()))
+    sv[rng.random((P, S)) < nan_frac] = np.nan
+    return {"Sv": sv.astype(dtype), "depth": depth.astype(dtype), "bottom": bottom, "pings": pings, "tops": tops,
+            "gains": gains}

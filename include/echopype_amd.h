@@ -738,6 +738,35 @@ int epa_shoal_echoview_link(const long long* parent, long long P, long long S, i
                             double minsho1, int* queue, unsigned long long* state, unsigned char* plane,
                             epa_stream_t stream);
 
+/* ---- transient-noise detectors: clean.detect_transient (clean/transient_noise/) -------------------------------------
+ * sv is [C*P*S] of dtype F32 / F64, mask_out u8 [C*P*S]: 1 = VALID, 0 = transient noise; written completely by the
+ * call.  The scalars that depend on the range row alone come from the host, one row per channel, in device tables.
+ *
+ * Fielding (transient_fielding.py): chan i32 [C*4] = up, lw, rmin, sf.  Ping j is flagged when j - n >= 0,
+ * j + n <= P - 1, its layer [up, lw) is not all NaN, 10log10(75th percentile of the linear layer) < maxts and
+ * 10log10(nanmedian lin layer of j) - 10log10(nanmedian lin layer of pings [j-n, j+n)) > thr0; a flagged ping walks up
+ * in steps of sf samples while the window start is above rmin, stops after the first window whose median difference
+ * is below thr1, and is masked from one step above that window (Python slice semantics for a negative start).
+ * up >= lw: the channel is left all-valid.  max_rows: the most samples any window has (bounds 2 * n * max_rows).
+ * list i64 [C*P] and count u32 [1] are scratch. */
+int epa_transient_fielding(const void* sv, int dtype, int C, int P, int S, const int* chan, int max_rows, int n,
+                           double thr0, double thr1, double maxts, long long* list, unsigned* count,
+                           uint8_t* mask_out, epa_stream_t stream);
+
+/* Matecho (transient_matecho.py): range f64 [C*S], the channel's range row; chan_i i32 [C*2] = s_lo, s_top, the run of
+ * samples inside [start_depth, start_depth + window_meter], nondecreasing in range; chan_d f64 [C*2] = r[1] - r[0],
+ * r[-1].  bottom f64 [bottom_rows*P] with bottom_rows 1 or C, or NULL with 0; NaN entries count as r[-1].  For ping j,
+ * h = half_window, j0 = max(0, j-h), j1 = min(P, j+h): the window samples are [s_lo, s_hi(j)), s_hi the first of the
+ * run that is not below min(bottom[j0:j1]) (float64 comparison); skipped when there is none, when
+ * (r[1]-r[0]) * count < min_window or when the ping has no value; flagged when 10log10(nanmean lin Sv[j, samples]) >
+ * percentile (np.percentile, linear, of the non-NaN dB values of pings [j0, j1) x samples) + delta_db.  Flags are
+ * dilated by extend_ping pings on each side; a flagged ping is masked over its whole column.
+ * s_hi i32 [C*P] and flag u8 [C*P] are scratch. */
+int epa_transient_matecho(const void* sv, int dtype, int C, int P, int S, const double* range, const int* chan_i,
+                          const double* chan_d, const double* bottom, int bottom_rows, int half_window,
+                          double percentile, double delta_db, int extend_ping, double min_window, int* s_hi,
+                          uint8_t* flag, uint8_t* mask_out, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
