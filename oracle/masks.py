@@ -177,7 +177,6 @@ def pool_Sv(Sv, range_arr, func, depth_bin, num_side_pings, exclude_above):
     n = num_side_pings
     dmin, dmax = np.nanmin(range_arr), np.nanmax(range_arr)
     pooled = np.full((C, P, S), np.nan)
-    pidx = np.arange(P)[:, None]
     for c in range(C):
         lin = _lin(Sv[c])
         for s in range(S):
@@ -186,12 +185,13 @@ def pool_Sv(Sv, range_arr, func, depth_bin, num_side_pings, exclude_above):
                 if not (d - depth_bin >= dmin and d + depth_bin <= dmax and d - depth_bin >= exclude_above
                         and p - n >= 0 and p + n <= P):
                     continue
+                # (p - n <= ping index <= p + n is a slice of rows: only those are compared with the window's edges)
+                rows = slice(p - n, min(p + n, P - 1) + 1)
                 with np.errstate(invalid="ignore"):
-                    w = ((d - depth_bin <= range_arr[c]) & (range_arr[c] <= d + depth_bin)
-                         & (p - n <= pidx) & (pidx <= p + n))
+                    w = (d - depth_bin <= range_arr[c, rows]) & (range_arr[c, rows] <= d + depth_bin)
                 with warnings.catch_warnings():
                     warnings.simplefilter("ignore", RuntimeWarning)
-                    pooled[c, p, s] = _log(func(np.where(w, lin, np.nan)))
+                    pooled[c, p, s] = _log(func(np.where(w, lin[rows], np.nan)))
     return pooled
 
 

@@ -17,6 +17,9 @@ Quantities (kernel lines cited where each bound is derived):
                          ``10*log10(s/n)``), NASC-style sums, the noise estimate's block means.
 * ``tl_bound`` / ``noise_bounds``  Sv_noise and Sv_corrected (csrc/noise_apply.hip, the SRC_SV_DENOISE branch of
                          csrc/block_reduce.hip), with the condition number of the subtraction.
+* ``pooled_mean_bound`` / ``pooled_median_bound``  the pooled and smoothed Sv of the noise masks (csrc/noise_masks.hip:
+                         float32 ``exp10f`` terms, double sums, one final rounding; medians double throughout), and
+                         ``threshold_`` / ``impulse_`` / ``attenuated_decision_bound`` for the comparisons made on them.
 * ``check_decisions``   a keep/remove or membership decision may differ only where the oracle's margin to the
                          threshold is within the bound of the quantity compared.
 
@@ -271,6 +274,133 @@ def noise_bounds(sv, x, a2, nb_exp, b_nb, ping_num, sn_exp, corr_lin_exp):
         b1 = db_of_rel(e)
         b_corr = (b1 + (2 * E_LOG + 1) * U * (np.abs(corr) + b1)) * (1 + 8 * U) + 8 * U64 * (np.abs(corr) + np.abs(sv))
     return b_sn, b_corr
+
+
+# ------------------------------------------------------------------------------------------------ noise masks
+# csrc/noise_masks.hip: float32 Sv, linear terms ``exp10f(v * 0.1f)`` (fast_math.h:65) widened to double at once, every
+# sum, mean and median in double (header, :12-13), the result ``(T)(10 * fast_log10(double))``; window membership, the
+# feasibility tests and every comparison against a threshold in float32 on the float32 values (``bound<T,..>``,
+# ``pool_feasible``, :866-901) -- the oracle is called on the float32 range array, so membership is never an error term.
+DD = 2.0**-102                    # one double-double addition (``Dd::add``, :952-966): a few 2^-106 of its result
+SUM64 = 2.0**-28                  # gamma of a double sum of up to 2^24 same-sign terms (2^24 * 2^-53 / (1 - ...))
+
+
+def f64_db_slack(exp):
+    """What the double part of a mask kernel and the oracle's own float64 evaluation may differ by, in dB: a double sum
+    of same-sign terms (SUM64, any order), a division, the double ``lin_from_db`` / ``fast_log10`` (4e-16 relative,
+    fast_math.h:6) and the multiplication by 10 on both sides."""
+    with np.errstate(invalid="ignore"):
+        return DB * 2 * SUM64 + 16 * U64 * np.abs(np.asarray(exp, np.float64))
+
+
+def sv_abs_max(sv):
+    """Largest finite |Sv| of the field (the argument ``exp10_rel`` is evaluated at)."""
+    a = np.abs(np.asarray(sv, np.float64))
+    a = a[np.isfinite(a)]
+    return float(a.max()) if a.size else 0.0
+
+
+def lin_max(sv):
+    """Largest finite linear value of the field: no window or running sum of n terms exceeds n times it."""
+    v = np.asarray(sv, np.float64)
+    v = v[np.isfinite(v)]
+    return float(10.0 ** (v.max() / 10.0)) if v.size else 0.0
+
+
+def pooled_mean_bound(sv, exp, carried_terms=0, carried_ops=0):
+    """Absolute dB bound of a pooled / smoothed float32 mean with double sums: ``range_bin_smooth_kernel`` (:123,134,140),
+    ``box_range_kernel`` / ``box_range_scan_kernel`` (:208,311) + ``box_ping_slide_kernel``, ``pool_value_mean_kernel``
+    (:931,936) and the ``row_*`` / ``value_slide*`` / staged / lean routes, which add the same terms in another order.
+      each term exp10f(v * 0.1f): relative ``exp10_rel(|v|)`` <= exp10_rel(max |Sv|); the terms are positive, so their
+          sum and mean inherit at most the largest relative error of a member (a weighted mean of the members' errors,
+          as ``bin_stats`` weighs them), plus E_EXP * 2^-149 per term where exp10f is subnormal (``mean_db_bound``)
+      the sum, the division and the logarithm in double: ``f64_db_slack``
+      (T)(10 log10 mean): 1/2 ulp of the float32 result.
+    The routes that SUBTRACT -- per-row double-double running sums W[hi-1] - W[lo-1] (``row_running_sum_kernel`` +
+    ``row_interval_sum_kernel``, :943-951) and the window sums carried down the columns (enter / leave:
+    ``box_ping_slide_kernel``, ``value_slide*``) -- hold sums of up to ``carried_terms`` values to DD each over
+    ``carried_ops`` additions: an ABSOLUTE error carried_ops * DD * carried_terms * max lin, i.e. relative to the window
+    sum (>= its mean, one value at least) carried_ops * DD * carried_terms * max lin / mean.  For the inputs used here
+    (a +60 dB sample over a background whose windows average -100 dB or more, rows of up to 8200 values) that is at
+    most 8200 * 2e-31 * 8200 * 10^6 / 10^-10 = 1.3e-7 relative (6e-7 dB, a sixth of the final rounding at -70 dB) in the
+    weakest window of such a row, and below 1e-15 wherever the field has no such spike.
+    ``sv`` = the float32 field (any shape); ``exp`` = the oracle's pooled value in dB."""
+    exp = np.asarray(exp, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        mean_lin = 10.0 ** (exp / 10.0)
+        carried = float(carried_ops) * DD * float(carried_terms) * lin_max(sv) / mean_lin if carried_ops else 0.0
+        R = (1 + exp10_rel(sv_abs_max(sv)) + E_EXP * TINY / mean_lin) * (1 + carried) - 1
+        b1 = db_of_rel(R)
+        return b1 * (1 + 8 * U) + half_ulp(np.abs(exp) + b1) + f64_db_slack(exp)
+
+
+def pooled_median_bound(exp):
+    """Absolute dB bound of a float32 median route (``pool_median*``, ``pool_value_median*``, ``attenuated_*``): the keys
+    are the float32 values themselves, the two middle ones go through the DOUBLE table (select.h:286-291), their mean
+    and logarithm are double -> ``f64_db_slack`` + 1/2 ulp of the float32 result."""
+    exp = np.asarray(exp, np.float64)
+    s = f64_db_slack(exp)
+    return half_ulp(np.abs(exp) + s) + s
+
+
+def sub_rounding(diff, b):
+    """Rounding of one float32 subtraction whose exact result is within ``b`` of ``diff``."""
+    with np.errstate(invalid="ignore"):
+        return half_ulp(np.abs(np.asarray(diff, np.float64)) + b)
+
+
+def threshold_decision_bound(x, out_exp, b_out, thr):
+    """``x - out > thr`` in float32 (:939 and every pooling route's epilogue): the bound of ``out``, the rounding of the
+    subtraction and the rounding of ``thr`` to float32.  ``x`` = the float32 Sv, ``out_exp`` = the oracle's pooled value."""
+    with np.errstate(invalid="ignore"):
+        d = np.asarray(x, np.float64) - np.asarray(out_exp, np.float64)
+    return b_out + sub_rounding(d, b_out) + half_ulp(thr)
+
+
+def impulse_decision_bound(up_exp, b_up, n, thr):
+    """``up[p] - up[p +- n] > thr`` (``impulse_compare_kernel``, :158-163), (..., P, S) arrays: two smoothed values and
+    one subtraction per side, the threshold rounded to float32.  The mask is the AND of two comparisons, so it can differ
+    from the oracle's only where ONE of them is within ITS bound.  Returns (margin, bound) for ``check_decisions``:
+    ``margin`` = the smaller of |difference - thr| / bound over the two sides, ``bound`` = 1 (a missing side or a NaN
+    difference counts as +inf on both sides of the comparison: ratio inf)."""
+    up = np.asarray(up_exp, np.float64)
+    b = np.broadcast_to(np.asarray(b_up, np.float64), up.shape)
+    P = up.shape[-2]
+    ratio = np.full(up.shape, np.inf)
+    k = max(P - n, 0)
+    for sgn in (1, -1):
+        d = np.full(up.shape, np.nan)
+        bb = np.zeros(up.shape)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            if sgn > 0:
+                d[..., :k, :] = up[..., :k, :] - up[..., n:, :]
+                bb[..., :k, :] = b[..., :k, :] + b[..., n:, :]
+            else:
+                d[..., n:, :] = up[..., n:, :] - up[..., :k, :]
+                bb[..., n:, :] = b[..., n:, :] + b[..., :k, :]
+            bb = bb + sub_rounding(d, bb) + half_ulp(thr)
+            r = np.abs(d - thr) / bb
+        r = np.where(np.isnan(r), np.inf, r)     # (a NaN difference or bound belongs to a NaN value: +inf > thr)
+        ratio = np.minimum(ratio, r)
+    return ratio, np.ones(up.shape)
+
+
+def attenuated_decision_bound(ping_db, block_db, thr):
+    """``ping_db - block_db < thr`` (:642-644; the walk, :2889,:2914): both medians cast to float32
+    (``pooled_median_bound``), one float32 subtraction, the threshold rounded to float32."""
+    b = pooled_median_bound(ping_db) + pooled_median_bound(block_db)
+    with np.errstate(invalid="ignore"):
+        d = np.asarray(ping_db, np.float64) - np.asarray(block_db, np.float64)
+    return b + sub_rounding(d, b) + half_ulp(thr)
+
+
+def assert_few_near(margin, bound, what="", cap=1e-3):
+    """The cap on what a decision check may leave out: at most ``cap`` of the decisions may lie within the bound of the
+    threshold (a condition on the INPUT, asserted before comparing)."""
+    with np.errstate(invalid="ignore"):
+        near = np.abs(np.asarray(margin, np.float64)) <= np.broadcast_to(np.asarray(bound, np.float64), np.shape(margin))
+    assert near.mean() <= cap, f"{what}: {int(near.sum())} of {near.size} decisions lie within the bound of the threshold"
+    return int(near.sum())
 
 
 # ------------------------------------------------------------------------------------------------ checks

@@ -343,3 +343,248 @@ def test_power_terms_add_up_to_the_oracle():
         f = np.isfinite(exp)
         assert np.max(np.abs(tot[f] - exp[f])) <= 1e-12
         assert t["nspread"] == (20.0 if cal_type == "Sv" else 40.0)
+
+
+# ---------------------------------------------------------------------------------------------------- noise masks
+def _lin32(v32):
+    """exp10f(v * 0.1f) widened to double (csrc/fast_math.h:65): the rounded float64 10^x is within 1/2 ulp."""
+    arg = (np.asarray(v32, f32).astype(np.float64) * np.float64(f32(0.1))).astype(f32)
+    with np.errstate(over="ignore"):
+        return (10.0 ** arg.astype(np.float64)).astype(f32).astype(np.float64)
+
+
+def _db32(x):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (10.0 * np.log10(x)).astype(f32)
+
+
+def _windows(a, n, m):
+    """Every interior (2n+1) x (2m+1) window of a (P, S) array, flattened: (P - 2n, S - 2m, W)."""
+    w = np.lib.stride_tricks.sliding_window_view(a, (2 * n + 1, 2 * m + 1))
+    return w.reshape(w.shape[0], w.shape[1], -1)
+
+
+def _mask_field(kind, P=30, S=600, seed=3):
+    rng = np.random.default_rng(seed)
+    if kind == "scene":
+        from test_gpu_masks import _scene
+
+        sv = _scene(1, P, S, 7)[0][0]
+    elif kind == "spike60":
+        sv = -90 + 0.5 * rng.standard_normal((P, S))
+        sv[P // 2, S // 2] = -30.0
+    elif kind == "near0":
+        sv = rng.uniform(-0.01, 0.01, (P, S))
+    else:
+        sv = rng.uniform(-151, -149, (P, S))
+    if kind != "scene":
+        sv[rng.random((P, S)) < 0.02] = np.nan
+    return sv.astype(f32)
+
+
+@pytest.mark.parametrize("field", ["scene", "spike60", "near0", "deep"])
+@pytest.mark.parametrize("n,m", [(0, 0), (2, 7), (10, 250)])     # windows of 1, 75 and 10 521 values
+def test_pooled_mean_emulation_within_bound(field, n, m):
+    sv32 = _mask_field(field)
+    w64 = _windows(sv32.astype(np.float64), n, m)
+    with warnings.catch_warnings(), np.errstate(divide="ignore", invalid="ignore"):
+        warnings.simplefilter("ignore", RuntimeWarning)
+        exp = 10 * np.log10(np.nanmean(10.0 ** (w64 / 10), axis=-1))
+        lin = _windows(_lin32(sv32), n, m)
+        cnt = (~np.isnan(lin)).sum(-1)
+        for order in ("forward", "reverse"):       # double sums: the order is below the slack
+            ll = lin if order == "forward" else lin[..., ::-1]
+            s = np.cumsum(np.where(np.isnan(ll), 0.0, ll), axis=-1)[..., -1]
+            got = np.where(cnt > 0, _db32(s / cnt), np.nan)
+            b = fb.pooled_mean_bound(sv32, exp)
+            err, ratio = fb.assert_f32_close(got, exp, b, f"emulated pooled mean {field} {order}")
+            assert ratio <= 1.0 and (ratio > 0 or (n, m) == (0, 0))   # (one value: the round trip may be exact)
+    # the decision x - out > thr in float32
+    thr = 6.0
+    x = sv32[n:sv32.shape[0] - n, m:sv32.shape[1] - m]
+    with np.errstate(invalid="ignore"):
+        keep = (x - got.astype(f32)).astype(f32) > f32(thr)
+        margin = x.astype(np.float64) - exp - thr
+    fb.check_decisions(keep, margin > 0, margin, fb.threshold_decision_bound(x, exp, b, thr), f"decisions {field}")
+
+
+class _Dd:
+    """``Dd`` of csrc/noise_masks.hip:952-966, operation by operation in float64."""
+
+    def __init__(self, hi=0.0, lo=0.0):
+        self.hi, self.lo = np.float64(hi), np.float64(lo)
+
+    def add(self, x):
+        t = self.hi + x
+        bb = t - self.hi
+        self.lo = self.lo + ((self.hi - (t - bb)) + (x - bb))
+        self.hi = t
+
+    def add_dd(self, b, sign):
+        bh, bl = sign * b.hi, sign * b.lo
+        t = self.hi + bh
+        bb = t - self.hi
+        e = (self.hi - (t - bb)) + (bh - bb) + self.lo + bl
+        hi = t + e
+        self.hi, self.lo = hi, e - (hi - t)
+
+
+def test_running_sum_emulation_within_bound():
+    """Per-row double-double running sums and their differences (:943-951): a +60 dB sample early in a row of 3000
+    values near -100 dB; every window after it is 10^16 times weaker than the running sums it is the difference of."""
+    rng = np.random.default_rng(4)
+    S, m = 3000, 6
+    sv32 = (-100 + 2 * rng.standard_normal(S)).astype(f32)
+    sv32[40] = f32(60.0)
+    lin = _lin32(sv32)
+    W = []
+    acc = _Dd()
+    for x in lin:
+        acc.add(np.float64(x))
+        W.append(_Dd(acc.hi, acc.lo))
+    got = np.empty(S - 2 * m, f32)
+    for i, s in enumerate(range(m, S - m)):
+        d = _Dd(W[s + m].hi, W[s + m].lo)
+        if s - m - 1 >= 0:
+            d.add_dd(W[s - m - 1], -1.0)
+        got[i] = _db32(np.float64((d.hi + d.lo) / (2 * m + 1)))
+    exp = 10 * np.log10(_windows((10.0 ** (sv32.astype(np.float64) / 10))[None], 0, m)[0].mean(-1))
+    b = fb.pooled_mean_bound(sv32, exp, carried_terms=S, carried_ops=S)
+    fb.assert_f32_close(got, exp, b, "emulated running sums")
+    assert np.all(b[100:] < 2 * fb.pooled_mean_bound(sv32, exp)[100:])   # the subtraction costs less than the final rounding
+    # plain double running sums would not do: the same differences in float64 are off by far more than the bound
+    cs = np.concatenate([[0.0], np.cumsum(lin)])
+    plain = _db32((cs[2 * m + 1:] - cs[:-(2 * m + 1)]) / (2 * m + 1))
+    assert (np.abs(plain.astype(np.float64) - exp)[100:] > b[100:]).mean() > 0.9
+
+
+@pytest.mark.parametrize("field", ["scene", "spike60", "near0", "deep"])
+@pytest.mark.parametrize("n,m", [(0, 0), (2, 7), (1, 12)])        # 1, 75 (odd) values; NaNs make even counts as well
+def test_pooled_median_emulation_within_bound(field, n, m):
+    sv32 = _mask_field(field, P=12, S=200)
+    w32 = _windows(sv32, n, m)
+    with warnings.catch_warnings(), np.errstate(divide="ignore", invalid="ignore"):
+        warnings.simplefilter("ignore", RuntimeWarning)
+        exp = 10 * np.log10(np.nanmedian(10.0 ** (w32.astype(np.float64) / 10), axis=-1))
+        srt = np.sort(w32, axis=-1)                       # NaN last: the keys are the float32 values themselves
+        cnt = (~np.isnan(srt)).sum(-1)
+        k1, k2 = np.maximum(cnt - 1, 0) // 2, cnt // 2
+        a = np.take_along_axis(srt, k1[..., None], -1)[..., 0].astype(np.float64)
+        c = np.take_along_axis(srt, np.minimum(k2, srt.shape[-1] - 1)[..., None], -1)[..., 0].astype(np.float64)
+        med = np.where(k1 == k2, 10.0 ** (a / 10), (10.0 ** (a / 10) + 10.0 ** (c / 10)) * 0.5)   # the double table
+        got = np.where(cnt > 0, _db32(med), np.nan)
+    assert (cnt % 2 == 0).any() or (n, m) == (0, 0)
+    fb.assert_f32_close(got, exp, fb.pooled_median_bound(exp), f"emulated median {field}")
+
+
+def test_impulse_and_attenuated_decision_emulation_within_bound():
+    rng = np.random.default_rng(6)
+    sv32 = _mask_field("scene", P=40, S=200)
+    # smoothing: 10-sample bins, forward-filled (range_bin_smooth_kernel), then up[p] - up[p +- n] > thr in float32
+    nper, n, thr = 10, 2, 10.0
+    lin = _lin32(sv32).reshape(40, 20, nper)
+    with warnings.catch_warnings(), np.errstate(divide="ignore", invalid="ignore"):
+        warnings.simplefilter("ignore", RuntimeWarning)
+        up32 = np.repeat(_db32(np.nanmean(lin, -1)), nper, axis=1)
+        up = np.repeat(10 * np.log10(np.nanmean(10.0 ** (sv32.astype(np.float64).reshape(40, 20, nper) / 10), -1)), nper, 1)
+    b_up = fb.pooled_mean_bound(sv32, up)
+    fb.assert_f32_close(up32, up, b_up, "emulated smoothing")
+    from oracle import masks as omask
+
+    exp = omask.echopy_impulse_noise_mask(up.T, n, thr).T
+    fwd = np.full(up32.shape, np.inf, f32)
+    bwd = np.full(up32.shape, np.inf, f32)
+    with np.errstate(invalid="ignore"):
+        fwd[:-n] = up32[:-n] - up32[n:]
+        bwd[n:] = up32[n:] - up32[:-n]
+    fwd[np.isnan(fwd)] = np.inf
+    bwd[np.isnan(bwd)] = np.inf
+    got = (fwd > f32(thr)) & (bwd > f32(thr))
+    margin, bound = fb.impulse_decision_bound(up, b_up, n, thr)
+    fb.check_decisions(got, exp, margin, bound, "emulated impulse mask")
+    assert exp.any() and not exp.all()
+    # attenuated: two medians cast to float32, one subtraction
+    ping = rng.uniform(-90, -60, 5000)
+    block = ping + rng.uniform(-8.001, -7.999, 5000)
+    athr = 8.0
+    got = (ping.astype(f32) - block.astype(f32)).astype(f32) < f32(athr)
+    fb.check_decisions(got, ping - block < athr, ping - block - athr, fb.attenuated_decision_bound(ping, block, athr))
+
+
+# ------------------------------------------------------------------------------------------ noise masks: sharpness
+def _pool_case(n=2, m=12, seed=8):
+    """A non-flat field (0.3 dB) pooled over 5 x 25 = 125-value windows: (sv32 interior, linear windows, exp, bound)."""
+    rng = np.random.default_rng(seed)
+    sv32 = (-70 + 0.3 * rng.standard_normal((12, 120))).astype(f32)
+    lin = _windows(10.0 ** (sv32.astype(np.float64) / 10), n, m)
+    exp = 10 * np.log10(lin.mean(-1))
+    return sv32, lin, exp, fb.pooled_mean_bound(sv32, exp)
+
+
+def test_sharp_pooled_value_times_1_plus_1e_3():
+    sv32, lin, exp, b = _pool_case()
+    _assert_sharp(exp + 10 * np.log10(1 + 1e-3), exp, b)
+
+
+def test_sharp_window_loses_or_gains_an_edge_sample():
+    sv32, lin, exp, b = _pool_case()
+    assert lin.shape[-1] >= 50
+    _assert_sharp(10 * np.log10(lin[..., :-1].mean(-1)), exp, b)                      # the last edge sample dropped
+    extra = 10.0 ** (np.roll(sv32, -1, axis=1)[2:-2, 12:-12].astype(np.float64) / 10)  # one sample beyond the edge added
+    _assert_sharp(10 * np.log10((lin.sum(-1) + extra) / (lin.shape[-1] + 1)), exp, b)
+
+
+@pytest.mark.parametrize("func", [np.nanmean, np.nanmedian])
+def test_sharp_membership_on_the_float64_depth(func):
+    """Window edges that fall on samples (0.3 m steps, a 1.5 m bin): d +- bin rounds differently in float32 and float64,
+    so the two memberships differ at some outputs -- where they differ by no more than the old bar, only the derived
+    bound tells them apart."""
+    from oracle import masks as omask
+
+    rng = np.random.default_rng(5)
+    C, P, S, n = 1, 7, 160, 1
+    sv32 = (-70 + 0.3 * rng.standard_normal((C, P, S))).astype(f32)
+    d32 = np.broadcast_to((0.3 * (np.arange(S) + 5)).astype(f32), (C, P, S)).copy()
+    sv64 = sv32.astype(np.float64)
+    exp = omask.pool_Sv(sv64, d32, func, f32(1.5), n, f32(2.0))
+    bad = omask.pool_Sv(sv64, d32.astype(np.float64), func, 1.5, n, 2.0)
+    b = fb.pooled_mean_bound(sv32, exp) if func is np.nanmean else fb.pooled_median_bound(exp)
+    np.testing.assert_array_equal(np.isnan(bad), np.isnan(exp))
+    fin = np.isfinite(exp)
+    differ = np.abs(bad - exp)[fin] > b[fin]
+    assert differ.mean() >= 0.01, differ.mean()
+    with np.errstate(invalid="ignore"):   # (a median may jump by more than the old bar: those the old bar sees too)
+        quiet = np.abs(bad - exp) <= fb.OLD_RTOL * np.maximum(np.abs(exp), 1.0)
+    bad = np.where(quiet, bad, exp)
+    assert (np.abs(bad - exp)[fin] > b[fin]).any()
+    assert _old_ok(bad, exp), "0.3 dB of spread keeps these wrong windows inside the old bar"
+    assert not _new_ok(bad, exp, b)
+
+
+def test_sharp_median_takes_the_upper_middle_value():
+    rng = np.random.default_rng(9)
+    w = np.sort((-70 + 0.3 * rng.standard_normal((500, 50))).astype(f32).astype(np.float64), axis=-1)   # even counts
+    exp = 10 * np.log10((10.0 ** (w[:, 24] / 10) + 10.0 ** (w[:, 25] / 10)) / 2)
+    np.testing.assert_allclose(exp, 10 * np.log10(np.median(10.0 ** (w / 10), axis=-1)), rtol=0, atol=1e-12)
+    _assert_sharp(w[:, 25], exp, fb.pooled_median_bound(exp))
+
+
+def test_sharp_mask_decision_flipped_1e_3_db_from_its_threshold():
+    sv32, lin, exp, b = _pool_case()
+    x = sv32[2:-2, 12:-12].astype(np.float64)
+    thr = 0.25
+    exp = exp.copy()
+    exp[3, 40] = x[3, 40] - thr - 1e-3                      # this decision sits 1e-3 dB above its threshold
+    margin = x - exp - thr
+    keep = margin > 0
+    bd = fb.threshold_decision_bound(x, exp, b, thr)
+    assert fb.assert_few_near(margin, bd) == 0
+    fb.check_decisions(keep, keep, margin, bd)
+    flipped = keep.copy()
+    flipped[3, 40] = ~flipped[3, 40]
+    sure = ~(np.abs(margin) < 2e-3)                         # the old margin leaves this decision out
+    np.testing.assert_array_equal(flipped[sure], keep[sure])
+    with pytest.raises(AssertionError, match="outside the bound"):
+        fb.check_decisions(flipped, keep, margin, bd)
+    with pytest.raises(AssertionError, match="within the bound"):
+        fb.assert_few_near(np.zeros(10), bd.ravel()[:10])

@@ -112,6 +112,7 @@ def test_random_masks_and_nasc(ep, seed):
     np.testing.assert_array_equal(att, exp_att)
     out = ep.mask.apply_mask(ds, [ep.DataArray(~att, DIMS3), ep.DataArray(~m, DIMS3)], fill_value=-1.0)
     np.testing.assert_array_equal(out["Sv"].values, omask.apply_mask(sv, [~exp_att, ~m], -1.0))
+    _masks_in_float32(ep, sv, depth, n, dbin, excl, func, up, lw)
     # NASC on the same scene with a random track
     lat = 40.0 + np.cumsum(rng.uniform(0, 2e-4, P))
     lon = -125.0 + np.cumsum(rng.uniform(0, 2e-4, P))
@@ -126,6 +127,62 @@ def test_random_masks_and_nasc(ep, seed):
 
 
 DIMS3 = ("channel", "ping_time", "range_sample")
+
+
+def _masks_in_float32(ep, sv, depth, n, dbin, excl, func, up, lw):
+    """The float32 pass of test_random_masks_and_nasc: the three masks of the same scene cast to float32, EVERY seed and
+    every mask the float64 pass compares, judged by the derived bounds of tests/f32_bounds.py (a decision may differ only
+    within the bound of the compared quantity, and at most 0.1 % of them may lie there).
+
+    The oracle is given what the API computes from a float32 range ("fp32 bounds"):
+      * the samples per bin ceil(bin / nanmean(diff(range))) come from the DOUBLE mean of the float32 steps
+        (clean/api.py ``_samples_per_bin``) -- index binning reads the range for nothing else, so its oracle takes the
+        float32 range upcast;
+      * the value bins of the impulse mask are the double edges r0 + j * bin from the float32 minimum r0
+        (np.arange on Python floats) -- the oracle takes the float32 range upcast and the bin as a Python float, which
+        are those edges and the same comparisons;
+      * the layer limits of the attenuated mask are rounded to float32 and |range - limit| is a float32 difference: the
+        oracle takes the float32 range and np.float32 limits."""
+    import f32_bounds as fb
+    from mask_judges import judge_attenuated
+    from oracle import masks as omask
+    from test_gpu_masks_api import _ds
+
+    f32 = np.float32
+    sv32, d32 = sv.astype(f32), depth.astype(f32)
+    sv64, d64 = sv32.astype(np.float64), d32.astype(np.float64)
+    C, P, S = sv.shape
+    ds = _ds(ep, sv32, d32)
+    b = float(dbin[:-1])
+    for index in (True, False):
+        m = ep.clean.mask_impulse_noise(ds, depth_bin=dbin, num_side_pings=n, use_index_binning=index).values
+        ups = omask.index_binning_downsample_upsample(sv64, d64, b) if index else omask.downsample_upsample(sv64, d64, b)[1]
+        exp = np.stack([omask.echopy_impulse_noise_mask(ups[c].T, n, 10.0) for c in range(C)])
+        margin, bound = fb.impulse_decision_bound(ups, fb.pooled_mean_bound(sv32, ups), n, 10.0)
+        margin, bound = margin.transpose(0, 2, 1), bound.transpose(0, 2, 1)
+        fb.assert_few_near(margin, bound, f"impulse f32 index={index}")
+        fb.check_decisions(m, exp, margin, bound, f"impulse f32 index={index}")
+    m = ep.clean.mask_transient_noise(ds, func=func, depth_bin=dbin, num_side_pings=n, exclude_above=excl,
+                                      transient_noise_threshold="6.0dB", use_index_binning=True).values
+    m_c = omask.nsamples_per_bin(d64, b)
+    if 2 * m_c.max() + 1 <= 2 * S and 2 * n + 1 <= 2 * P:   # (the float64 pass's condition on scipy's reflect: see there)
+        f = np.nanmean if func == "nanmean" else np.nanmedian
+        pooled = omask.index_binning_pool_Sv(sv64, d64, f, b, n, float(excl[:-1]))
+        with np.errstate(invalid="ignore"):
+            margin = sv64 - pooled - 6.0
+        W = (2 * n + 1) * (2 * int(m_c.max()) + 1)
+        bp = fb.pooled_mean_bound(sv32, pooled, carried_terms=W, carried_ops=P) if func == "nanmean" else \
+            fb.pooled_median_bound(pooled)
+        bound = fb.threshold_decision_bound(sv64, pooled, bp, 6.0)
+        fb.assert_few_near(margin, bound, "transient f32")
+        fb.check_decisions(m, margin > 0, margin, bound, "transient f32")
+    upv, lwv = float(f"{up:09.3f}"), float(f"{lw:09.3f}")
+    att = ep.clean.mask_attenuated_signal(ds, upper_limit_sl=f"{up:09.3f}m", lower_limit_sl=f"{lw:09.3f}m",
+                                          num_side_pings=n, attenuation_signal_threshold="-3.0dB").values
+    if upv > float(np.nanmax(d32)) or lwv < float(np.nanmin(d32)):   # (clean/api.py:322-324 of the reference)
+        assert not att.any()
+    else:
+        judge_attenuated("attenuated f32", att, sv32, d32, upv, lwv, n, -3.0, need_both=False)
 
 
 @pytest.mark.parametrize("seed", range(12))

@@ -2,21 +2,26 @@
 and vs the outputs of the reference's own leaf functions (tests/golden/ref_mask_goldens.npz).
 
 Masks are boolean: they must be IDENTICAL wherever the oracle's decision margin
-|difference - threshold| exceeds the floating-point noise of the compared quantity (1e-9 dB in
-fp64, 1e-3 dB in fp32); the pooled / smoothed Sv they derive from are held to the usual tolerances.
+|difference - threshold| exceeds the floating-point noise of the compared quantity: 1e-9 dB in
+fp64, in fp32 the bound tests/f32_bounds.py derives from the kernel's operations (a few 1e-6 dB).
+The pooled / smoothed Sv they derive from are held to 1e-9 in fp64 and to those bounds in fp32.
+A float32 case calls the oracle with the float32 range array and float32 window parameters (and
+the float32 Sv values upcast to float64): window edges and feasibility are then evaluated as the
+kernels evaluate them, in float32, and the oracle's windows are the kernel's windows.
 """
 import os
 
 import numpy as np
 import pytest
 
+import f32_bounds as fb
+from mask_judges import F64_TOL, close as _close, judge_attenuated as _judge_attenuated, judge_pooled as _judge_pooled, \
+    t_of as _t, value_mean_bound as _value_mean_bound
 from oracle import masks as omask
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_mask_goldens.npz")
-RTOL = {"float64": 1e-9, "float32": 1e-3}
-MARGIN = {"float64": 1e-9, "float32": 2e-3}
 
 
 @pytest.fixture(scope="module")
@@ -38,16 +43,6 @@ def gold():
 def _dev(torch, a, dtype=None):
     t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
     return t.to(dtype) if dtype is not None else t
-
-
-def _close(got, exp, rtol, what=""):
-    got, exp = np.asarray(got, dtype=np.float64), np.asarray(exp, dtype=np.float64)
-    assert got.shape == exp.shape
-    np.testing.assert_array_equal(np.isnan(got), np.isnan(exp), err_msg=f"{what}: NaN pattern")
-    fin = np.isfinite(exp)
-    np.testing.assert_array_equal(got[~fin & ~np.isnan(exp)], exp[~fin & ~np.isnan(exp)])
-    err = np.abs(got[fin] - exp[fin]) / np.maximum(np.abs(exp[fin]), 1.0)
-    assert err.size == 0 or err.max() <= rtol, f"{what}: max rel err {err.max():.3e} > {rtol}"
 
 
 def _scene(C, P, S, seed, step=0.19, nan_frac=0.03, spikes=True, ragged=False):
@@ -74,13 +69,17 @@ def test_range_bin_smooth_index_mode(env, dtype):
     torch, ops = env
     sv, depth = _scene(3, 17, 203, 1, ragged=True)
     sv, depth = sv.astype(dtype), depth.astype(dtype)
+    # (index binning reads the range only for ceil(bin / mean step), which the API takes from the DOUBLE mean of the steps)
     exp = omask.index_binning_downsample_upsample(sv.astype(np.float64), depth.astype(np.float64), 2.0)
     n = omask.nsamples_per_bin(depth.astype(np.float64), 2.0)
     assert len(set(n.tolist())) == 3  # channel-specific block lengths
     svt = _dev(torch, sv)
     for c in range(3):
         got = ops.range_bin_smooth(svt[c:c + 1].contiguous(), nper=int(n[c])).cpu().numpy()
-        _close(got[0], exp[c], RTOL[dtype], f"channel {c}")
+        if dtype == "float64":
+            _close(got[0], exp[c], F64_TOL, f"channel {c}")
+        else:
+            fb.assert_f32_close(got[0], exp[c], fb.pooled_mean_bound(sv, exp[c]), f"mask: range_bin_smooth index, channel {c}")
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
@@ -90,12 +89,15 @@ def test_range_bin_smooth_value_mode(env, dtype):
     sv[0, 3, :] = np.nan  # an all-NaN ping -> every bin NaN
     sv, depth = sv.astype(dtype), depth.astype(dtype)
     d64 = depth.astype(np.float64)
-    down, exp = omask.downsample_upsample(sv.astype(np.float64), d64, 5.0)
+    down, exp = omask.downsample_upsample(sv.astype(np.float64), depth, _t(dtype, 5.0))
     r0 = float(np.nanmin(d64))
     nb = len(np.arange(r0, np.nanmax(d64) + 5.0, 5.0)) - 1
     assert down.shape[-1] == nb
     got = ops.range_bin_smooth(_dev(torch, sv), range=_dev(torch, depth), r0=r0, bin=5.0, nbins=nb)
-    _close(got.cpu().numpy(), exp, RTOL[dtype])
+    if dtype == "float64":
+        _close(got.cpu().numpy(), exp, F64_TOL)
+    else:
+        fb.assert_f32_close(got.cpu().numpy(), exp, fb.pooled_mean_bound(sv, exp), "mask: range_bin_smooth value mode")
 
 
 def test_range_bin_smooth_value_mode_edges_and_nan_depth(env):
@@ -211,11 +213,10 @@ def test_attenuated_mask_vs_oracle(env, dtype):
     exp = np.stack([omask.echopy_attenuated_signal_mask(sv[c].astype(np.float64), depth[c],
                                                         np.dtype(dtype).type(30.0), np.dtype(dtype).type(90.0),
                                                         6, -5.0) for c in range(3)])
-    diff = got.astype(bool) != exp
     if dtype == "float64":
-        assert not diff.any()
-    else:  # a ping whose median difference sits within fp32 noise of the threshold may flip
-        assert diff.any(axis=2).sum() <= 1
+        assert not (got.astype(bool) != exp).any()
+    else:  # a ping may differ only where its median difference lies within the derived bound of the threshold
+        np.testing.assert_array_equal(_judge_attenuated("attenuated_mask", got, sv, depth, 30.0, 90.0, 6, -5.0), exp)
     assert exp.any() and not exp.all()
 
 
@@ -230,7 +231,7 @@ def test_pool_sv_vs_generic_filter(env, dtype, func):
     sv[0, 5:9, 30:50] = np.nan  # a window with no valid sample at all
     sv, depth = sv.astype(dtype), depth.astype(dtype)
     f = np.nanmean if func == "nanmean" else np.nanmedian
-    d64 = depth.astype(np.float64)
+    d64 = depth.astype(np.float64)   # (read only for ceil(bin / mean step) -- a double mean in the API -- and for s0)
     m = omask.nsamples_per_bin(d64, 2.0)
     exclude_above = 6.0
     s0 = int(np.argmin(d64 <= exclude_above))
@@ -240,12 +241,12 @@ def test_pool_sv_vs_generic_filter(env, dtype, func):
     svt = _dev(torch, sv)
     for c in range(C):
         pooled, mask = ops.pool_sv(svt[c:c + 1].contiguous(), s0, 3, int(m[c]), func=func, threshold=thr)
-        _close(pooled.cpu().numpy()[0], exp[c], RTOL[dtype], f"{func} channel {c}")
+        W = 7 * (2 * int(m[c]) + 1)
+        bound = None if dtype == "float64" else (fb.pooled_mean_bound(sv[c], exp[c], carried_terms=W, carried_ops=P)
+                                                 if func == "nanmean" else fb.pooled_median_bound(exp[c]))
+        _judge_pooled(dtype, f"{func} channel {c}", sv[c], pooled.cpu().numpy()[0], mask.cpu().numpy()[0], exp[c], thr, bound)
         with np.errstate(invalid="ignore"):
-            margin = sv[c].astype(np.float64) - exp[c] - thr
-        sure = ~(np.abs(margin) < MARGIN[dtype])
-        np.testing.assert_array_equal(mask.cpu().numpy()[0].astype(bool)[sure], (margin > 0)[sure])
-        assert (margin > 0).any()
+            assert (sv[c].astype(np.float64) - exp[c] - thr > 0).any()
 
 
 def test_pool_sv_window_larger_than_array(env):
@@ -367,12 +368,9 @@ def test_pool_sv_median_window_carried_from_ping_to_ping(env, dtype):
     got = pooled.cpu().numpy()[0]
     assert np.isnan(got[:, :2]).all() and not mask.cpu().numpy()[0, :, :2].any()
     exp2 = _median_filter_db(sv[0, :, 2:], n, m)  # pooled from the first sample on: the reflect domain starts there
-    _close(got[:, 2:], exp2, RTOL[dtype], "carried median")
     assert np.isnan(exp2).any() and (exp2[np.isfinite(exp2)] < -256).any() and (exp2[np.isfinite(exp2)] > 0).any()
-    with np.errstate(invalid="ignore"):
-        margin = sv[0, :, 2:].astype(np.float64) - exp2 - thr
-    sure = ~(np.abs(margin) < MARGIN[dtype])
-    np.testing.assert_array_equal(mask.cpu().numpy()[0, :, 2:].astype(bool)[sure], (margin > 0)[sure])
+    _judge_pooled(dtype, "carried median", sv[0, :, 2:], got[:, 2:], mask.cpu().numpy()[0, :, 2:], exp2, thr,
+                  None if dtype == "float64" else fb.pooled_median_bound(exp2))
 
 
 def test_pool_sv_median_of_a_flat_field_uses_the_radix_selection(env):
@@ -439,12 +437,10 @@ def test_pool_sv_value_running_sums_equal_window_sums(env, dtype, same_rows):
     np.testing.assert_array_equal(np.isnan(a), np.isnan(b))
     _close(a, b, 1e-12 if dtype == "float64" else 1e-5, "running sums vs window sums")
     assert np.isposinf(a).any() and np.isfinite(a).any()
-    exp = omask.pool_Sv(sv.astype(np.float64), depth.astype(np.float64), np.nanmean, dbin, n, 2.0)
-    _close(a, exp, RTOL[dtype], "vs oracle")
-    agree = ma.cpu().numpy() == mb.cpu().numpy()
-    with np.errstate(invalid="ignore"):
-        sure = ~(np.abs(sv.astype(np.float64) - exp - 6.0) < MARGIN[dtype])
-    assert agree[sure].all()
+    exp = omask.pool_Sv(sv.astype(np.float64), depth, np.nanmean, _t(dtype, dbin), n, _t(dtype, 2.0))
+    bound = None if dtype == "float64" else _value_mean_bound(sv, exp, n)
+    _judge_pooled(dtype, "running sums vs oracle", sv, a, ma.cpu().numpy(), exp, 6.0, bound)
+    _judge_pooled(dtype, "window sums vs oracle", sv, b, mb.cpu().numpy(), exp, 6.0, bound)
 
 
 @pytest.mark.parametrize("same_rows", [False, True, "mixed"])
@@ -484,14 +480,11 @@ def test_pool_sv_value_median_carried_window_equals_windows_from_memory(env, dty
     a, b = a.cpu().numpy(), b.cpu().numpy()
     np.testing.assert_array_equal(a, b)   # the same two middle values, the same conversion
     np.testing.assert_array_equal(ma.cpu().numpy(), mb.cpu().numpy())
-    exp = omask.pool_Sv(sv.astype(np.float64), depth.astype(np.float64), np.nanmedian, dbin, n, 2.0)
-    if dtype == "float64":
-        _close(a, exp, RTOL[dtype], "vs oracle")
-    else:  # d +- bin in fp32 moves a sample on a window edge in or out: a median may jump to its neighbour value
-        np.testing.assert_array_equal(np.isnan(a), np.isnan(exp))
-        fin = np.isfinite(exp)
-        off = np.abs(a[fin] - exp[fin]) > 1e-3 * np.maximum(np.abs(exp[fin]), 1.0)
-        assert off.mean() < 2e-3 and np.abs(a[fin] - exp[fin])[off].max(initial=0.0) < 1.0
+    # (float32: d +- bin in float32 moves a sample on a window edge in or out -- the oracle is given the float32 range and
+    #  bin, so its windows are the kernel's and every median is the same middle pair)
+    exp = omask.pool_Sv(sv.astype(np.float64), depth, np.nanmedian, _t(dtype, dbin), n, _t(dtype, 2.0))
+    _judge_pooled(dtype, "carried window vs oracle", sv, a, ma.cpu().numpy(), exp, 6.0,
+                  None if dtype == "float64" else fb.pooled_median_bound(exp))
     assert np.isfinite(exp[:, P - n]).any() and np.isnan(exp[:, P - n + 1:]).all() and np.isnan(exp[:, :n]).all()
 
 
@@ -583,11 +576,17 @@ def test_pool_sv_value_staged_neighbour_rows(env, dtype, case):
     b, mb = ops.pool_sv_value(svt, rgt, nvalid, dbin, n, 2.0, lo, hi, threshold=6.0, running_sums=False)
     a, b = a.cpu().numpy(), b.cpu().numpy()
     np.testing.assert_array_equal(np.isnan(a), np.isnan(b))
-    _close(a, b, 1e-12 if dtype == "float64" else 1e-5, "staged running sums vs window sums")
     assert np.isposinf(a).any() and np.isfinite(a).any()
-    if case in ("blocks_of_pings", "rows_not_affine", "a_shallow_neighbour_row") and dtype == "float64":  # (fp32 window edges d -+ bin round differently: a vs b only)
-        exp = omask.pool_Sv(sv.astype(np.float64), depth.astype(np.float64), np.nanmean, dbin, n, 2.0)
-        _close(a, exp, RTOL[dtype], "vs oracle")
+    if dtype == "float64":
+        _close(a, b, 1e-12, "staged running sums vs window sums")
+        if case in ("blocks_of_pings", "rows_not_affine", "a_shallow_neighbour_row"):
+            exp = omask.pool_Sv(sv, depth, np.nanmean, dbin, n, 2.0)
+            _close(a, exp, F64_TOL, "vs oracle")
+    else:  # each route against the oracle on the float32 range and bin (its windows are the kernels' windows)
+        exp = omask.pool_Sv(sv.astype(np.float64), depth, np.nanmean, _t(dtype, dbin), n, _t(dtype, 2.0))
+        bound = _value_mean_bound(sv, exp, n)
+        _judge_pooled(dtype, "staged running sums vs oracle", sv, a, ma.cpu().numpy(), exp, 6.0, bound)
+        _judge_pooled(dtype, "window sums vs oracle", sv, b, mb.cpu().numpy(), exp, 6.0, bound)
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
@@ -633,11 +632,17 @@ def test_pool_sv_value_runs_of_one_range_vector(env, dtype, case):
     b, mb = ops.pool_sv_value(svt, rgt, nvalid, dbin, n, 2.0, lo, hi, threshold=6.0, running_sums=False)
     a, b = a.cpu().numpy(), b.cpu().numpy()
     np.testing.assert_array_equal(np.isnan(a), np.isnan(b))
-    _close(a, b, 1e-12 if dtype == "float64" else 1e-5, "runs vs window sums")
     assert np.isposinf(a).any() and np.isfinite(a).any()
-    if dtype == "float64" and case in ("runs", "bridged"):  # (the triple loop takes half a minute at this size)
-        exp = omask.pool_Sv(sv.astype(np.float64), depth.astype(np.float64), np.nanmean, dbin, n, 2.0)
-        _close(a, exp, RTOL[dtype], "vs oracle")
+    if dtype == "float64":
+        _close(a, b, 1e-12, "runs vs window sums")
+        if case in ("runs", "bridged"):  # (the triple loop takes a quarter of a minute at this size)
+            exp = omask.pool_Sv(sv, depth, np.nanmean, dbin, n, 2.0)
+            _close(a, exp, F64_TOL, "vs oracle")
+    else:  # each route against the oracle on the float32 range and bin
+        exp = omask.pool_Sv(sv.astype(np.float64), depth, np.nanmean, _t(dtype, dbin), n, _t(dtype, 2.0))
+        bound = _value_mean_bound(sv, exp, n)
+        _judge_pooled(dtype, "runs vs oracle", sv, a, ma.cpu().numpy(), exp, 6.0, bound)
+        _judge_pooled(dtype, "window sums vs oracle", sv, b, mb.cpu().numpy(), exp, 6.0, bound)
 
 
 def test_pool_sv_everything_above_exclusion(env):

@@ -8,6 +8,7 @@ import logging
 import numpy as np
 import pytest
 
+import f32_bounds as fb
 from oracle import masks as omask
 from test_gpu_masks import _scene
 
@@ -77,12 +78,22 @@ def test_mask_impulse_noise(ep, use_index_binning, on_device):
 
 
 def test_mask_impulse_noise_echo_range_f32(ep):
+    """float32 Sv and range: the oracle on the float32 Sv upcast, the WHOLE mask equal outside the derived bound of the
+    two smoothed values compared (tests/f32_bounds.py), at most 0.1 % of the decisions inside it."""
     sv, depth = _scene(2, 30, 200, 22)
-    ds = _ds(ep, sv.astype(np.float32), depth.astype(np.float32), range_name="echo_range")
+    sv32, d32 = sv.astype(np.float32), depth.astype(np.float32)
+    ds = _ds(ep, sv32, d32, range_name="echo_range")
     m = ep.clean.mask_impulse_noise(ds, range_var="echo_range", use_index_binning=True).values
-    exp = omask.mask_impulse_noise(sv.astype(np.float32).astype(np.float64),
-                                   depth.astype(np.float32).astype(np.float64), use_index_binning=True)
-    assert (m != exp).mean() < 2e-3  # fp32 decision noise only
+    # (index binning reads the range only for ceil(bin / mean step), which the API takes from the DOUBLE mean of the steps)
+    d64 = d32.astype(np.float64)
+    up = omask.index_binning_downsample_upsample(sv32.astype(np.float64), d64, 5.0)
+    exp = np.stack([omask.echopy_impulse_noise_mask(up[c].T, 2, 10.0) for c in range(2)])
+    np.testing.assert_array_equal(exp, omask.mask_impulse_noise(sv32.astype(np.float64), d64, use_index_binning=True))
+    margin, bound = fb.impulse_decision_bound(up, fb.pooled_mean_bound(sv32, up), 2, 10.0)
+    margin, bound = margin.transpose(0, 2, 1), bound.transpose(0, 2, 1)
+    fb.assert_few_near(margin, bound, "impulse mask, float32")
+    fb.check_decisions(m, exp, margin, bound, "impulse mask, float32")
+    assert exp.any() and not exp.all()
 
 
 # --------------------------------------------------------------------------------- transient noise
@@ -112,15 +123,24 @@ def test_mask_transient_noise(ep, func, use_index_binning):
 
 
 def test_mask_transient_noise_value_window_ragged_and_f32(ep):
+    """float32 Sv and depth: the oracle's windows are taken on the float32 depth with the bin and ``exclude_above`` in
+    float32, as the kernels take them; the WHOLE mask equal outside the derived bound of Sv - pooled."""
     sv, depth = _scene(2, 14, 50, 24, step=0.5, ragged=True)
-    ds = _ds(ep, sv.astype(np.float32), depth.astype(np.float32))
+    sv32, d32 = sv.astype(np.float32), depth.astype(np.float32)
+    ds = _ds(ep, sv32, d32)
     m = ep.clean.mask_transient_noise(ds, depth_bin="2m", num_side_pings=2, exclude_above="4.0m",
                                       transient_noise_threshold="6.0dB").values
-    sv32, d32 = sv.astype(np.float32).astype(np.float64), depth.astype(np.float32).astype(np.float64)
-    pooled = omask.pool_Sv(sv32, d32, np.nanmean, 2.0, 2, 4.0)
+    sv64 = sv32.astype(np.float64)
+    pooled = omask.pool_Sv(sv64, d32, np.nanmean, np.float32(2.0), 2, np.float32(4.0))
     with np.errstate(invalid="ignore"):
-        margin = sv32 - pooled - 6.0
-    _same_mask(m, margin > 0, ~(np.abs(margin) < 2e-3))
+        margin = sv64 - pooled - 6.0
+    P, S = sv.shape[1:]
+    b = fb.pooled_mean_bound(sv32, pooled, carried_terms=5 * S, carried_ops=S + P)
+    bound = fb.threshold_decision_bound(sv64, pooled, b, 6.0)
+    fb.assert_few_near(margin, bound, "transient mask, float32")
+    assert m.dtype == np.bool_
+    fb.check_decisions(m, margin > 0, margin, bound, "transient mask, float32")
+    assert (margin > 0).any() and not (margin > 0).all()
 
 
 def test_mask_transient_noise_errors_and_warning(ep, caplog):
