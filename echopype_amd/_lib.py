@@ -98,6 +98,7 @@ SIGNATURES = {
     "epa_selftest_lin_from_db": [_vp, _vp, _sz, _vp],
     "epa_selftest_log10": [_vp, _vp, _sz, _vp],
     "epa_selftest_log10_inline": [_vp, _vp, _sz, _vp],
+    "epa_selftest_correlate": [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "epa_mvbs_finalize": [_vp, _vp, _sz, _d, _vp, _i, _vp],
     "epa_edge_pack": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "epa_edge_prepare_max": [_vp, _i, _vp],

@@ -736,7 +736,48 @@ __global__ __launch_bounds__(epa::kBlock) void range_complex_kernel(const InT* _
   }
 }
 
+// Self-test of the transform alone: tile `blockIdx.x` of x (2048 complex samples, lane j owns j + 256 i as in
+// process_tile) through correlate<F> with the spectrum replica_prepare_kernel left in the workspace, raw output.
+template <typename F>
+__global__ __launch_bounds__(epa::kBlock) void selftest_correlate_kernel(const C2<F>* __restrict__ x,
+                                                                         const double* __restrict__ ws,
+                                                                         C2<F>* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) unsigned char xs[Xs<F>::kBytes];
+  __shared__ C2<F> tw[kTwEntries<F>];
+  const int j = threadIdx.x;
+  const C2<F>* wtab = reinterpret_cast<const C2<F>*>(ws + (sizeof(F) == 4 ? ws_tw32() : ws_tw64()));
+  if (!kSmallTw<F>) tw[j] = wtab[j];  // as stage_tables; published by correlate()'s first barrier
+  else if (j < 68) tw[j] = j < 64 ? wtab[4 * j] : wtab[j - 64];
+  const C2<F>* spec = reinterpret_cast<const C2<F>*>(ws + (sizeof(F) == 4 ? ws_spec32(1, 0) : ws_spec64(1, 0)));
+  const LaneMap lm = lane_map();
+  const size_t base = (size_t)blockIdx.x * kN;
+  C2<F> v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = x[base + j + 256 * i];
+  correlate<F>(v, xs, tw, spec, lm, wtab[j]);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out[base + j + 256 * i] = v[i];
+}
+
 }  // namespace
+
+extern "C" int epa_selftest_correlate(const void* x, int n_tiles, const float* replica, const int32_t* replica_off,
+                                      int fft_dtype, void* out, double* workspace, epa_stream_t stream) {
+  EPA_CHECK_ARG(x && replica && replica_off && out && workspace, "epa_selftest_correlate: NULL array argument");
+  EPA_CHECK_ARG(n_tiles > 0, "epa_selftest_correlate: n_tiles=%d", n_tiles);
+  EPA_CHECK_ARG(fft_dtype == EPA_F32 || fft_dtype == EPA_F64, "epa_selftest_correlate: bad fft_dtype %d", fft_dtype);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(replica_prepare_kernel, dim3(1), dim3(epa::kBlock), 0, st, replica, replica_off, 1, workspace, 0,
+                     workspace + ws_logtab(1, 1, 1));
+  if (int rc = epa::check_launch("replica_prepare_kernel")) return rc;
+  if (fft_dtype == EPA_F32)
+    hipLaunchKernelGGL(selftest_correlate_kernel<float>, dim3((unsigned)n_tiles), dim3(epa::kBlock), 0, st,
+                       reinterpret_cast<const C2<float>*>(x), workspace, reinterpret_cast<C2<float>*>(out));
+  else
+    hipLaunchKernelGGL(selftest_correlate_kernel<double>, dim3((unsigned)n_tiles), dim3(epa::kBlock), 0, st,
+                       reinterpret_cast<const C2<double>*>(x), workspace, reinterpret_cast<C2<double>*>(out));
+  return epa::check_launch("selftest_correlate_kernel");
+}
 
 extern "C" int epa_range_complex(const void* re, int in_dtype, const double* ccoef, int C, int P, int S, int B,
                                  void* range_out, int out_dtype, epa_stream_t stream) {

@@ -503,6 +503,26 @@ def selftest_log10(x, inline=False):
     return out
 
 
+def selftest_correlate(x, replica, fft_dtype=None):
+    """The raw output of the LDS transform's circular correlation (accuracy self-test): ``x`` (T, 2048) complex64 /
+    complex128 tiles, ``replica`` complex64 (taps <= 2048) -> out[t, k] = sum_j x[t, (k + j) mod 2048] conj(replica[j])
+    in ``x``'s precision, through the spectrum the replica preparation of sv_complex's fft form builds."""
+    if x.dim() != 2 or x.shape[1] != _lib.EK80_NFFT or x.dtype not in (torch.complex64, torch.complex128):
+        raise ValueError(f"x: (T, {_lib.EK80_NFFT}) complex64 / complex128 tiles expected")
+    if replica.dtype != torch.complex64 or replica.dim() != 1 or not 1 <= replica.numel() <= _lib.EK80_NFFT:
+        raise ValueError(f"replica: 1 .. {_lib.EK80_NFFT} complex64 taps expected")
+    fdt = torch.float32 if x.dtype == torch.complex64 else torch.float64
+    if fft_dtype is not None and torch_dtype(fft_dtype) != fdt:
+        raise ValueError("fft_dtype is the precision of x")
+    xr, rr = torch.view_as_real(x.contiguous()), torch.view_as_real(replica.contiguous())
+    off = torch.tensor([0, replica.numel()], dtype=torch.int32, device=x.device)
+    ws = torch.empty(768 + 4 + 3 * _lib.EK80_NFFT + 3 * 1024 + 2 + 1 + 5 + 256, dtype=torch.float64,
+                     device=x.device)  # EPA_EK80_FFT_WS_DOUBLES(1, 1, 1)
+    out = torch.empty_like(xr)
+    call("epa_selftest_correlate", _p(xr), x.shape[0], _p(rr), _p(off), _DT[fdt], _p(out), _p(ws), _stream())
+    return torch.view_as_complex(out)
+
+
 def mvbs_finalize(ssum, cnt, fill_value=float("nan")):
     out = torch.empty_like(ssum)
     call("epa_mvbs_finalize", _p(ssum), _p(cnt), ssum.numel(), float(fill_value), _p(out),

@@ -433,6 +433,14 @@ int epa_sv_complex_fft(const void* re, const void* im, int in_dtype, const float
                        int S, int B, int cal_type, void* out, void* range_out, void* prx_out,
                        int out_dtype, int fft_dtype, double* workspace, double* range_stats_out,
                        epa_stream_t stream);
+/* Self-test hook: the raw complex output of that transform's circular correlation alone.  x, out: n_tiles tiles of
+ * EPA_EK80_NFFT interleaved (re, im) samples of fft_dtype; replica: interleaved f32, replica_off: i32 [2] = {0, taps}
+ * (device), taps <= EPA_EK80_NFFT; out[t][k] = sum_j x[t][(k + j) mod EPA_EK80_NFFT] conj(replica[j]), through the
+ * spectrum the replica preparation of epa_sv_complex_fft builds.  workspace: f64 [EPA_EK80_FFT_WS_DOUBLES(1, 1, 1)].
+ * A test hook: the caller guarantees replica_off[1] - replica_off[0] <= EPA_EK80_NFFT (the offsets live on the
+ * device and are not read back) and an n_tiles the arrays hold; one workgroup per tile. */
+int epa_selftest_correlate(const void* x, int n_tiles, const float* replica, const int32_t* replica_off,
+                           int fft_dtype, void* out, double* workspace, epa_stream_t stream);
 /* ... with one replica per (channel, filter interval), as epa_sv_complex_indexed.  workspace: f64
  * [EPA_EK80_FFT_WS_DOUBLES(max(C, n_replicas), P, S)]. */
 int epa_sv_complex_fft_indexed(const void* re, const void* im, int in_dtype, const float* replica,

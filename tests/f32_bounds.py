@@ -22,6 +22,10 @@ Quantities (kernel lines cited where each bound is derived):
                          ``threshold_`` / ``impulse_`` / ``attenuated_decision_bound`` for the comparisons made on them.
 * ``check_decisions``   a keep/remove or membership decision may differ only where the oracle's margin to the
                          threshold is within the bound of the quantity compared.
+* ``fft_tile_bound`` / ``direct_form_bound`` / ``bb_sample_bound`` / ``splitbeam_angle_bound``  the EK80 broadband
+                         routes: a normwise bound of one tile of the LDS transform's correlation (csrc/lds_fft.h, pass
+                         by pass), the per-sample bound of the direct form's fma chains, from either amplitude bound to
+                         Sv / TS in dB and to linear amplitude, and to the split-beam electrical angles.
 
 ``assert_f32_close`` also asserts the old north-star bar (|got - exp| / max(|exp|, 1) <= 1e-3), so a passing check
 implies the old one at every element.
@@ -404,11 +408,11 @@ def assert_few_near(margin, bound, what="", cap=1e-3):
 
 
 # ------------------------------------------------------------------------------------------------ checks
-def _log(what, err, ratio, shape):
+def _log(what, err, ratio, shape, **extra):
     path = os.environ.get("EPA_F32_BOUNDS_LOG")
     if path:
         with open(path, "a") as f:
-            f.write(json.dumps({"what": what, "max_err": err, "max_ratio": ratio, "shape": list(shape)}) + "\n")
+            f.write(json.dumps({"what": what, "max_err": err, "max_ratio": ratio, "shape": list(shape), **extra}) + "\n")
 
 
 def assert_f32_close(got, exp, bound, what=""):
@@ -455,3 +459,288 @@ def check_decisions(got_keep, exp_keep, margin, bound, what="", max_frac=None):
     if max_frac is not None:
         assert nflip <= max_frac * flip.size, (what, nflip, flip.size)
     return nflip
+
+
+# ------------------------------------------------------------------------------------------------ EK80 broadband
+# The pulse-compressed routes (csrc/lds_fft.h, csrc/ek80_fft.hip, csrc/ek80_complex.hip, csrc/splitbeam.hip).  The
+# oracle is the plain correlation y[k] = sum_j x[k + j] conj(h[j]) in float64 / longdouble of exactly the float32
+# samples and complex64 replica the kernel read.
+NFFT = 2048                       # EPA_EK80_NFFT: the tile of the LDS transform
+ULD = 2.0**-64                    # unit roundoff of the x87 long double the complex128 transform's oracle sums in
+E_SINCOS = 2.0                    # ocml's double sincospi: ulp of its result (the twiddle table, ek80_fft.hip:106)
+
+
+def _cmul_rel(u):
+    """|fl(a b) - a b| <= (2u + u^2) |a b| for the product-then-fma complex product (lds_fft.h:53-55 ``cmul``, :375
+    ``pk::cmul`` = v_pk_mul then v_pk_fma): re = fl(a_r b_r - fl(a_i b_i)), im = fl(a_r b_i + fl(a_i b_r)); the inner
+    products err by u |a_i b_i|, u |a_i b_r| (together u |a_i| |b| in norm), the fma rounds the result once (u |a b|
+    (1 + u))."""
+    return 2 * u + u * u
+
+
+def _twiddle_rel(tau1, u, radix):
+    """Largest relative error of v[q] * w^q over q = 1 .. radix-1 for ``twiddle8`` (lds_fft.h:109-120, :414-423) /
+    ``twiddle4`` (:121-128, :424-429): w1 carries tau1, the powers come from the product tree w2 = w1 w1, w3 = w2 w1,
+    w4 = w2 w2, w5 = w4 w1, w6 = w3 w3, w7 = w4 w3 (depth 1 to 3), each product (1 + tau_a)(1 + tau_b)(1 + cmul) - 1,
+    and the application to v[q] is one more ``cmul``.  A tone can put a tile's whole energy into one register q, so the
+    normwise constant of the step is the largest of them (q = 7: about 21 u for tau1 = u; q = 3 of the first pass's
+    second butterfly: about 18 u)."""
+    cm = _cmul_rel(u)
+
+    def mul(a, b):
+        return (1 + a) * (1 + b) * (1 + cm) - 1
+
+    w = {1: tau1}
+    w[2] = mul(w[1], w[1])
+    w[3] = mul(w[2], w[1])
+    if radix == 8:
+        w[4] = mul(w[2], w[2])
+        w[5] = mul(w[4], w[1])
+        w[6] = mul(w[3], w[3])
+        w[7] = mul(w[4], w[3])
+    return max((1 + w[q]) * (1 + cm) - 1 for q in range(1, radix))
+
+
+def fft_constants(u=U):
+    """The normwise constants of ``correlate<F>`` (lds_fft.h:276-335 for double, :444-523 for float), u = U (complex64)
+    or U64 (complex128): dict(fwd, prod, inv, total), each a relative error in the 2-norm of the tile.
+
+    Every pass is sqrt(r) times a unitary map followed or preceded by a diagonal map of unit-modulus twiddles, so an
+    error e of norm <= eps ||z|| made in one step reaches the output with the same relative norm and the steps compound
+    as prod(1 + eps_i) - 1.
+      complex add / sub (``cadd``, v_pk_add, also with the exact factors -i, +i through op_sel / neg): one rounding per
+          component -> u ||result||.
+      ``dft4`` (:71-77, :378-384): two stages of adds -> (1 + u)^2 - 1.
+      ``dft8`` (:79-91, :393-413): dft4 on evens and odds, then out = e +- rot(o).  The rotations of o1, o3 by
+          e^{-+i pi/4}: float forms q = o -+ i o (one rounding), then fma(q, kh, e) -- kh = fl(1/sqrt 2) (<= u) -- so
+          rot(o) carries rho = (1 + u)^2 - 1 before the fma's own rounding; double multiplies (o_r + o_i) kh first
+          (three roundings: rho = (1 + u)^3 - 1).  ||o|| <= ||out|| / sqrt 2 and an error dt of rot(o) enters two
+          outputs (sqrt 2 ||dt||): stage 3 errs by (1 + u)(1 + rho) - 1 of ||out||.
+          -> dft8 = (1 + u)^3 (1 + rho) - 1  (5 u float, 6 u double); the inverse forms are the same operations.
+      twiddle table (ek80_fft.hip:104-111): double sincospi (E_SINCOS ulp), rounded to F: tau = u + 2 E_SINCOS 2^-53.
+      first pass (``fwd_pass0`` :172-180, :456-462): dft4, then ``twiddle4`` with wa = table entry and
+          wb = kh (wa - i wa): one add, one product, kh -> tau_b = (1 + tau)(1 + u)^3 - 1.
+      inner passes: dft8 then ``twiddle8`` with a table entry (double: the 68-entry table holds every index they use,
+          ``tw_mul4`` :159-162).
+      last pass (``inv_pass0`` :181-190, :514-520): the conjugate twiddles (exact sign flip), then idft4; double takes
+          wa = ``tw_any`` = one ``cmul`` of two table entries (:154-158).
+      spectral product (:310, :490): the spectrum entry (ek80_fft.hip:161-166: double, 1/N folded in exactly, float
+          rounds it once: u per component; the double transform that made it is charged in ``fft_tile_bound``), one
+          ``cmul``.
+    Sum for complex64: forward 2 + 18 + 2 (5 + 21) + 5 = 77 u, product 3 u, inverse the same 77 u: total about 157 u
+    (computed exactly below, with the second-order terms).  Derived, not measured."""
+    double = u < U
+    cm = _cmul_rel(u)
+    dft4 = (1 + u) ** 2 - 1
+    rho = (1 + u) ** 3 - 1 if double else (1 + u) ** 2 - 1
+    dft8 = (1 + u) ** 3 * (1 + rho) - 1
+    tau = u + 2 * E_SINCOS * U64
+    tau_b = (1 + tau) * (1 + u) ** 3 - 1
+    tw4_fwd = max(_twiddle_rel(tau, u, 4), _twiddle_rel(tau_b, u, 4))
+    tau_inv = (1 + tau) ** 2 * (1 + cm) - 1 if double else tau
+    tau_inv_b = (1 + tau_inv) * (1 + u) ** 3 - 1
+    tw4_inv = max(_twiddle_rel(tau_inv, u, 4), _twiddle_rel(tau_inv_b, u, 4))
+    inner = (1 + dft8) * (1 + _twiddle_rel(tau, u, 8)) - 1
+    fwd = (1 + dft4) * (1 + tw4_fwd) * (1 + inner) ** 2 * (1 + dft8) - 1
+    inv = (1 + dft8) * (1 + inner) ** 2 * (1 + tw4_inv) * (1 + dft4) - 1
+    prod = (1 + (0.0 if double else u)) * (1 + cm) - 1
+    return dict(fwd=fwd, prod=prod, inv=inv, total=(1 + fwd) * (1 + prod) * (1 + inv) - 1)
+
+
+def fft_tile_bound(x, h, u=U, u_oracle=U64):
+    """Normwise bound of one ``correlate<F>`` tile (lds_fft.h:276-335, :444-523):
+        || got - y ||_2 <= K ||x||_2 max_k |FFT(h)_k| + (1 + K) sqrt(N) K64 ||x||_2 ||h||_2 (+ the oracle's own sums)
+    for y[k] = sum_j x[(k + j) mod N] conj(h[j]), N = 2048; every sample's error is at most that.
+
+    K = ``fft_constants(u)['total']`` (about 157 u for complex64).  Why ||x||_2 max|H|: with X = FFT(x) (norm sqrt N
+    ||x||), the spectrum H = conj(FFT(h)) / N and y = IFFT_unnormalised(X H) (norm sqrt N ||X H||), a forward error of
+    relative norm eps reaches the product as at most eps ||X|| max|H|, i.e. eps ||x|| max|FFT(h)| in y; the product's
+    and the inverse's errors are relative to ||X H|| <= ||X|| max|H| as well.
+    The spectrum itself comes from the double transform of ``replica_prepare_kernel`` (ek80_fft.hip:135-166: the
+    scalar templates, full twiddle table): || dH ||_2 <= K64 ||H||_2 with K64 = ``fft_constants(U64)['fwd']``; a tone
+    can put all of X into the one bin where dH sits, so that part is bounded by max|X| ||dH|| <= ||X||_2 K64 ||H||_2,
+    which is sqrt(N) K64 ||x||_2 ||h||_2 in y.  (For complex64 it is 1e-13 of the first term.)
+    The oracle's plain sum in precision ``u_oracle``: gamma_{2 taps} (|x| * |h|)[k] <= gamma ||x|| ||h|| per sample.
+    ``x`` (..., 2048) complex: the tile(s) as the transform received them; ``h`` complex replica (<= 2048 taps).
+    Returns the bound per tile, shape x.shape[:-1]."""
+    x = np.asarray(x)
+    h = np.asarray(h).astype(np.complex128)
+    assert x.shape[-1] == NFFT and h.size <= NFFT
+    xn = np.sqrt(np.sum(np.abs(x.astype(np.complex128)) ** 2, axis=-1))
+    hn = float(np.sqrt(np.sum(np.abs(h) ** 2)))
+    hmax = float(np.abs(np.fft.fft(h, NFFT)).max()) * (1 + 64 * U64) + 64 * U64 * hn
+    K = fft_constants(u)["total"]
+    K64 = fft_constants(U64)["fwd"]
+    g_or = 2 * h.size * u_oracle / (1 - 2 * h.size * u_oracle)
+    return K * xn * hmax + np.sqrt(NFFT) * ((1 + K) * K64 + g_or) * xn * hn
+
+
+def direct_form_bound(x, h, u=U, u_oracle=U64):
+    """Per-sample bound of the direct form ``conv8`` (ek80_complex.hip:139-165) on one staged series ``x`` (1-D complex,
+    zero-filled) with the replica ``h``: each component is a chain of 2 taps fused multiply-adds in the accumulation
+    type (:156-159), so
+        |d re[k]| <= gamma_{2 taps} sum_j (|x_r| |h_r| + |x_i| |h_i|)[k + j],   |d im[k]| likewise with (|x_i| |h_r| +
+        |x_r| |h_i|)
+    (zero-padded taps add exact zeros) and the complex error is their hypot.  Local -- relative to the products under
+    the sample's own window, not to the tile's peak.  Returns (S,) for y[k] = sum_j x[k + j] conj(h[j]), k + j < S."""
+    x = np.asarray(x).astype(np.complex128)
+    h = np.asarray(h).astype(np.complex128)
+    n = 2 * h.size
+
+    def g(uu):
+        return n * uu / (1 - n * uu)
+
+    def cor(a, b):
+        return np.convolve(np.concatenate([a, np.zeros(b.size - 1)]), b[::-1], mode="valid")
+
+    xr, xi, hr, hi = np.abs(x.real), np.abs(x.imag), np.abs(h.real), np.abs(h.imag)
+    er = cor(xr, hr) + cor(xi, hi)
+    ei = cor(xi, hr) + cor(xr, hi)
+    return (g(u) + g(u_oracle)) * np.hypot(er, ei)
+
+
+def sector_sum_bound(abs_re_sum, abs_im_sum, B, u=U):
+    """The staged sector sum in F (``sum_plain`` ek80_fft.hip:289-299, ``load_sample`` :192-256, ``stage_tile``
+    ek80_complex.hip:113-124): B - 1 additions in any order -> |d| <= gamma_{B-1} hypot(sum_b |re_b|, sum_b |im_b|)."""
+    m = max(B - 1, 0)
+    return m * u / (1 - m * u) * np.hypot(abs_re_sum, abs_im_sum)
+
+
+def norm_scale_rel(taps, form, u=U):
+    """Relative error of the factor 1 / (||h||^2 n) the amplitude is scaled with, including the product with y.
+      "fft" (ek80_fft.hip:133,142-145,404-406,601-603): ||h||^2 and its reciprocal in double (a sum of taps positive
+          terms: gamma64_{taps + 8}), the product (double) y invn in double, one rounding to T -> u + (taps + 12) 2^-53.
+      "direct" (ek80_complex.hip:196-209, 266, 279-281): ||h||^2 summed in the accumulation type -- per tap a square
+          and an fma (2 roundings), one add per 256-tap round of a lane, six shuffle adds, three adds of the wavefront
+          sums, all terms positive: (1 + u)^(2 + ceil(taps8 / 256) + 9) - 1; then 1 / norm2, / n valid sectors and the
+          product with y: three more roundings (division in HIP is correctly rounded by default)."""
+    if form == "fft":
+        return u + (taps + 12) * U64
+    taps8 = -(-taps // 8) * 8
+    return (1 + u) ** (2 + -(-taps8 // 256) + 9 + 3) - 1
+
+
+def _range_terms_bound(prx, Rt, R, shift, alpha2, const, nspread, U=U):
+    """The dB terms around the received power, as ``cw_complex_bound`` derives them (the epilogues of
+    ek80_complex.hip:283-293 and ek80_fft.hip:605-620 are the CW kernel's): returns (bound without the power's own
+    relative error, sum of |term|).  ``U``: unit roundoff of the output type (float64 output: the table-driven double
+    logarithm, 4e-16 relative, fast_math.h:6, is within E_LOG ulp as well, and the tabulated time-varied gain holds the
+    per-sample form's roundings, ek80_fft.hip:342-365)."""
+    Tp = np.abs(10 * np.log10(prx))
+    drt = U * (np.abs(R) + np.abs(shift) + np.abs(Rt))
+    rel_rt = drt / Rt
+    Ts = np.abs(nspread * np.log10(Rt))
+    b_s = abs(nspread) / LN10 * rel_rt / (1 - rel_rt) + (2 * E_LOG + 1) * U * Ts
+    Ta = np.abs(alpha2 * Rt)
+    b_a = 2 * U * Ta + np.abs(alpha2) * drt
+    Tc = np.abs(const)
+    tot = Tp + Ts + Ta + Tc
+    return (2 * E_LOG + 1) * U * Tp + b_s + b_a + U * Tc + 3 * U * tot, tot
+
+
+def bb_sample_bound(delta, y_abs, scale, eps_scale, pscale, prx, Rt, R, shift, alpha2, const, nspread, u_t=U):
+    """From an amplitude bound ``delta`` of the summed, pulse-compressed sectors y to the float32 Sv / TS and to the
+    linear amplitude sqrt(prx), for either form.  Returns (b_db, b_lin).
+
+      m = y * scale, scale = 1 / (||h||^2 n): |dm| <= d' = scale (delta (1 + eps_scale) + |y| eps_scale)
+          (``norm_scale_rel``: ek80_fft.hip:601-603 ``mr = (T)(y * invn)`` through double; ek80_complex.hip:279-281)
+      prx = fl(pscale) (mr mr + mi mi) (ek80_fft.hip:605, ek80_complex.hip:283): fl(pscale) (u), the sum of squares
+          (two roundings), the product (u):  relative error e_p = (1 + (2 |m| d' + d'^2) / |m|^2)(1 + u)^4 - 1, as
+          ``cw_complex_bound``
+      10 log10f(prx) (``fast_log10_lean<float>`` is log10f: E_LOG), the time-varied gain n log10f(R') + 2 alpha R'
+          per ping (float output never takes the table, ek80_fft.hip:410-411), the additions and the final rounding:
+          ``_range_terms_bound``
+      -> b_db = DB -ln(1 - e_p) + the range terms; infinite where e_p >= 1 (the sample is at the error floor).
+      linear: sqrt(prx_got) = sqrt(pscale) |m_got| sqrt(1 + eta), |eta| <= (1 + u)^4 - 1 = e4:
+          |sqrt(prx_got) - sqrt(prx_exp)| <= sqrt(pscale) (d' + (|m| + d') e4 / 2 (1 + e4)) + sqrt(4 pscale 2^-149)
+          (the last term: a sum of squares in float32's subnormal range is off by up to a few 2^-149 absolutely).
+          It needs no dynamic-range exclusion: it is finite at every sample.
+    delta, y_abs, prx, Rt, R (C, P, S); scale, pscale, shift, alpha2, const broadcast to it.  ``u_t``: unit roundoff of
+    the output type -- 2^-53 for a float32 transform under the float64 epilogue (no subnormal term then; the double
+    logarithm's absolute error near 1, 2e-16, and the oracle's own evaluation go into 64 * 2^-53 (1 + sum |term|))."""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        m = y_abs * scale
+        d = scale * (delta * (1 + eps_scale) + y_abs * eps_scale)
+        e4 = (1 + u_t) ** 4 - 1
+        ep = (1 + (2 * m * d + d * d) / (m * m)) * (1 + e4) - 1
+        rng, tot = _range_terms_bound(prx, Rt, R, shift, alpha2, const, nspread, u_t)
+        b_db = (db_of_rel(ep) + rng) * (1 + 8 * u_t) + (8 if u_t == U else 64) * U64 * (tot + (0 if u_t == U else 1))
+        tiny = np.sqrt(4 * pscale * TINY) if u_t == U else 0.0
+        b_lin = (np.sqrt(pscale) * (d + (m + d) * e4 / 2 * (1 + e4)) + tiny) * (1 + 8 * U64)
+    return b_db, b_lin
+
+
+def assert_amp_close(got_prx, exp_amp, b_lin, what=""):
+    """Every sample in LINEAR received amplitude: |sqrt(prx_got) - exp_amp| <= b_lin wherever ``exp_amp`` is a number
+    (a NaN ``prx_got`` there is the kernels' "prx <= 0 -> NaN": amplitude 0).  Returns (max error, max ratio)."""
+    got_prx, exp_amp = np.asarray(got_prx, np.float64), np.asarray(exp_amp, np.float64)
+    b = np.broadcast_to(np.asarray(b_lin, np.float64), exp_amp.shape)
+    fin = np.isfinite(exp_amp)
+    assert np.all(np.isfinite(b[fin])), f"{what}: a sample without a finite linear bound"
+    with np.errstate(invalid="ignore"):
+        amp = np.sqrt(np.where(np.isnan(got_prx), 0.0, got_prx))
+    err = np.abs(amp[fin] - exp_amp[fin])
+    ratio = err / b[fin]
+    k = int(np.argmax(ratio)) if ratio.size else 0
+    assert ratio.size == 0 or ratio[k] <= 1.0, (f"{what}: amplitude off by {err[k]:.3e} > bound {b[fin][k]:.3e} at "
+                                                f"{np.unravel_index(np.flatnonzero(fin)[k], exp_amp.shape)}")
+    if ratio.size:
+        _log(what, float(err.max()), float(ratio.max()), exp_amp.shape)
+    return (float(err.max()), float(ratio.max())) if ratio.size else (0.0, 0.0)
+
+
+def assert_norm_close(got, exp, bound, what=""):
+    """One transform tile per row: ||got - exp||_2 <= bound and max |got - exp| <= bound.  Returns the largest ratio."""
+    d = np.abs(np.asarray(got).astype(np.clongdouble) - np.asarray(exp).astype(np.clongdouble)).astype(np.float64)
+    l2 = np.sqrt(np.sum(d * d, axis=-1))
+    bound = np.broadcast_to(np.asarray(bound, np.float64), l2.shape)
+    assert np.all(np.isfinite(np.asarray(got).view(np.float64 if np.asarray(got).dtype == np.complex128 else np.float32))), \
+        f"{what}: non-finite output"
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(l2 > 0, l2 / bound, 0.0)
+    k = int(np.argmax(ratio))
+    assert ratio[k] <= 1.0, f"{what}: tile {k}: ||err||_2 {l2[k]:.3e} > bound {bound[k]:.3e}"
+    assert np.all(d.max(axis=-1) <= bound), f"{what}: a sample's error exceeds the tile bound"
+    _log(what, float(l2.max()), float(ratio.max()), np.shape(got))
+    return float(ratio.max())
+
+
+E_ATAN2 = 2.0                     # atan2f / atan2: ulp of the result (HIP's documented accuracy)
+
+
+def phase_bound_deg(a_abs, da, b_abs, db, u_t=U64):
+    """Bound, in degrees, of the angle of a conj(b) computed from a, b known to |da|, |db| (csrc/splitbeam.hip:92-97
+    ``angle_deg`` in the output type T, unit roundoff ``u_t``):
+      the factors: the phase of a moves by at most asin(da / |a|), of b by asin(db / |b|) (infinite once the bound
+          reaches the factor: the sample's phase is then not determined);
+      re = ar br + ai bi, im = ai br - ar bi: two roundings each (a product and an fma, or three operations of which
+          the sum rounds the larger): |d re|, |d im| <= gamma_2 |a| |b| -> asin(sqrt 2 gamma_2);
+      atan2 (E_ATAN2 ulp of a result <= pi), the factor 180 / pi rounded to T (u) and the product (u)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ra, rb = da / a_abs, db / b_abs
+        pa = np.where(ra < 1, np.arcsin(np.minimum(ra, 1.0)), np.inf)
+        pb = np.where(rb < 1, np.arcsin(np.minimum(rb, 1.0)), np.inf)
+    g2 = 2 * u_t / (1 - 2 * u_t)
+    rad = pa + pb + np.arcsin(np.sqrt(2) * g2) + 2 * E_ATAN2 * u_t * np.pi
+    return np.degrees(rad) * (1 + 2 * u_t) + 2 * u_t * 180.0
+
+
+def splitbeam_angle_bound(b0, b1, e_al, e_at, four, sens_al, off_al, sens_at, off_at, u_t=U64):
+    """Bound of the ELECTRICAL angles (theta + offset) sensitivity the split-beam tests compare (splitbeam_ref
+    ``electrical``), from the phase bounds b0, b1 (``phase_bound_deg``) of the two products
+    (``finish``, csrc/splitbeam.hip:100-109; the combination products of ``splitbeam_ref.combinations``):
+      four sectors (type 1): e_al = ang0, e_at = ang1;
+      three sectors: e_al = (ang0 + ang1) / sqrt 3 (an add, fl(sqrt 3) and a division: 3 u), e_at = ang1 - ang0 (u);
+      theta = e / fl(sens) - fl(off) in T: fl(sens) (u), the division (u), fl(off) (u |off|), the subtraction
+          (u |theta|); back in electrical degrees: 2 u |e| + u |off sens| + u |e - off sens|.
+    Returns (b_al, b_at)."""
+    e_al, e_at = np.abs(e_al), np.abs(e_at)
+    if four:
+        ba, bt = b0, b1
+    else:
+        ba = (b0 + b1) / np.sqrt(3.0) + 3 * u_t * e_al
+        bt = b0 + b1 + u_t * e_at
+    osa, ost = np.abs(off_al * sens_al), np.abs(off_at * sens_at)
+    ba = ba + u_t * (3 * e_al + 2 * osa)
+    bt = bt + u_t * (3 * e_at + 2 * ost)
+    return ba * (1 + 8 * u_t) + 64 * U64 * (e_al + osa), bt * (1 + 8 * u_t) + 64 * U64 * (e_at + ost)

@@ -135,3 +135,99 @@ def assert_complex_close(got, want, sens, off, weak, tol=1e-3, beam_types=None):
     assert ok.sum() > 0.5 * (~np.isnan(want)).sum(), "too few well-conditioned samples to compare"
     err = np.abs(d[ok]).max() if ok.any() else 0.0
     assert err <= tol, f"electrical angle differs by {err:.3g} deg (tolerance {tol})"
+
+
+def _kernel_combos(beam_type):
+    """The sector pairs the kernels filter (csrc/splitbeam.hip ``combo_sectors``: plain sums, no factor 1/2 -- a phase
+    does not see it), in ``combinations``' order: list of (u, v) with v = None for a single sector."""
+    if beam_type == 1:
+        return [(2, 3), (0, 1), (0, 3), (1, 2)]
+    if beam_type == 17:
+        return [(2, None), (0, None), (1, None)]
+    return [(2, 3), (0, 3), (1, 3)]
+
+
+def complex_angle_bounds(re, im, beam_types, sa, st, oa, ot, replicas, replica_id=None, form="fft", max_taps=None,
+                         u_f=2.0**-24, u_t=2.0**-53):
+    """The float64 oracle angles of the pulse-compressed route on the float32 samples and the complex64-ROUNDED
+    replicas the kernels read, with the derived per-sample bound of the electrical angles (tests/f32_bounds.py):
+    per combination the amplitude bound of its filtered series -- the float add of its two sectors (u_f |c|) through
+    the exact filter, plus ``fft_tile_bound`` of its 2048-sample tile (form "fft", transform precision u_f) or
+    ``direct_form_bound`` (form "direct", accumulation in the output type, u_t), and the rounding of a wider
+    transform's output to the output type -- then ``phase_bound_deg`` of the two products and ``splitbeam_angle_bound``.  -> (theta, phi, b_al, b_at, weak); ``weak`` is ``complex_angles``'."""
+    import f32_bounds as fb
+
+    reps = [np.asarray(r).astype(np.complex64).astype(np.complex128) for r in replicas]
+    theta, phi, (e_al, e_at), weak = complex_angles(re, im, beam_types, sa, st, oa, ot, reps, replica_id)
+    x = re.astype(np.float64) + 1j * im.astype(np.float64)
+    C, P, S, B = x.shape
+    b_al, b_at = np.full((C, P, S), np.inf), np.full((C, P, S), np.inf)
+    if max_taps is None:
+        max_taps = max(r.size for r in reps)
+    opt = fb.NFFT - max_taps + 1
+
+    def bc(v, c):
+        v = np.asarray(v, float)
+        return v[c] if v.ndim == 1 else v[c][:, None]
+
+    for c in range(C):
+        bt = int(beam_types[c])
+        if bt not in SUPPORTED:
+            continue
+        pairs = _kernel_combos(bt)
+        yabs = np.zeros((len(pairs), P, S))
+        dlt = np.zeros((len(pairs), P, S))
+        for p in range(P):
+            h = reps[c if replica_id is None else int(replica_id[c, p])]
+            habs = np.abs(h)
+            for k, (u, v) in enumerate(pairs):
+                xz = np.where(np.isnan(x[c, p]), 0, x[c, p])
+                ck = xz[:, u] + (xz[:, v] if v is not None else 0)
+                d_add = (u_f if v is not None else 0.0) * np.abs(ck)
+                yabs[k, p] = np.abs(np.convolve(np.concatenate([ck, np.zeros(h.size - 1)]), np.conj(h)[::-1], "valid"))
+                d = np.convolve(np.concatenate([d_add, np.zeros(h.size - 1)]), habs[::-1], "valid")
+                if form == "fft":
+                    nt = -(-S // opt)
+                    tiles = np.zeros((nt, fb.NFFT), np.complex128)
+                    for t in range(nt):
+                        seg = ck[t * opt:t * opt + fb.NFFT]
+                        tiles[t, :seg.size] = seg * (1 + u_f)
+                    tb = fb.fft_tile_bound(tiles, h, u_f)
+                    d = d + np.repeat(tb, opt)[:S]
+                else:
+                    d = d + fb.direct_form_bound(ck * (1 + u_f), h, u_t)
+                if u_t > u_f:   # the transform's output is rounded to the output type before the product (:574)
+                    d = d + u_t * (yabs[k, p] + d)
+                dlt[k, p] = d
+        four = bt == 1
+        b0 = fb.phase_bound_deg(yabs[0], dlt[0], yabs[1], dlt[1], u_t)
+        b1 = fb.phase_bound_deg(yabs[2], dlt[2], yabs[3], dlt[3], u_t) if four else \
+            fb.phase_bound_deg(yabs[0], dlt[0], yabs[2], dlt[2], u_t)
+        b_al[c], b_at[c] = fb.splitbeam_angle_bound(b0, b1, e_al[c], e_at[c], four, bc(sa, c), bc(oa, c), bc(st, c),
+                                                    bc(ot, c), u_t)
+    return theta, phi, b_al, b_at, weak
+
+
+def assert_complex_bound(got, want, sens, off, weak, bound, cap, what=""):
+    """The electrical angle against the oracle's with the derived per-sample ``bound``, ``cap`` (the old flat
+    tolerance) on top of it: |difference| <= min(bound, cap) at every sample ``assert_complex_close`` compares.
+    Returns (largest ratio, share of the compared samples at which the DERIVED bound is the smaller of the two, i.e.
+    governs); the share is logged with the ratio.  For a complex64 transform the derived bound is the tile's normwise
+    bound taken per sample and governs only the strongest few per cent of the samples (the cap judges the rest); for a
+    complex128 transform and for the direct form it governs everywhere."""
+    import f32_bounds as fb
+
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
+    ok = ~np.isnan(want) & ~weak
+    assert ok.sum() > 0.5 * (~np.isnan(want)).sum(), "too few well-conditioned samples to compare"
+    d = np.abs(wrap(electrical(got, sens, off) - electrical(want, sens, off)))[ok]
+    tol = np.minimum(bound[ok], cap)
+    ratio = d / tol
+    k = int(np.argmax(ratio))
+    assert ratio[k] <= 1.0, f"{what}: electrical angle differs by {d[k]:.3g} deg (bound {bound[ok][k]:.3g}, cap {cap})"
+    gov = bound[ok] <= cap
+    fb._log(f"{what}: electrical angle", float(d.max()), float(ratio.max()), want.shape, governed=float(gov.mean()),
+            max_ratio_where_governed=float(ratio[gov].max()) if gov.any() else 0.0,
+            bound_median_deg=float(np.median(bound[ok])))
+    return float(ratio.max()), float(gov.mean())

@@ -215,6 +215,16 @@ def _bb_oracle_window(bb, p0, w):
     return exp, prx
 
 
+def _bb_inputs(bb, p0, w):
+    """What the derived float32 judgement of tests/bb_tolerance.py needs of a window: the planes, the complex64
+    replicas the kernel read, the coefficient rows and the form ``ops.sv_complex`` chose."""
+    lens = [r.size for r in bb["reps"]]
+    rep = np.concatenate(bb["reps"]).astype(np.complex64)
+    fft = bb["ops"].sv_complex_uses_fft(bb["repf"], max(lens))
+    return dict(re=bb["re"][:, p0:p0 + w].cpu().numpy(), im=bb["im"][:, p0:p0 + w].cpu().numpy(), rep=rep, lens=lens,
+                cc=bb["cc"][:, p0:p0 + w], form="fft" if fft else "direct")
+
+
 def test_bb_float64_planes_volume_windows_match_the_oracle():
     """backscatter_r / _i as the converter stores them -- float64 (convert/parse_base.py:306-309) -- at 2 x 50 000 x
     8192 x 4 (52 GB of planes, a quarter of configs[3]'s ping count: the full volume is 210 GB and would not fit next to
@@ -226,7 +236,7 @@ def test_bb_float64_planes_volume_windows_match_the_oracle():
         for p0 in (0, 31_313, 49_990):
             exp, prx = _bb_oracle_window(d, p0, 10)
             assert_bb_close(d["f64"][:, p0:p0 + 10].cpu().numpy(), exp, "float64", prx=prx)
-            assert_bb_close(d["f32"][:, p0:p0 + 10].cpu().numpy(), exp, "float32", prx=prx)
+            assert_bb_close(d["f32"][:, p0:p0 + 10].cpu().numpy(), exp, "float32", prx=prx, inputs=_bb_inputs(d, p0, 10))
     finally:
         d.clear()
         gc.collect()
@@ -241,7 +251,7 @@ def test_bb_windows_match_the_scipy_convolve_oracle(bb, p0):
     w = 10
     exp, prx = _bb_oracle_window(bb, p0, w)
     assert_bb_close(bb["f64"][:, p0:p0 + w].cpu().numpy(), exp, "float64", prx=prx)
-    assert_bb_close(bb["f32"][:, p0:p0 + w].cpu().numpy(), exp, "float32", prx=prx)
+    assert_bb_close(bb["f32"][:, p0:p0 + w].cpu().numpy(), exp, "float32", prx=prx, inputs=_bb_inputs(bb, p0, w))
 
 
 # ---- configs[4]'s range depth: the fused kernel with 4096 samples and 787 range bins ---------------------------------

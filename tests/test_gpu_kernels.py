@@ -585,28 +585,15 @@ def test_sv_complex_fft_path_matches_direct(env, in_dtype, out_dtype, fft_dtype,
     for mixed NaN patterns, NaN tails, two channels with different replica lengths; complex64 and complex128
     transforms (default: the output's precision)."""
     torch, ops, synth = env
-    rng = np.random.default_rng(taps + S)
-    C, P = 2, 5
-    amp = 10.0 ** rng.uniform(-7, 0, (C, P, S, 1))
-    re = (amp * rng.standard_normal((C, P, S, B))).astype(in_dtype)
-    im = (amp * rng.standard_normal((C, P, S, B))).astype(in_dtype)
-    re[:, :, S - 37:], im[:, :, S - 37:] = np.nan, np.nan  # end-of-ping padding
-    re[1, 1], im[1, 1] = np.nan, np.nan                    # a whole missing ping
-    if mixed:
-        re[0, 0, 100:130, B - 1] = np.nan                  # one sector missing -> per-sector fallback
-        im[0, 2, S // 2, 0] = np.nan
-        re[1, 0, 200:203, 0] = np.nan                      # beam 0 missing: masked echo_range, Sv NaN (B > 1: others valid)
-    lens = [taps, max(taps // 2, 1)]
-    rep = np.concatenate([(rng.standard_normal(n) + 1j * rng.standard_normal(n)) * np.hanning(n + 2)[1:-1]
-                          for n in lens]).astype(np.complex64)
+    import bb_ref
+
+    # (the inputs live in tests/bb_ref.py, which also holds their float64 oracle: echoes over 140 dB, end-of-ping NaN
+    # padding, a whole missing ping, partly-NaN sectors -> per-sector fallback, a missing beam 0, two replica lengths,
+    # a ping that leaves the time-varied-gain table, per-ping gain / power terms)
+    re, im, rep, lens, cc = bb_ref.fft_path_case(taps, S, mixed, B)
+    re, im = re.astype(in_dtype), im.astype(in_dtype)
     repf = _dev(torch, np.stack([rep.real, rep.imag], axis=1).astype(np.float32).reshape(-1))
     off = _dev(torch, np.array([0, lens[0], lens[0] + lens[1]], dtype=np.int32))
-    cc = np.zeros((C, P, 8))
-    cc[..., 0], cc[..., 1], cc[..., 2], cc[..., 3], cc[..., 4], cc[..., 5] = 2.6e-5, 750.0, 0.2, 0.02, -30.0, 1e3
-    # a ping with its own sound speed / absorption: it leaves the per-channel time-varied-gain table (and its
-    # neighbours in a tile do not)
-    cc[0, 2, 1], cc[1, 2, 3] = 751.5, 0.021
-    cc[:, 3, 4], cc[:, 4, 5] = -31.5, 1.1e3                 # per-ping gain / power terms
     kw = dict(replica=repf, replica_off=off, max_taps=taps, dtype=getattr(torch, out_dtype), want_prx=True)
     args = (_dev(torch, re), _dev(torch, im), _dev(torch, cc))
     d = ops.sv_complex(*args, method="direct", **kw)
@@ -647,6 +634,27 @@ def test_sv_complex_fft_path_matches_direct(env, in_dtype, out_dtype, fft_dtype,
         strong = pd > peak * (1e-4 if fft32 else 1e-10)
     tol = 1e-6 if not f32 else 2e-3
     assert np.nanmax(np.abs(sf[strong] - sd[strong])) < tol  # NaN where R' <= 0 (both paths alike)
+    if out_dtype == "float64" and fft_dtype == "float32":
+        # the complex64 transform under the float64 epilogue, on its own against the oracle: the tile bound with
+        # u = 2^-24, the sector mean, received power, logarithms and gain terms with u = 2^-53
+        case = bb_ref.sv_case("path", taps, S, mixed, B)
+        case = dict(case, fft=bb_ref.sample_bounds(case["o"], "fft", taps, fb.U, fb.U64))
+        bb_ref.judge_sv(sf, pf, case, "fft", f"fft==direct rows {in_dtype}->{out_dtype} fft={fft_dtype} taps={taps} "
+                                             f"S={S} fft(complex64, float64 epilogue)")
+    if out_dtype == "float32":
+        # ... and each form on its own against the float64 oracle of the float32 values it computed with, within the
+        # derived bounds of tests/f32_bounds.py: every sample in linear amplitude, the dB value wherever its bound is
+        # finite.  (The float64 -> float32 row feeds float64 planes that are NOT float32 numbers: both kernels round
+        # every sector value to float on load -- ``(A)vr`` in stage_tile, ``(F)raw`` in sum_plain -- and the oracle
+        # starts from those rounded values, so input rounding is not charged.)
+        case = bb_ref.sv_case("path", taps, S, mixed, B)
+        what = f"fft==direct rows {in_dtype}->{out_dtype} fft={fft_dtype} taps={taps} S={S}"
+        bb_ref.judge_sv(sd, pd, case, "direct", what + " direct")
+        if fft32:
+            bb_ref.judge_sv(sf, pf, case, "fft", what + " fft")
+        else:  # a complex128 transform under the float32 epilogue: the same derivation with u = 2^-53
+            case64 = dict(case, fft=bb_ref.sample_bounds(case["o"], "fft", taps, fb.U64))
+            bb_ref.judge_sv(sf, pf, case64, "fft", what + " fft(complex128)")
 
 
 @pytest.mark.parametrize("in_dtype", ["float32", "float64"])
