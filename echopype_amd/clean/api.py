@@ -15,8 +15,9 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..commongrid.api import _coef_rows, _dev, _full, _range_stats
+from ..commongrid.api import _coef_rows, _range_stats
 from ..commongrid.utils import _parse_x_bin
+from ..device_view import as_tensor, broadcast_to_dims, device_view
 from ..utils.prov import echopype_prov_attrs, insert_processing_level
 from ..xr_lite import DataArray, DeviceArray, LazyDeviceArray, from_xarray, xarray_io
 from .transient_noise import transient_noise_fielding, transient_noise_matecho
@@ -26,7 +27,7 @@ from .utils import add_remove_background_noise_attrs, extract_dB
 def _inputs(ds_Sv):
     sv_da = ds_Sv["Sv"]
     order = tuple(sv_da.dims)
-    sv_t = _dev(sv_da)
+    sv_t = as_tensor(sv_da)
     if sv_t.dtype not in (torch.float32, torch.float64):
         sv_t = sv_t.double()
     # a lazy echo_range straight from compute_Sv on power samples: the kernels evaluate its coefficient rows and take the
@@ -36,7 +37,7 @@ def _inputs(ds_Sv):
     if raw is not None and raw.dtype == torch.float32 and tuple(raw.shape) == tuple(sv_t.shape) and raw.is_contiguous():
         rg_t = (rows, raw)
     else:
-        rg_t = _dev(_full(ds_Sv["echo_range"], ds_Sv, order), sv_t.dtype)
+        rg_t = as_tensor(broadcast_to_dims(ds_Sv["echo_range"], ds_Sv, order), sv_t.dtype)
     C, P, S = sv_t.shape
     return order, sv_t, rg_t, _alpha2(ds_Sv, order, C, P)
 
@@ -285,21 +286,16 @@ logger = logging.getLogger("echopype_amd.clean")
 _CPS = ("channel", "ping_time", "range_sample")
 
 
-def _cube(da, ds, dtype=None):
+def _cube(da, ds, dtype=None, floating=False):
     """Device tensor of a variable in (channel, ping_time, range_sample) order (the reference
     transposes to it, clean/utils.py:125-127), broadcast if lower-dimensional."""
     if set(da.dims) != set(_CPS):
-        da = _full(da, ds, _CPS)
-    t = _dev(da, dtype)
-    if tuple(da.dims) != _CPS:
-        t = t.permute([da.dims.index(d) for d in _CPS])
-    return t.contiguous()
+        da = broadcast_to_dims(da, ds, _CPS)
+    return device_view(da, _CPS, dtype=dtype, floating=floating)
 
 
 def _mask_inputs(ds_Sv, range_var, need_range):
-    sv_t = _cube(ds_Sv["Sv"], ds_Sv)
-    if sv_t.dtype not in (torch.float32, torch.float64):
-        sv_t = sv_t.double()
+    sv_t = _cube(ds_Sv["Sv"], ds_Sv, floating=True)
     rg_t = _cube(ds_Sv[range_var], ds_Sv, sv_t.dtype) if need_range else None
     return sv_t, rg_t
 

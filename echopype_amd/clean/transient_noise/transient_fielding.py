@@ -7,7 +7,7 @@ import torch
 
 from ... import ops
 from ...xr_lite import xarray_io
-from .utils import _cube, _mask_array, _range_rows
+from .utils import _channel_cube, _mask_array, _range_rows
 
 
 def _layer_rows(r, r0, r1, roff, jumps):
@@ -66,7 +66,7 @@ def transient_noise_fielding(ds_Sv, var_name="Sv", range_var="depth", r0=900, r1
     if start > 0:
         raise NotImplementedError("start > 0 is not supported: the reference pads the mask to the wrong shape and fails "
                                   "(ValueError from np.vstack, or a result of P + start pings)")
-    sv = _cube(var, var_name, device)
+    sv = _channel_cube(var, var_name, device)
     C, P, S = sv.shape
     if P == 0 or S == 0:
         return _mask_array(var, torch.ones((C, P, S), dtype=torch.bool, device=sv.device), "fielding_mask_valid")

@@ -4,9 +4,9 @@ import numpy as np
 import torch
 
 from ... import ops
-from ...commongrid.api import _dev
+from ...device_view import device_view
 from ...xr_lite import xarray_io
-from .utils import _cube, _mask_array, _range_rows
+from .utils import _channel_cube, _mask_array, _range_rows
 
 
 def _window_rows(r, start_depth, window_meter, range_var):
@@ -73,7 +73,7 @@ def transient_noise_matecho(ds, var_name="Sv", range_var="depth", time_var="ping
         raise ValueError(f"Dimensions {{{time_var!r}}} do not exist. Expected one or more of {tuple(r_da.dims)}")
     if not 0 <= percentile <= 100:
         raise ValueError("Percentiles must be in the range [0, 100]")
-    sv = _cube(var, var_name, device)
+    sv = _channel_cube(var, var_name, device)
     C, P, S = sv.shape
     if P == 0 or S == 0:
         return _mask_array(var, torch.ones((C, P, S), dtype=torch.bool, device=sv.device), "matecho_mask_valid")
@@ -92,12 +92,7 @@ def transient_noise_matecho(ds, var_name="Sv", range_var="depth", time_var="ping
         if tuple(b_da.dims) not in (("ping_time",), ("channel", "ping_time"), ("ping_time", "channel")):
             raise NotImplementedError(f"bottom_var={bottom_var!r} must have dims (ping_time) or (channel, ping_time), got "
                                       f"{tuple(b_da.dims)}")
-        bottom = _dev(b_da, torch.float64)
-        if bottom.device != sv.device:
-            bottom = bottom.to(sv.device)
-        if tuple(b_da.dims) == ("ping_time", "channel"):
-            bottom = bottom.T
-        bottom = bottom.contiguous()
+        bottom = device_view(b_da, ("channel", "ping_time"), device=sv.device, dtype=torch.float64)
     mask = ops.transient_matecho(sv, rows, chan_i, chan_d, bottom, int(window_ping // 2), percentile, delta_db,
                                  max(int(extend_ping), 0), min_window)
     return _mask_array(var, mask, "matecho_mask_valid")

@@ -1,9 +1,9 @@
 """What the two transient-noise detectors share: the (channel, ping_time, range_sample) device cube of the selected
 variable, the range rows on the host (the one device-to-host copy of a call), and the result container."""
 import numpy as np
-import torch
 
 from ... import ops
+from ...device_view import device_view
 from ...xr_lite import DataArray, DeviceArray
 
 _CPS = ("channel", "ping_time", "range_sample")
@@ -17,35 +17,15 @@ def _to_host(t):
     return ops.fetch_async(t).cpu()
 
 
-def _device(device):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _cube(var, var_name, device):
+def _channel_cube(var, var_name, device):
     """``var`` as a contiguous (C, P, S) float32 / float64 device tensor; a variable without a channel dimension is
     one channel.  Device arrays are read where they are, host arrays uploaded."""
     dims = list(var.dims)
     if not {"ping_time", "range_sample"}.issubset(dims) or not set(dims).issubset(_CPS):
         raise NotImplementedError(f"{var_name!r} must have dims (channel, ping_time, range_sample) in some order, "
                                   f"got {tuple(dims)}")
-    perm = [dims.index(d) for d in _CPS if d in dims]
-    dev = _device(device)
-    d = var.data
-    if isinstance(d, DeviceArray):
-        t = d.tensor
-        if t.device != dev:
-            t = t.to(dev)
-        t = t.permute(*perm)
-        if t.dtype not in (torch.float32, torch.float64):
-            t = t.double()
-    else:
-        a = np.asarray(d).transpose(perm)
-        if a.dtype not in (np.float32, np.float64):
-            a = a.astype(np.float64)
-        t = ops.to_device(np.ascontiguousarray(a), device=dev)
-    if "channel" not in dims:
-        t = t[None]
-    return t.contiguous()
+    t = device_view(var, _CPS, device=device, floating=True)
+    return t if "channel" in dims else t[None]
 
 
 def _range_rows(r_da, range_var, ping_dim, C, S):

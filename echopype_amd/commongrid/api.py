@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
+from ..device_view import as_tensor, broadcast_to_dims
 from ..utils.prov import echopype_prov_attrs, insert_processing_level
 from ..xr_lite import (DataArray, Dataset, DeferredDataset, DeviceArray, LazyDeviceArray, defer_mvbs_enabled, from_xarray,
                        xarray_io)
@@ -23,14 +24,6 @@ _TORCH_DT = {"float64": torch.float64, "float32": torch.float32}
 _AGG_MSG = ("Aggregation may be negatively impacted since Flox will not aggregate any "
             "```Sv``` values that have corresponding NaN coordinate values. Consider handling "
             "these values before calling your intended commongrid function.")
-
-
-def _dev(a, dtype=None):
-    data = a.data if isinstance(a, DataArray) else a
-    if isinstance(data, DeviceArray):
-        t = data.tensor
-        return t if dtype is None or t.dtype == dtype else t.to(dtype)
-    return ops.to_device(np.asarray(data), dtype=dtype)
 
 
 def _range_stats(da, t):
@@ -57,17 +50,6 @@ def _coef_rows(da, order, sv_t):
     if d.shape != tuple(sv_t.shape) or _TORCH_DT.get(d.dtype.name) != sv_t.dtype:
         return None
     return d.coef_rows()
-
-
-def _full(da, ds, order):
-    """Broadcast a variable to the (dim_0, ping_time, range_sample) cube if it is lower-dimensional."""
-    if tuple(da.dims) == tuple(order):
-        return da
-    a = np.asarray(da.values)
-    shape = [ds.sizes[d] for d in order]
-    idx = [slice(None) if d in da.dims else None for d in order]
-    src = np.transpose(a, [da.dims.index(d) for d in order if d in da.dims])
-    return DataArray(np.ascontiguousarray(np.broadcast_to(src[tuple(idx)], shape)), order)
 
 
 @xarray_io()
@@ -138,12 +120,12 @@ def _mvbs_plain(ds_Sv, range_var, range_bin_m, ping_time_bin, skipna, fill_value
     sv_da = ds_Sv["Sv"]
     order = tuple(sv_da.dims)
     dim_0 = order[0]
-    sv_t = _dev(sv_da)
+    sv_t = as_tensor(sv_da)
     if sv_t.dtype not in (torch.float32, torch.float64):
         sv_t = sv_t.double()
     # (a lazy echo_range straight from compute_Sv: binned through its coefficient rows, never written)
     rows = _coef_rows(ds_Sv[range_var], order, sv_t) if skipna else None
-    rg_t = _dev(_full(ds_Sv[range_var], ds_Sv, order), sv_t.dtype) if rows is None else None
+    rg_t = as_tensor(broadcast_to_dims(ds_Sv[range_var], ds_Sv, order), sv_t.dtype) if rows is None else None
     C, P, S = sv_t.shape
 
     if _shard is None and rows is not None and allow_defer and defer_mvbs_enabled():
@@ -546,10 +528,10 @@ def compute_MVBS_index_binning(ds_Sv, range_sample_num=100, ping_num=100):
     ds_Sv = from_xarray(ds_Sv)
     sv_da = ds_Sv["Sv"]
     order = tuple(sv_da.dims)
-    sv_t = _dev(sv_da)
+    sv_t = as_tensor(sv_da)
     if sv_t.dtype not in (torch.float32, torch.float64):
         sv_t = sv_t.double()
-    rg_t = _dev(_full(ds_Sv["echo_range"], ds_Sv, order), sv_t.dtype)
+    rg_t = as_tensor(broadcast_to_dims(ds_Sv["echo_range"], ds_Sv, order), sv_t.dtype)
     mv, rmin = ops.mvbs_index(sv_t, ping_num, range_sample_num, range=rg_t)
     C, Pb, Sb = mv.shape
     ping_time = np.asarray(ds_Sv["ping_time"].values)
@@ -600,10 +582,10 @@ def compute_NASC(ds_Sv, range_bin="10m", dist_bin="0.5nmi", method="map-reduce",
     sv_da = ds_Sv["Sv"]
     order = tuple(sv_da.dims)
     dim_0 = order[0]
-    sv_t = _dev(sv_da)
+    sv_t = as_tensor(sv_da)
     if sv_t.dtype not in (torch.float32, torch.float64):
         sv_t = sv_t.double()
-    dp_t = _dev(_full(ds_Sv[range_var], ds_Sv, order), sv_t.dtype)
+    dp_t = as_tensor(broadcast_to_dims(ds_Sv[range_var], ds_Sv, order), sv_t.dtype)
     C, P, S = sv_t.shape
 
     lo, hi, _ = _range_stats(ds_Sv[range_var], dp_t)

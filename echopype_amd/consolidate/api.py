@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..commongrid.api import _dev, _full
+from ..device_view import as_tensor, broadcast_to_dims
 from ..xr_lite import DataArray, DeviceArray, LazyDeviceArray, from_xarray, xarray_io
 from .ek_depth_utils import (align_to_ping_time, ek_use_beam_angles, ek_use_platform_angles,
                              ek_use_platform_vertical_offsets)
@@ -105,7 +105,7 @@ def add_depth(ds, echodata=None, depth_offset=None, tilt=None, downward=True,
         er_t, C = None, lazy.shape[0]
     else:
         rows = raw = None
-        er_t = _dev(_full(er, ds, order))
+        er_t = as_tensor(broadcast_to_dims(er, ds, order))
         if er_t.dtype not in (torch.float32, torch.float64):
             er_t = er_t.double()
         C = er_t.shape[0]

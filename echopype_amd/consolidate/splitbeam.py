@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..device_view import device_view, resolve_device
 from ..calibrate.calibrate_ek import retrieve_correct_beam_group
 from ..calibrate.ek80_complex import get_filter_coeff, get_transmit_signal
 from ..echodata import EchoData, as_lite_echodata
@@ -43,31 +44,14 @@ def _channel_index(ds_beam, channels):
     return [have.index(c) for c in want]
 
 
-def _samples(da, idx, device, dtype=None):
+def _samples(da, idx, device):
     """A beam-group variable as a device tensor, channels picked by ``idx`` (read where it lives after to_device())."""
-    d = da.data
-    if isinstance(d, DeviceArray):
-        t = d.tensor
-        if t.device != device:
-            t = t.to(device)
-        if idx is not None:
-            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
-        return t.contiguous() if dtype is None else t.to(dtype).contiguous()
-    a = np.asarray(d)
-    if idx is not None:
-        a = a[idx]
-    return ops.to_device(a, dtype=dtype, device=device)
+    return device_view(da, _DIMS + ("beam",), device=device, index=idx)
 
 
 def _param(da, device):
     """An angle parameter of source_Sv (scalar, (channel,) or (channel, ping_time)) as an f64 device tensor."""
-    d = da.data
-    if isinstance(d, DeviceArray):
-        return d.tensor.to(device=device, dtype=torch.float64).contiguous()
-    a = np.asarray(d, dtype=np.float64)
-    if tuple(da.dims) == ("ping_time", "channel"):
-        a = a.T
-    return ops.to_device(np.ascontiguousarray(a), device=device)
+    return device_view(da, ("channel", "ping_time"), device=device, dtype=torch.float64)
 
 
 def _complex_beam_types(ds_beam):
@@ -158,7 +142,7 @@ def add_splitbeam_angle(source_Sv, echodata, waveform_mode, encode_mode, pulse_c
     else:
         bt = _complex_beam_types(ds_beam)
 
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(device)
     out_dt = ops.torch_dtype(dtype) if dtype is not None else torch.float64
     prm = [_param(params[n], dev) for n in ops.SPLITBEAM_PARAMS]
     if power:

@@ -7,9 +7,9 @@ import torch
 
 from ... import ops
 from ...xr_lite import DataArray, DeviceArray, xarray_io
+from ...device_view import channel_position
 from . import utils
-from .utils import _check_inputs, _parse_blackwell_thresholds, _plane
-
+from .utils import _channel_plane, _check_inputs, _parse_blackwell_thresholds
 
 
 def _log2lin(data):
@@ -68,9 +68,9 @@ def bottom_blackwell(ds, var_name, channel, threshold=-75, offset=0.3, r0=0, r1=
 
     tSv, ttheta, tphi = _parse_blackwell_thresholds(threshold)
 
-    ci = [str(c) for c in np.asarray(ds["channel"].values).reshape(-1)].index(str(channel))
-    theta = _plane(ds["angle_alongship"], ci, sv.device, "angle_alongship")
-    phi = _plane(ds["angle_athwartship"], ci, sv.device, "angle_athwartship")
+    ci = channel_position(ds["channel"].values, channel)
+    theta = _channel_plane(ds["angle_alongship"], ci, sv.device, "angle_alongship")
+    phi = _channel_plane(ds["angle_athwartship"], ci, sv.device, "angle_athwartship")
     if theta.dtype != phi.dtype:
         theta, phi = theta.double(), phi.double()
     P, S = sv.shape

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from ... import ops
-from ...xr_lite import DeviceArray
+from ...device_view import channel_position, device_view, resolve_device
 
 _DIMS = ("channel", "ping_time", "range_sample")
 
@@ -20,36 +20,12 @@ def _to_host(t):
     return t.cpu()
 
 
-def _channel_index(ds, channel):
-    chans = [str(c) for c in np.asarray(ds["channel"].values).reshape(-1)]
-    if str(channel) not in chans:
-        raise KeyError(channel)
-    return chans.index(str(channel))
-
-
-def _device(device):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _plane(da, ci, dev, name):
+def _channel_plane(da, ci, dev, name):
     """One channel of a (channel, ping_time, range_sample) variable as a contiguous (P, S) float32 / float64 device
     tensor: device arrays are sliced where they are (a lazy array is materialised), host arrays uploaded."""
     if set(da.dims) != set(_DIMS) or len(da.dims) != 3:
         raise ValueError(f"{name!r} must have the dimensions {_DIMS}, got {tuple(da.dims)}")
-    perm = [list(da.dims).index(d) for d in _DIMS]
-    d = da.data
-    if isinstance(d, DeviceArray):
-        t = d.tensor
-        if t.device != dev:
-            t = t.to(dev)
-        t = t.permute(*perm)[ci]
-        if t.dtype not in (torch.float32, torch.float64):
-            t = t.double()
-        return t.contiguous()
-    a = np.asarray(d).transpose(perm)[ci]
-    if a.dtype not in (np.float32, np.float64):
-        a = a.astype(np.float64)
-    return ops.to_device(np.ascontiguousarray(a), device=dev)
+    return device_view(da, _DIMS, device=dev, index=ci, floating=True)
 
 
 def _check_inputs(ds, var_name, channel, required_vars=None, device=None):
@@ -67,10 +43,10 @@ def _check_inputs(ds, var_name, channel, required_vars=None, device=None):
         if var not in ds:
             raise KeyError(f"Required variable {var!r} not found in dataset")
 
-    ci = _channel_index(ds, channel)
-    dev = _device(device)
-    sv = _plane(ds[var_name], ci, dev, var_name)
-    depth = _plane(ds["depth"], ci, dev, "depth")
+    ci = channel_position(ds["channel"].values, channel)
+    dev = resolve_device(device)
+    sv = _channel_plane(ds[var_name], ci, dev, var_name)
+    depth = _channel_plane(ds["depth"], ci, dev, "depth")
     if depth.shape[0] == 0:
         raise IndexError("index 0 is out of bounds for axis 0 with size 0")
     bad = ops.seafloor_depth_uniform(depth)

@@ -4,7 +4,7 @@ import numpy as np
 
 from ... import ops
 from ...xr_lite import xarray_io
-from .utils import _check_state, _mask_array, _plane
+from .utils import _channel_plane, _check_state, _mask_array
 
 
 def _axis(a, name, need):
@@ -52,7 +52,7 @@ def shoal_echoview(ds, var_name, channel, idim, jdim, thr=-70.0, mincan=(3.0, 10
         raise ValueError("Please specify channel for multi-channel data")
     if np.isnan(idim).any() or np.isnan(jdim).any():
         raise ValueError("idim and jdim must not contain NaN")
-    sv = _plane(var, channel, device, var_name)
+    sv = _channel_plane(var, channel, device, var_name)
 
     P, S = sv.shape
     if P == 0 or S == 0:

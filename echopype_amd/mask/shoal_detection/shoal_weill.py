@@ -2,7 +2,7 @@
 "MOVIES-B -- an acoustic detection description software. Application to shoal species' classification")."""
 from ... import ops
 from ...xr_lite import xarray_io
-from .utils import _check_state, _mask_array, _plane
+from .utils import _channel_plane, _check_state, _mask_array
 
 
 @xarray_io()
@@ -34,7 +34,7 @@ def shoal_weill(ds, var_name, channel=None, thr=-70.0, maxvgap=5, maxhgap=0, min
     rest = [d for d in var.dims if d != "channel"]
     if not {"ping_time", "range_sample"}.issubset(set(rest)):
         raise ValueError(f"'{var_name}' must have dims including 'ping_time' and 'range_sample', got {tuple(rest)}")
-    sv = _plane(var, channel, device, var_name)
+    sv = _channel_plane(var, channel, device, var_name)
 
     P, S = sv.shape
     if P == 0 or S == 0:
