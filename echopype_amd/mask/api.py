@@ -6,6 +6,7 @@ Masks and sources given as file paths are out of scope (no zarr / netCDF IO in t
 """
 import datetime
 import pathlib
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -227,3 +228,227 @@ def detect_shoal(ds, method, params):
     if method not in METHODS_SHOAL:
         raise ValueError(f"Unsupported shoal detection method: {method}")
     return METHODS_SHOAL[method](ds, **params)
+
+
+# ---- frequency differencing (reference: mask/api.py:467-675) ---------------------------------------------------------
+from .freq_diff import _check_freq_diff_source_Sv, _parse_freq_diff_eq  # noqa: E402
+
+
+@xarray_io()
+def frequency_differencing(source_Sv, storage_options={}, freqABEq=None, chanABEq=None):
+    """Boolean mask ``Sv[chanA] - Sv[chanB] operator diff`` ("frequency differencing", "dB differencing").
+
+    The criterion is one string: ``freqABEq`` such as ``"38.0kHz - 120 kHz >= 10.0dB"`` (frequencies with the prefixes
+    "", k, M, G, matched against ``frequency_nominal`` by exact equality) or ``chanABEq`` such as
+    ``'"chan1" - "chan2" < 5dB'`` (channel names in double quotes); the operators are ``> < <= >= ==``.  Exactly one
+    of the two is given.  ``source_Sv`` holds ``Sv`` with a ``channel`` dimension in any position, the coordinate
+    ``channel`` and the variable ``frequency_nominal``; a file path raises ``NotImplementedError``
+    (``storage_options`` is unused), and sharded datasets are not supported.
+
+    The rule is NumPy's for an array and a Python scalar: the difference is rounded in the type of ``Sv`` and ``diff``
+    is converted to that type before the comparison (float32 data is compared in float32; anything but float32 /
+    float64 is converted to float64 first).  NaN in either channel, and inf - inf, give False for every operator.
+
+    Returns the DataArray ``mask`` over the dimensions of ``Sv`` without ``channel``, with the coordinates of ``Sv``
+    that do not carry ``channel`` and the reference's attributes ``mask_type`` and ``history``.  Its data stays on the
+    device (a ``torch.bool`` tensor) and goes straight into ``mask.apply_mask``.
+
+    Device work: one streaming pass over the two selected planes (16-byte loads, four mask bytes per store); a device
+    array with ``channel`` first is read where it lies, otherwise the two planes are gathered (device) or uploaded
+    (host) first.  Host synchronisations: none."""
+    freqAB, chanAB, operator, diff = _parse_freq_diff_eq(freqABEq, chanABEq)
+    _no_paths(source_Sv, "source_Sv")
+    source_Sv = from_xarray(source_Sv)
+    _check_freq_diff_source_Sv(source_Sv, freqAB, chanAB)
+
+    channels = [str(c) for c in source_Sv["channel"].values]
+    if freqAB is not None:
+        freqs = np.asarray(source_Sv["frequency_nominal"].values)
+        pos = [int(np.flatnonzero(freqs == f)[0]) for f in freqAB]
+    else:
+        pos = [channels.index(c) for c in chanAB]
+    chanA, chanB = channels[pos[0]], channels[pos[1]]
+
+    sv_da = source_Sv["Sv"]
+    rest = tuple(d for d in sv_da.dims if d != "channel")
+    in_place = (is_device(sv_da.data) and sv_da.dims[0] == "channel" and sv_da.data.tensor.is_contiguous()
+                and sv_da.data.tensor.dtype in (torch.float32, torch.float64))
+    if in_place:
+        sv_t, a, b = sv_da.data.tensor, pos[0], pos[1]
+        if sv_t.device != torch.device("cuda", torch.cuda.current_device()):
+            sv_t = sv_t.to(torch.device("cuda", torch.cuda.current_device()))
+    else:  # the two planes alone are gathered / uploaded and converted
+        sv_t, a, b = device_view(sv_da, ("channel",) + rest, index=pos, floating=True), 0, 1
+    plane = ops.freq_diff_mask(sv_t, a, b, operator, diff)
+
+    return DataArray(
+        DeviceArray(plane), rest,
+        coords={k: v for k, v in sv_da.coords.items() if k != "channel"},
+        name="mask",
+        attrs={
+            "mask_type": "frequency differencing",
+            "history": f"{datetime.datetime.now(datetime.timezone.utc)}. `depth` calculated using:. "
+                       "Mask created by mask.frequency_differencing. "
+                       f"Operation: Sv['{chanA}'] - Sv['{chanB}'] {operator} {diff}",
+        })
+
+
+# ---- a mask on the MVBS grid (reference: mask/api.py:678-863) ----------------------------------------------------------
+from ..commongrid.utils import _parse_x_bin, ping_time_bin_parsing_and_conversion, resample_edges  # noqa: E402
+
+
+@xarray_io()
+def regrid_mask(mask_da, range_da, range_bin="20m", ping_time_bin="20s", third_dim=None, func="logical-AND",
+                method="map-reduce", reindex=False, closed="left", range_var_max=None, **flox_kwargs):
+    """``mask_da`` brought onto the (ping-time bin, range bin) grid of ``compute_MVBS``.
+
+    A cell of the result is 1 / True where samples fall into it and, ``func="logical-AND"``, all of them are 1, or,
+    ``func="logical-OR"``, one of them is; a cell without samples is 0 for both (the reference takes the group-by mean
+    with ``fill_value=0.0`` and tests it for ``== 1.0`` / ``!= 0.0``).  The range edges are
+    ``np.arange(0, range_var_max + 1e-8 + range_bin, range_bin)``, ``range_var_max`` the NaN-skipping maximum of
+    ``range_da`` unless given (a string such as ``"250m"``); the time edges are those of
+    ``ping_time.resample(ping_time=ping_time_bin)`` plus one closing edge; ``closed`` says which side of the intervals
+    of both axes is closed.  Samples beyond the last range edge or with a NaN range belong to no cell.
+
+    ``mask_da``: dimensions ``ping_time`` and ``depth`` plus ``third_dim`` if given, in any order; bool, uint8, any
+    integer or float type holding only 0 and 1 (else ``ValueError``); on the device or the host.  ``range_da``: the range
+    of every sample over ``depth``, or over ``(ping_time, depth)``; its name is the name of the result's range
+    dimension.  With ``third_dim``, the result has one slice per distinct value of that coordinate, in sorted order;
+    slices of ``mask_da`` with the same value merge their samples.  ``method``, ``reindex`` and ``flox_kwargs`` are
+    checked as the reference checks them and otherwise ignored.  ``ping_time`` must be non-decreasing without NaT
+    (``NotImplementedError`` otherwise: the time bins are offsets into the sorted pings); sharded datasets are not
+    supported.
+
+    Returns a DataArray with ``mask_da``'s name and type over ``(third_dim,) ping_time, <range_da.name>``, the
+    coordinates the left edges of the bins, and the reference's attributes.  Its data stays on the device.
+
+    Device work: one sweep over the mask (16 mask bytes per lane and load).  A workgroup takes a run of consecutive
+    pings of one slice; with a 1-D range its lanes OR / AND the rows of a time bin in registers, the flags "a sample
+    fell into the cell" and "a zero (AND) / a one (OR) fell into it" meet in LDS and are merged into the result with
+    atomic OR, so a time bin of any length is shared by many workgroups and the result does not depend on their
+    order; a range grid too large for LDS (more than 32768 bins) merges into the result directly.  A small launch
+    before clears the flags, one after turns them into the result.  Host synchronisations: one for a bool / uint8 mask
+    (the kernel's "a byte is neither 0 nor 1" word, read after the sweep) plus one for the maximum of a ``range_da``
+    that lies on the device and no ``range_var_max``; masks of other types are checked and narrowed with torch first
+    (one more)."""
+    if method != "map-reduce" and reindex is not None:
+        raise ValueError(f"Passing in reindex={reindex} is only allowed when method='map_reduce'.")
+    if not isinstance(ping_time_bin, str):
+        raise TypeError("ping_time_bin must be a string")
+    mask_da = from_xarray(mask_da)
+    range_da = from_xarray(range_da)
+    if third_dim is None and len(mask_da.dims) != 2:
+        raise ValueError("Mask must have only 2 dimensions unless 'third_dim' is specified.")
+    if third_dim is not None and third_dim not in mask_da.dims:
+        raise ValueError(f"Mask must contain the specified '{third_dim}' as a dimension.")
+    if third_dim is not None and len(mask_da.dims) != 3:
+        raise ValueError("Mask must have 3 dimensions when 'third_dim' is specified.")
+    core = ("ping_time", "depth")
+    if set(mask_da.dims) != set(core) | ({third_dim} if third_dim is not None else set()):
+        raise ValueError(f"Mask must have the dimensions 'ping_time' and 'depth', got {tuple(mask_da.dims)}")
+    order = ((third_dim,) if third_dim is not None else ()) + core
+
+    in_dtype = mask_da.data.tensor.dtype if is_device(mask_da.data) else None
+    if in_dtype is None and mask_da.dtype in (np.bool_, np.uint8):
+        in_dtype = torch.bool if mask_da.dtype == np.bool_ else torch.uint8
+    by_kernel = in_dtype in (torch.bool, torch.uint8)  # the sweep itself reports a byte that is neither 0 nor 1
+    m_t = None
+    if by_kernel:
+        pass
+    elif is_device(mask_da.data):
+        m_t = device_view(mask_da, order)
+        if not bool(((m_t == 0) | (m_t == 1)).all()):
+            raise ValueError("Mask must be binary True/False or 1/0.")
+        m_t = m_t.to(torch.uint8)
+    else:
+        host = np.asarray(mask_da.data)
+        if not np.isin(host, [1, 0]).all():
+            raise ValueError("Mask must be binary True/False or 1/0.")
+        in_dtype = host.dtype
+        mask_da = DataArray(host.astype(np.uint8), mask_da.dims, mask_da.coords, name=mask_da.name)
+    if func not in ["logical-AND", "logical-OR"]:
+        if in_dtype == torch.uint8:  # (the reference's order: the binary check comes first; no sweep will run to make it)
+            d = mask_da.data
+            if bool((d.tensor > 1).any()) if is_device(d) else bool((np.asarray(d) > 1).any()):
+                raise ValueError("Mask must be binary True/False or 1/0.")
+        raise ValueError("'func' must be 'logical-AND' or 'logical-OR'.")
+    if closed not in ["right", "left"]:
+        raise ValueError(f"{closed} is not a valid option. Options are 'left' or 'right'.")
+    if m_t is None:
+        m_t = device_view(mask_da, order)
+    if m_t.dim() == 2:
+        m_t = m_t.unsqueeze(0)
+    T, P, D = m_t.shape
+
+    # the range grid
+    range_bin = _parse_x_bin(range_bin)
+    if range_da.name is None:
+        raise ValueError("range_da must have a name: it names the range dimension of the result")
+    if set(range_da.dims) not in ({"depth"}, set(core)):
+        raise ValueError(f"range_da must have the dimensions ('depth',) or ('ping_time', 'depth'), got {tuple(range_da.dims)}")
+    r_t = device_view(range_da, core, dtype=torch.float64)
+    if tuple(r_t.shape) not in ((D,), (P, D)):
+        raise ValueError(f"range_da of shape {tuple(r_t.shape)} does not match the mask ({P} pings, {D} samples)")
+    if range_var_max is None:
+        if is_device(range_da.data):
+            range_var_max = ops.nanminmax(r_t)[1]
+        else:
+            a = np.asarray(range_da.data, dtype=np.float64)
+            range_var_max = float(np.max(a[~np.isnan(a)])) if np.any(~np.isnan(a)) else float("nan")
+        if not np.isfinite(range_var_max):
+            raise ValueError("range_da holds no finite maximum to size the range grid with")
+    else:
+        range_var_max = _parse_x_bin(range_var_max)
+    range_var_max = range_var_max + 1e-8  # (the reference: "to ensure that we grab the last value")
+    range_edges = np.arange(0, range_var_max + range_bin, range_bin)
+    n_rbins = len(range_edges) - 1
+
+    # the time grid
+    ping_time = np.asarray(mask_da.coords["ping_time"])
+    _, sorted_valid, pt_dev = ops.ping_time_facts(ping_time)
+    if not sorted_valid:
+        raise NotImplementedError("regrid_mask needs a non-decreasing ping_time without NaT")
+    e0, dt, n_tbins = resample_edges(ping_time, ping_time_bin, sorted_valid=True)
+    bin_start = ops.time_bin_offsets(pt_dev, e0, dt, n_tbins, closed)
+
+    # the slices of the third dimension: one per distinct coordinate value, sorted (expected_groups=None)
+    group = third_vals = None
+    n_groups = T
+    if third_dim is not None:
+        vals = np.asarray(mask_da.coords[third_dim]) if third_dim in mask_da.coords else np.arange(T)
+        third_vals, inverse = np.unique(vals, return_inverse=True)
+        n_groups = len(third_vals)
+        if not np.array_equal(inverse, np.arange(T)):
+            group = ops.to_device_small(inverse.astype(np.int32), device=m_t.device)
+
+    out, nonbinary = ops.regrid_mask(m_t, r_t, bin_start, n_tbins, range_bin, n_rbins, group=group, n_groups=n_groups,
+                                     func=func, closed=closed)
+    if by_kernel and int(nonbinary.item()):
+        raise ValueError("Mask must be binary True/False or 1/0.")
+    if third_dim is None:
+        out = out[0]
+    if isinstance(in_dtype, torch.dtype):
+        out = out.view(torch.bool) if in_dtype == torch.bool else out.to(in_dtype)
+        data = DeviceArray(out)
+    else:  # a host mask of a type torch may lack: the small result is given that type on the device where it has it
+        td = getattr(torch, np.dtype(in_dtype).name, None)
+        data = DeviceArray(out.to(td)) if isinstance(td, torch.dtype) else out.cpu().numpy().astype(in_dtype)
+
+    range_var = range_da.name
+    value, unit = ping_time_bin_parsing_and_conversion(ping_time_bin)
+    coords = OrderedDict()
+    if third_dim is not None:
+        coords[third_dim] = third_vals
+    coords["ping_time"] = (np.int64(e0) + np.int64(dt) * np.arange(n_tbins, dtype=np.int64)).view("datetime64[ns]")
+    coords[range_var] = DataArray(range_edges[:-1].astype(np.float64), (range_var,),
+                                  attrs={"long_name": "Range distance", "units": "m"})
+    return DataArray(
+        data, ((third_dim,) if third_dim is not None else ()) + ("ping_time", range_var), coords=coords,
+        name=mask_da.name,
+        attrs={
+            "cell_methods": f"ping_time: mean (interval: {value} {unit} comment: ping_time is the interval start) "
+                            f"{range_var}: mean (interval: {range_bin} meter comment: {range_var} is the interval start)",
+            "binning_mode": "physical units",
+            "range_meter_interval": str(range_bin) + "m",
+            "ping_time_interval": ping_time_bin,
+        })

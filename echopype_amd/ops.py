@@ -986,6 +986,50 @@ def transient_matecho(sv, range_rows, chan_i, chan_d, bottom, half_window, perce
     return mask
 
 
+# ---- masks from Sv differences, masks on the MVBS grid (mask.frequency_differencing / mask.regrid_mask) ----------------
+_CMP = {">": _lib.CMP_GT, "<": _lib.CMP_LT, "<=": _lib.CMP_LE, ">=": _lib.CMP_GE, "==": _lib.CMP_EQ}
+
+
+def freq_diff_mask(sv, chan_a, chan_b, operator, diff):
+    """(sv[chan_a] - sv[chan_b]) operator diff -> bool like ``sv[0]``; ``sv`` float32 / float64 with the channel axis
+    first.  The difference and ``diff`` are rounded in sv's dtype, as NumPy does (``epa_freq_diff_mask``)."""
+    if operator not in _CMP:
+        raise ValueError(f"freq_diff_mask: operator must be one of {list(_CMP)}, got {operator!r}")
+    C = sv.shape[0]
+    out = torch.empty(tuple(sv.shape[1:]), dtype=torch.bool, device=sv.device)
+    call("epa_freq_diff_mask", _p(sv), C, out.numel(), int(chan_a), int(chan_b), _CMP[operator], float(diff), _p(out),
+         _DT[sv.dtype], _stream())
+    return out
+
+
+def regrid_needs_global_flags(n_rbins):
+    """Mirror of mask_grid.hip: the flags of one time bin (4 bytes per range bin) do not fit in LDS."""
+    return 4 * n_rbins > 128 * 1024
+
+
+def regrid_mask(mask, range, bin_start, n_tbins, range_bin, n_rbins, *, group=None, n_groups=None, func="logical-AND",
+                closed="left"):
+    """``mask`` uint8 / bool (T, P, D) onto the (time bin, range bin) grid -> (uint8 (G, n_tbins, n_rbins), int32 (1,)
+    device tensor that is non-zero when a mask byte is neither 0 nor 1).  ``range`` f64 (D,) or (P, D); ``group``
+    int32 (T,) device tensor of output slices 0 .. n_groups-1 or None (identity, G = T) (``epa_regrid_mask``)."""
+    T, P, D = mask.shape
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dtype != torch.uint8:
+        raise ValueError(f"regrid_mask: mask must be bool or uint8, got {mask.dtype}")
+    if range.dtype != torch.float64 or tuple(range.shape) not in ((D,), (P, D)):
+        raise ValueError(f"regrid_mask: range must be float64 of shape ({D},) or ({P}, {D}), got {range.dtype} "
+                         f"{tuple(range.shape)}")
+    G = T if group is None else int(n_groups)
+    cells = G * n_tbins * n_rbins
+    buf = torch.empty((cells + 3) // 4 * 4, dtype=torch.uint8, device=mask.device)  # whole 32-bit words (the header)
+    nonbinary = torch.empty(1, dtype=torch.int32, device=mask.device)
+    call("epa_regrid_mask", _p(mask), _p(group), T, P, D, _p(range), int(range.dim() == 2), _p(bin_start), int(n_tbins),
+         float(range_bin), int(n_rbins), _lib.BIN_CLOSED_RIGHT if closed == "right" else 0,
+         {"logical-AND": 0, "logical-OR": 1}[func], _p(buf), _p(nonbinary), _stream())
+    return buf[:cells].view(G, n_tbins, n_rbins), nonbinary
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

@@ -390,8 +390,11 @@ class DataArray:
         if len(self.dims) != data.ndim:
             raise ValueError(f"dims {self.dims} do not match data of shape {data.shape}")
         self.coords = OrderedDict()
+        self.coord_attrs = {}  # attributes of coordinates that have some (a coordinate given as a DataArray with attrs)
         for k, v in (coords or {}).items():
             self.coords[k] = v if isinstance(v, np.ndarray) else np.asarray(getattr(v, "values", v))
+            if isinstance(v, DataArray) and v.attrs:
+                self.coord_attrs[k] = dict(v.attrs)
         self.attrs = _copy_attrs(attrs)
         self.name = name
 
@@ -430,7 +433,8 @@ class DataArray:
 
     def __getitem__(self, key):
         if isinstance(key, str):
-            return DataArray(self.coords[key], dims=(key,) if self.coords[key].ndim == 1 else None)
+            return DataArray(self.coords[key], dims=(key,) if self.coords[key].ndim == 1 else None,
+                             attrs=self.coord_attrs.get(key))
         return self.values[key]
 
     def __len__(self):
@@ -438,10 +442,13 @@ class DataArray:
 
     def copy(self):
         d = self.data if isinstance(self.data, DeviceArray) else self.data.copy()
-        return DataArray(d, self.dims, dict(self.coords), self.attrs, self.name)
+        out = DataArray(d, self.dims, dict(self.coords), self.attrs, self.name)
+        out.coord_attrs = {k: dict(v) for k, v in self.coord_attrs.items()}
+        return out
 
     def assign_attrs(self, attrs=None, **kw):
         out = DataArray(self.data, self.dims, dict(self.coords), self.attrs, self.name)
+        out.coord_attrs = {k: dict(v) for k, v in self.coord_attrs.items()}
         out.attrs.update(attrs or {})
         out.attrs.update(kw)
         return out
@@ -703,8 +710,12 @@ def to_xarray(obj):
     if isinstance(obj, DataArray):
         if _xr is None:
             raise ImportError("xarray is not installed")
-        return _xr.DataArray(obj.values, dims=obj.dims, coords={k: v for k, v in obj.coords.items() if np.ndim(v) == 1},
-                             attrs=dict(obj.attrs), name=obj.name)
+        out = _xr.DataArray(obj.values, dims=obj.dims, coords={k: v for k, v in obj.coords.items() if np.ndim(v) == 1},
+                            attrs=dict(obj.attrs), name=obj.name)
+        for k, at in obj.coord_attrs.items():
+            if k in out.coords:
+                out.coords[k].attrs.update(at)
+        return out
     if isinstance(obj, (tuple, list)):
         return type(obj)(to_xarray(o) for o in obj)
     return obj

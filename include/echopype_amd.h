@@ -775,6 +775,32 @@ int epa_transient_matecho(const void* sv, int dtype, int C, int P, int S, const 
                           double percentile, double delta_db, int extend_ping, double min_window, int* s_hi,
                           uint8_t* flag, uint8_t* mask_out, epa_stream_t stream);
 
+/* ---- masks from Sv differences and masks on the MVBS grid: mask.frequency_differencing / mask.regrid_mask ------------
+ * mask_out[i] = (sv[chan_a*n + i] - sv[chan_b*n + i]) cmp diff (mask/api.py:593-608): sv [C*n] of dtype F32 / F64,
+ * mask_out u8 [n].  NumPy's arithmetic for an array and a Python scalar: the difference is rounded in dtype and diff
+ * is converted to dtype before the comparison (float32 data: fl32(a - b) against fl32(diff)).  NaN on either side and
+ * inf - inf give 0 for all five operators. */
+enum epa_cmp { EPA_CMP_GT = 0, EPA_CMP_LT = 1, EPA_CMP_LE = 2, EPA_CMP_GE = 3, EPA_CMP_EQ = 4 };
+int epa_freq_diff_mask(const void* sv, int C, size_t n, int chan_a, int chan_b, int cmp, double diff,
+                       uint8_t* mask_out, int dtype, epa_stream_t stream);
+
+/* A mask on the (ping-time bin, range bin) grid of compute_MVBS (mask/api.py:759-841: a group-by mean followed by
+ * == 1.0 / != 0.0, kept here as two flags per cell: did any sample fall into it, did any zero (AND) / any one (OR)).
+ *   mask   : u8 [T*P*D] (T = 1 without a third dimension); the low bit of a byte is its value
+ *   group  : i32 [T] on the device or NULL (identity): the output slice of every input slice; its values are exactly
+ *            0 .. G-1, each at least once (slices with the same value merge their samples)
+ *   range  : f64 [D], or [P*D] when range_per_ping != 0; NaN: the sample belongs to no cell
+ *   bin_start : i32 [n_tbins+1] (epa_time_bin_offsets); range edges e_i = i*range_bin, i = 0..n_rbins, the side
+ *            EPA_BIN_CLOSED_RIGHT of bin_flags selects closed; samples outside the edges are dropped
+ *   func   : 0 = AND (1 where a cell holds samples and all are one), 1 = OR (1 where it holds a one); empty cells are 0
+ *   out    : u8 [G*n_tbins*n_rbins], 4-byte aligned, in an allocation that reaches the next multiple of 4 bytes (the
+ *            flags are merged with 32-bit atomics; bytes past the last cell keep their value)
+ *   nonbinary_out : i32 [1], non-zero when a mask byte is neither 0 nor 1 (np.isin(mask, [1, 0]).all(), :752)
+ * The result does not depend on the order in which workgroups finish. */
+int epa_regrid_mask(const uint8_t* mask, const int32_t* group, int T, int P, int D, const double* range,
+                    int range_per_ping, const int32_t* bin_start, int n_tbins, double range_bin, int n_rbins,
+                    unsigned bin_flags, int func, uint8_t* out, int32_t* nonbinary_out, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
