@@ -156,6 +156,7 @@ SIGNATURES = {
     "epa_transient_matecho": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _d, _vp, _vp, _vp, _vp],
     "epa_freq_diff_mask": [_vp, _i, _sz, _i, _i, _i, _d, _vp, _i, _vp],
     "epa_regrid_mask": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _u, _i, _vp, _vp, _vp],
+    "epa_echo_metrics": [_vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -1030,6 +1030,34 @@ def regrid_mask(mask, range, bin_start, n_tbins, range_bin, n_rbins, *, group=No
     return buf[:cells].view(G, n_tbins, n_rbins), nonbinary
 
 
+# ---- echo summary statistics per row (metrics.*) ------------------------------------------------------------------------
+METRICS = ("abundance", "center_of_mass", "dispersion", "evenness", "aggregation")
+
+
+def echo_metrics(sv, range, *, cm=None, want=METRICS, _max_grid=0):
+    """The statistics named in ``want`` of every row of ``sv`` (R, S) -> {name: (R,) tensor of sv's dtype}, from one
+    sweep over ``sv`` and ``range`` (``epa_echo_metrics``).  ``range``: sv's dtype, (R, S) or (S,) shared by all rows.
+    ``cm``: float64 (R,) centres for ``dispersion``; None: the row's own centre of mass.  The arrays may start at any
+    element (a contiguous view).  ``_max_grid``: the most workgroups to launch (tests: the row loops at small shapes)."""
+    want = tuple(want)
+    if not want or any(w not in METRICS for w in want):
+        raise ValueError(f"echo_metrics: want must name some of {METRICS}, got {want!r}")
+    if sv.dim() != 2 or sv.dtype not in _DT:
+        raise ValueError(f"echo_metrics: sv must be float32 / float64 of shape (R, S), got {sv.dtype} {tuple(sv.shape)}")
+    R, S = sv.shape
+    if range.dtype != sv.dtype or tuple(range.shape) not in ((R, S), (S,)):
+        raise ValueError(f"echo_metrics: range must be {sv.dtype} of shape ({R}, {S}) or ({S},), got {range.dtype} "
+                         f"{tuple(range.shape)}")
+    if cm is not None and (cm.dtype != torch.float64 or tuple(cm.shape) != (R,)):
+        raise ValueError(f"echo_metrics: cm must be float64 of shape ({R},), got {cm.dtype} {tuple(cm.shape)}")
+    out = {w: torch.empty(R, dtype=sv.dtype, device=sv.device) for w in METRICS if w in want}
+    if R == 0:
+        return out
+    call("epa_echo_metrics", _p(sv), _p(range), int(range.dim() == 2), R, S, _p(cm), *(_p(out.get(w)) for w in METRICS),
+         _DT[sv.dtype], int(_max_grid), _stream())
+    return out
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

@@ -801,6 +801,21 @@ int epa_regrid_mask(const uint8_t* mask, const int32_t* group, int T, int P, int
                     int range_per_ping, const int32_t* bin_start, int n_tbins, double range_bin, int n_rbins,
                     unsigned bin_flags, int func, uint8_t* out, int32_t* nonbinary_out, epa_stream_t stream);
 
+/* ---- echo summary statistics per row: metrics.abundance / center_of_mass / dispersion / evenness / aggregation --------
+ * (metrics/summary_statistics.py).  sv [R*S] and range of dtype F32 / F64; range is [R*S] when range_per_row != 0,
+ * else [S], shared by all rows.  For j = 1 .. S-1: dz_j = range_j - range_{j-1} rounded in dtype, 0 -> NaN;
+ * lin_j = 10^(sv_j / 10) (F32: exp10f(sv_j * 0.1f)); w_j = lin_j dz_j.  In double, each sum skipping its NaN terms (an
+ * all-NaN row, and S <= 1, sum to 0):  A = sum w_j,  B = sum range_j w_j,  Q = sum lin_j^2 dz_j,
+ * I = sum (range_j - cm)^2 w_j with cm = B / A of the same row, or cm_in[row] when cm_in (f64 [R], device) is given.
+ *   abundance = 10 log10 A, center_of_mass = B / A, dispersion = I / A, evenness = A^2 / Q, aggregation = Q / A^2,
+ * each [R] of dtype, rounded once; a NULL output is not computed, at least one is wanted.  +-inf, negative dz and 0/0
+ * follow IEEE.  Every array may start at any element.  A row is reduced by one wave (S <= 2048) or one workgroup, in a
+ * fixed order: the result does not depend on scheduling, nor on which other outputs are asked for, nor on max_grid:
+ * the most workgroups to launch, 1 .. 65536, 0 = 65536 (waves and workgroups beyond take further rows in a loop). */
+int epa_echo_metrics(const void* sv, const void* range, int range_per_row, long long R, long long S,
+                     const double* cm_in, void* abundance, void* center_of_mass, void* dispersion, void* evenness,
+                     void* aggregation, int dtype, int max_grid, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
