@@ -31,6 +31,7 @@ FLAG_GUARD_POS, FLAG_MASK_RANGE = 1, 2
 BIN_SKIPNA, BIN_CLOSED_RIGHT, BIN_RANGE_AS_STORED = 1, 2, 4
 POOL_NANMEAN, POOL_NANMEDIAN = 0, 1
 CMP_GT, CMP_LT, CMP_LE, CMP_GE, CMP_EQ = range(5)  # enum epa_cmp
+ALIGN_LINEAR, ALIGN_NEAREST = 0, 1  # epa_align_to_ping_time mode
 CCP = ("sample_interval", "tau_nominal", "transmit_power", "sound_speed", "absorption", "gain", "freq_center", "psi",
        "sa_correction", "z_er", "z_et", "angle_offset_alongship", "angle_offset_athwartship", "beamwidth_alongship",
        "beamwidth_athwartship")  # enum epa_ccoef_param
@@ -157,6 +158,7 @@ SIGNATURES = {
     "epa_freq_diff_mask": [_vp, _i, _sz, _i, _i, _i, _d, _vp, _i, _vp],
     "epa_regrid_mask": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _u, _i, _vp, _vp, _vp],
     "epa_echo_metrics": [_vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "epa_align_to_ping_time": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

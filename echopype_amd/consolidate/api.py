@@ -1,4 +1,4 @@
-"""consolidate.add_depth -- the step between compute_Sv and compute_MVBS(range_var="depth")
+"""consolidate.add_depth and add_location -- the steps between compute_Sv and compute_MVBS(range_var="depth")
 (SURVEY 8f "next" row 1; reference: /root/reference/echopype/consolidate/api.py:68-243).
 
 depth = transducer_depth + orientation * echo_range * echo_range_scaling; the (channel, ping_time,
@@ -17,11 +17,16 @@ import torch
 
 from .. import ops
 from ..device_view import as_tensor, broadcast_to_dims
-from ..xr_lite import DataArray, DeviceArray, LazyDeviceArray, from_xarray, xarray_io
+from ..xr_lite import DataArray, Dataset, DeviceArray, LazyDeviceArray, from_xarray, xarray_io
+from ..utils.align import align_many_to_ping_time
+from ..utils.prov import insert_processing_level
 from .ek_depth_utils import (align_to_ping_time, ek_use_beam_angles, ek_use_platform_angles,
                              ek_use_platform_vertical_offsets)
+from .loc_utils import check_loc_time_dim_duplicates, check_loc_vars_validity, loc_names, sel_nmea
 
 logger = logging.getLogger("echopype_amd.consolidate")
+
+POSITION_VARIABLES = ["latitude", "longitude"]
 
 
 def _align_to_ping_time(da, ping_time):
@@ -169,6 +174,57 @@ def add_depth(ds, echodata=None, depth_offset=None, tilt=None, downward=True,
                    + (f", Echodata `{beam_group_name}` Angles" if used_beam_angles and beam_group_name else "")
                    + "."})
     return ds
+
+
+@xarray_io()  # the reference returns a copy: the caller's dataset is left as it is
+def add_location(ds, echodata, datagram_type=None, nmea_sentence=None):
+    """Add ``latitude`` and ``longitude`` on ``ping_time`` to an Sv or MVBS dataset (a copy is returned), interpolated
+    linearly from the navigation track of ``echodata["Platform"]`` (consolidate/api.py:245-342 of the reference).
+
+    ``datagram_type``: None (positions from NMEA datagrams: ``latitude`` / ``longitude``), or ``"MRU1"`` / ``"IDX"`` for
+    EK models (``latitude_mru1`` ...).  ``nmea_sentence``: use only the fixes of that NMEA sentence type, e.g. "GGA"
+    (NMEA positions only).  Missing or all-NaN positions raise; NaNs or zeros among them are warned about; duplicate
+    times in the selected subset raise.
+
+    Only ``ds["ping_time"]`` is read.  Both variables come from one kernel launch (``epa_align_to_ping_time``, one search
+    per ping) and stay in HBM as float64; the end segments extrapolate, a NaN fix spoils the two segments it belongs to,
+    a NaT ping gives NaN.  A single fix is repeated on every ping and a track on ``ping_time`` itself passes through, both
+    without a launch.  ``processing_level`` becomes "Level 2A" when the fixes that were used hold a finite latitude and
+    a finite longitude (the reference looks at the interpolated positions instead: the same answer unless every ping
+    falls on a segment spoiled by a NaN fix); nothing is read back for that."""
+    from ..echodata import as_lite_echodata
+
+    ds = from_xarray(ds)
+    echodata = as_lite_echodata(echodata)  # (echopype's own EchoData, handed in by position: its groups as lite Datasets)
+    lat_name, lon_name = loc_names(echodata.sonar_model, datagram_type)
+
+    for validity_check in ("missing", "all_nan", "some_nan", "some_zero"):  # the first two raise, the others warn
+        check_loc_vars_validity(echodata, lat_name, lon_name, datagram_type, validity_check)
+
+    time_dim_name = list(echodata["Platform"][lon_name].dims)[0]
+    loc_vars = []
+    for loc_name in (lat_name, lon_name):
+        loc_var = sel_nmea(echodata=echodata, loc_name=loc_name, nmea_sentence=nmea_sentence, datagram_type=datagram_type)
+        check_loc_time_dim_duplicates(loc_var, time_dim_name)
+        loc_vars.append(loc_var)
+
+    # both variables lie on the Platform group's one ``time_dim_name`` coordinate: one search, one launch for the two
+    aligned = align_many_to_ping_time(loc_vars, time_dim_name, ds["ping_time"], "linear")
+
+    interp_ds = ds.copy()
+    now = datetime.datetime.now(datetime.timezone.utc)
+    # (the reference's wording, its `depth` slip included)
+    history_attr = f"{now}. `depth` calculated using:Interpolated or propagated from Platform {lat_name}/{lon_name}."
+    for name, da in zip(POSITION_VARIABLES, aligned):
+        interp_ds[name] = DataArray(da.data, ("ping_time",), attrs={**da.attrs, "history": history_attr})
+    if time_dim_name in interp_ds:
+        interp_ds = interp_ds.drop_vars(time_dim_name)
+    # "Level 2A" = Sv with valid positions.  The reference looks at the positions it returns; here that would be a
+    # read-back, so the fixes that went in are looked at instead: both variables hold a finite value.
+    fixes = Dataset()
+    for name, v in zip(POSITION_VARIABLES, loc_vars):
+        fixes[name] = ((v.dims[0],), np.asarray(v.values, dtype=np.float64))
+    return insert_processing_level(interp_ds, "L2A", input_ds=fixes)
 
 
 def _lazy_depth(er_lazy, rows, raw, scale, offset, scale_h, offset_h):

@@ -1058,6 +1058,32 @@ def echo_metrics(sv, range, *, cm=None, want=METRICS, _max_grid=0):
     return out
 
 
+# ---- an external clock brought onto ping_time (utils.align.align_to_ping_time, consolidate.add_location) -------------------
+ALIGN_MODES = {"linear": _lib.ALIGN_LINEAR, "nearest": _lib.ALIGN_NEAREST}
+
+
+def align_to_ping_time(t_ext, y, ping_time, method="linear"):
+    """``y`` (V, N) float64, recorded at the int64-ns times ``t_ext`` (N,) (strictly increasing, no NaT), on the int64-ns
+    ``ping_time`` (P,) (any order, INT64_MIN = NaT -> NaN) -> (V, P) float64 (``epa_align_to_ping_time``): one launch,
+    one search per ping for all V rows.  ``method``: "linear" (scipy's interp1d with extrapolation, bit for bit) or
+    "nearest" (ties to the earlier sample, the end sample outside the track)."""
+    if method not in ALIGN_MODES:
+        raise ValueError(f"align_to_ping_time: method must be 'linear' or 'nearest', got {method!r}")
+    if t_ext.dtype != torch.int64 or t_ext.dim() != 1 or ping_time.dtype != torch.int64 or ping_time.dim() != 1:
+        raise ValueError(f"align_to_ping_time: t_ext and ping_time must be 1-D int64, got {t_ext.dtype} "
+                         f"{tuple(t_ext.shape)} and {ping_time.dtype} {tuple(ping_time.shape)}")
+    N, P = t_ext.numel(), ping_time.numel()
+    if y.dtype != torch.float64 or y.dim() != 2 or y.shape[1] != N:
+        raise ValueError(f"align_to_ping_time: y must be float64 of shape (V, {N}), got {y.dtype} {tuple(y.shape)}")
+    if not (t_ext.device == y.device == ping_time.device):
+        raise ValueError(f"align_to_ping_time: t_ext, y and ping_time must be on one device, got {t_ext.device}, "
+                         f"{y.device} and {ping_time.device}")
+    V = y.shape[0]
+    out = torch.empty((V, P), dtype=torch.float64, device=y.device)
+    call("epa_align_to_ping_time", _p(t_ext), N, _p(y), V, _p(ping_time), P, ALIGN_MODES[method], _p(out), _stream())
+    return out
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

@@ -816,6 +816,20 @@ int epa_echo_metrics(const void* sv, const void* range, int range_per_row, long 
                      const double* cm_in, void* abundance, void* center_of_mass, void* dispersion, void* evenness,
                      void* aggregation, int dtype, int max_grid, epa_stream_t stream);
 
+/* ---- utils.align.align_to_ping_time / consolidate.add_location: values on an external clock brought onto ping_time ------
+ * t_ext [N] int64 ns, strictly increasing, no NaT; y [V*N] f64, V rows of N values; ping_time [P] int64 ns in any order,
+ * INT64_MIN = NaT; out [V*P] f64.  All device arrays.  One search per ping serves all V rows.
+ * With x_i = (double)(t_ext[i] - t_ext[0]), q = (double)(ping_time[p] - t_ext[0]) (integer difference, one conversion)
+ * and k = clamp(first i with x_i >= q, 1, N-1):
+ *   mode 0, linear: out = ((y[k] - y[k-1]) / (x[k] - x[k-1])) * (q - x[k-1]) + y[k-1], every operation rounded on its own
+ *     (no fma): scipy's interp1d(kind="linear", fill_value="extrapolate") bit for bit.  The end segments extrapolate; a NaN
+ *     value makes the two segments it belongs to NaN.
+ *   mode 1, nearest: y[k-1] when ping - t_ext[k-1] <= t_ext[k] - ping in int64 (ties to the earlier sample), else y[k];
+ *     a ping outside the track takes the end sample.
+ * A NaT ping gives NaN in both modes.  EPA_EINVAL: N < 2, V < 1, P < 1, a NULL array, a mode other than 0 or 1. */
+int epa_align_to_ping_time(const int64_t* t_ext, int N, const double* y, int V, const int64_t* ping_time, int P, int mode,
+                           double* out, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
