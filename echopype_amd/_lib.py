@@ -32,6 +32,11 @@ BIN_SKIPNA, BIN_CLOSED_RIGHT, BIN_RANGE_AS_STORED = 1, 2, 4
 POOL_NANMEAN, POOL_NANMEDIAN = 0, 1
 CMP_GT, CMP_LT, CMP_LE, CMP_GE, CMP_EQ = range(5)  # enum epa_cmp
 ALIGN_LINEAR, ALIGN_NEAREST = 0, 1  # epa_align_to_ping_time mode
+QC_FACTS = 4  # EPA_QC_FACTS
+QC_FIRST, QC_COUNT, QC_NAT, QC_SLOTS = range(4)  # the words of the facts
+QC_MAX_WIN = 1024  # EPA_QC_MAX_WIN
+QC_MEDIAN_WAVES = 1024  # EPA_QC_MEDIAN_WAVES
+QC_SCAN_TILE = 1024  # EPA_QC_SCAN_TILE
 CCP = ("sample_interval", "tau_nominal", "transmit_power", "sound_speed", "absorption", "gain", "freq_center", "psi",
        "sa_correction", "z_er", "z_et", "angle_offset_alongship", "angle_offset_athwartship", "beamwidth_alongship",
        "beamwidth_athwartship")  # enum epa_ccoef_param
@@ -59,6 +64,7 @@ lib = _load()
 
 _vp, _i, _u, _d, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_size_t
 _i64 = ctypes.c_int64
+_ll = ctypes.c_longlong
 
 # name -> argtypes; every function returns int status except epa_version / epa_last_error
 SIGNATURES = {
@@ -159,6 +165,9 @@ SIGNATURES = {
     "epa_regrid_mask": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _u, _i, _vp, _vp, _vp],
     "epa_echo_metrics": [_vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "epa_align_to_ping_time": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp],
+    "epa_time_reversals": [_vp, _ll, _vp, _vp, _vp],
+    "epa_reversal_medians": [_vp, _ll, _i, _vp, _vp, _vp, _vp],
+    "epa_time_rebuild": [_vp, _ll, _vp, _vp, _vp, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

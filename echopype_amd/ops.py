@@ -284,6 +284,24 @@ def ping_time_facts(ping_time, want_device=True):
     return ns, ok, t
 
 
+def register_ping_time(ping_time, tensor, sorted_and_valid):
+    """Make a datetime64[ns] array that cannot be written to known to :func:`ping_time_facts` together with its int64
+    device twin ``tensor`` and the verdict ``sorted_and_valid``, both computed on the device already (``qc``: the
+    repaired coordinate is the download of ``tensor``).  The next ``ping_time_facts(ping_time)`` on that device then
+    neither looks at the times nor uploads them.  The caller vouches for the three belonging together."""
+    import weakref
+
+    pt = ping_time
+    if not isinstance(pt, np.ndarray) or pt.dtype != np.dtype("datetime64[ns]") or pt.flags.writeable:
+        raise ValueError("register_ping_time: a datetime64[ns] ndarray that cannot be written to is needed")
+    if tensor.dtype != torch.int64 or tuple(tensor.shape) != pt.shape or not tensor.is_cuda or not tensor.is_contiguous():
+        raise ValueError(f"register_ping_time: the tensor must be contiguous int64 of shape {pt.shape} on a device, got "
+                         f"{tensor.dtype} {tuple(tensor.shape)} on {tensor.device}")
+    key = id(pt)
+    _PING_NS[key] = (weakref.ref(pt, lambda _r, k=key, known=_PING_NS: known.pop(k, None)), pt.view(np.int64),
+                     bool(sorted_and_valid), {tensor.device: tensor})
+
+
 def _mode_of(t, C, P):
     n = t.numel()
     if n == 1:
@@ -1081,6 +1099,54 @@ def align_to_ping_time(t_ext, y, ping_time, method="linear"):
     V = y.shape[0]
     out = torch.empty((V, P), dtype=torch.float64, device=y.device)
     call("epa_align_to_ping_time", _p(t_ext), N, _p(y), V, _p(ping_time), P, ALIGN_MODES[method], _p(out), _stream())
+    return out
+
+
+# ---- a time coordinate that steps backwards (qc.exist_reversed_time, qc.coerce_increasing_time) ----------------------------
+QC_MAX_WIN = _lib.QC_MAX_WIN
+
+
+def _qc_times(t, what):
+    if t.dtype != torch.int64 or t.dim() != 1:
+        raise ValueError(f"{what}: the times must be 1-D int64, got {t.dtype} {tuple(t.shape)}")
+    return t.numel()
+
+
+def time_reversals(t, want_list=False):
+    """The facts of the int64 ticks ``t`` (N >= 1; INT64_MIN = NaT) -> (facts, list): ``facts`` int64 (4,) on the device
+    -- the first reversal index (-1: none), the number of reversals, the number of NaT, the entries of the list
+    (``_lib.QC_FIRST`` ...) --, ``list`` the (N - 1,) reversal indices in no particular order (the first ``count`` are
+    meant) or None (``epa_time_reversals``, one launch).  A difference is a reversal when it is negative and touches no
+    NaT."""
+    N = _qc_times(t, "time_reversals")
+    facts = torch.empty(_lib.QC_FACTS, dtype=torch.int64, device=t.device)
+    lst = torch.empty(max(N - 1, 1), dtype=torch.int64, device=t.device) if want_list else None
+    call("epa_time_reversals", _p(t), N, _p(facts), _p(lst), _stream())
+    return facts, lst
+
+
+def reversal_medians(t, facts, lst, win_len, sub=None):
+    """``sub`` (N - 1,) int64 with, at every reversal ``ni`` of ``lst``, the median of the original differences
+    ``d[max(0, ni - win_len) : ni]`` (``epa_reversal_medians``; the other entries are not written).  ``facts`` and ``lst``
+    as :func:`time_reversals` left them for the same ``t``, which must hold no NaT."""
+    N = _qc_times(t, "reversal_medians")
+    if sub is None:
+        sub = torch.empty(N - 1, dtype=torch.int64, device=t.device)
+    if lst.numel() < N - 1 or sub.numel() < N - 1 or facts.numel() != _lib.QC_FACTS:
+        raise ValueError("reversal_medians: facts, list and sub must belong to the times")
+    call("epa_reversal_medians", _p(t), N, int(win_len), _p(facts), _p(lst), _p(sub), _stream())
+    return sub
+
+
+def time_rebuild(t, facts, sub):
+    """The times with the differences at the reversals replaced by ``sub`` (``epa_time_rebuild``: three launches, tile
+    sums, carries, apply) -> a new (N,) int64 tensor; the times up to the first reversal are copies."""
+    N = _qc_times(t, "time_rebuild")
+    if sub.numel() < N - 1 or facts.numel() != _lib.QC_FACTS:
+        raise ValueError("time_rebuild: facts and sub must belong to the times")
+    out = torch.empty_like(t)
+    work = torch.empty((N - 1 + _lib.QC_SCAN_TILE - 1) // _lib.QC_SCAN_TILE, dtype=torch.int64, device=t.device)
+    call("epa_time_rebuild", _p(t), N, _p(facts), _p(sub), _p(work), _p(out), _stream())
     return out
 
 

@@ -830,6 +830,44 @@ int epa_echo_metrics(const void* sv, const void* range, int range_per_row, long 
 int epa_align_to_ping_time(const int64_t* t_ext, int N, const double* y, int V, const int64_t* ping_time, int P, int mode,
                            double* out, epa_stream_t stream);
 
+/* ---- qc.exist_reversed_time / coerce_increasing_time: a time coordinate that steps backwards, found and repaired ---------
+ * (qc/api.py:12-85).  t [N] int64 ticks of a datetime64 coordinate in any unit, INT64_MIN = NaT; all arrays on the device;
+ * all arithmetic is int64 and wraps like NumPy's, so the results are exact whatever order the wavefronts run in.
+ * d[i] = t[i+1] - t[i], i = 0 .. N-2; difference i is a REVERSAL when d[i] < 0 and neither t[i] nor t[i+1] is NaT. */
+#define EPA_QC_FACTS 4         /* int64 words of the facts */
+#define EPA_QC_FIRST 0         /*   the smallest reversal index, -1 without a reversal */
+#define EPA_QC_COUNT 1         /*   the number of reversals */
+#define EPA_QC_NAT 2           /*   the number of NaT among the N times */
+#define EPA_QC_SLOTS 3         /*   entries written to the list (EPA_QC_COUNT with a list, else 0) */
+#define EPA_QC_MAX_WIN 1024    /* the longest median window (it lives in LDS) */
+#define EPA_QC_MEDIAN_WAVES 1024 /* wavefronts of an epa_reversal_medians launch, whatever the number of reversals */
+#define EPA_QC_SCAN_TILE 1024  /* differences per workgroup of epa_time_rebuild */
+
+/* facts [EPA_QC_FACTS] int64 out (initialised here); list [N-1] out or NULL: the reversal indices, in no particular
+ * order.  One launch, one thread per time; with list NULL this is all of exist_reversed_time (facts[EPA_QC_COUNT] != 0).
+ * EPA_EINVAL: N < 1, t or facts NULL. */
+int epa_time_reversals(const int64_t* t, long long N, int64_t* facts, long long* list, epa_stream_t stream);
+
+/* sub[ni] = the median of the original differences d[max(0, ni - win_len) .. ni) for every listed reversal ni (facts and
+ * list as epa_time_reversals left them; the count is read on the device: the launch is the same for any count).  The
+ * differences are recomputed from t, so a reversal inside another one's window enters that median as it is.  An even
+ * number of values gives the wrapping sum of the two middle ones divided by 2, truncated toward zero (np.median of
+ * timedelta64: [3, 8] -> 5, [-3, -8] -> -5, [-3, 8] -> 2, [-8, 3] -> -2).  sub [N-1] int64: only the reversal positions
+ * are written, the rest keeps whatever it held; ni = 0 (an empty window) is not written either.  t must hold no NaT
+ * (facts[EPA_QC_NAT] == 0): a NaT takes part as the integer it is.
+ * EPA_EINVAL: N < 2, win_len outside 1 .. EPA_QC_MAX_WIN, a NULL array. */
+int epa_reversal_medians(const int64_t* t, long long N, int win_len, const int64_t* facts, const long long* list,
+                         int64_t* sub, epa_stream_t stream);
+
+/* out [N] = the repaired times: with f = facts[EPA_QC_FIRST], out[j] = t[j] for j <= f and
+ * out[i+1] = t[f] + sum of d'[f .. i] for i >= f, where d'[i] = sub[i] at a reversal and d[i] elsewhere; without a
+ * reversal out = t.  Three launches on the stream -- the sum of every tile of EPA_QC_SCAN_TILE differences, one workgroup
+ * that turns the tile sums into carries, the tiles again with their carries -- so no workgroup waits for another one.
+ * tile_workspace: int64 [ceil((N-1) / EPA_QC_SCAN_TILE)], scratch.  out must not be t; t without NaT, as above.
+ * EPA_EINVAL: N < 2, a NULL array, out == t. */
+int epa_time_rebuild(const int64_t* t, long long N, const int64_t* facts, const int64_t* sub, int64_t* tile_workspace,
+                     int64_t* out, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
