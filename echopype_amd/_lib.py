@@ -37,6 +37,8 @@ QC_FIRST, QC_COUNT, QC_NAT, QC_SLOTS = range(4)  # the words of the facts
 QC_MAX_WIN = 1024  # EPA_QC_MAX_WIN
 QC_MEDIAN_WAVES = 1024  # EPA_QC_MEDIAN_WAVES
 QC_SCAN_TILE = 1024  # EPA_QC_SCAN_TILE
+CT_I8, CT_I16, CT_I32, CT_I64, CT_F32, CT_F64 = range(6)  # enum epa_concat_type
+CONCAT_SEG_WORDS = 5  # int64 words of an epa_concat_seg: base, P, W, first, C
 CCP = ("sample_interval", "tau_nominal", "transmit_power", "sound_speed", "absorption", "gain", "freq_center", "psi",
        "sa_correction", "z_er", "z_et", "angle_offset_alongship", "angle_offset_athwartship", "beamwidth_alongship",
        "beamwidth_athwartship")  # enum epa_ccoef_param
@@ -168,6 +170,7 @@ SIGNATURES = {
     "epa_time_reversals": [_vp, _ll, _vp, _vp, _vp],
     "epa_reversal_medians": [_vp, _ll, _i, _vp, _vp, _vp, _vp],
     "epa_time_rebuild": [_vp, _ll, _vp, _vp, _vp, _vp, _vp],
+    "epa_concat_rows": [_vp, _vp, _vp, _vp, _i, _i, _ll, _i, _i, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

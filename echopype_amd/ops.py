@@ -1150,6 +1150,70 @@ def time_rebuild(t, facts, sub):
     return out
 
 
+# ---- many files into one volume (combine_echodata) -----------------------------------------------------------------------
+_CT = {torch.int8: _lib.CT_I8, torch.int16: _lib.CT_I16, torch.int32: _lib.CT_I32, torch.int64: _lib.CT_I64,
+       torch.float32: _lib.CT_F32, torch.float64: _lib.CT_F64}
+_CT_BITS = {1: _lib.CT_I8, 2: _lib.CT_I16, 4: _lib.CT_I32, 8: _lib.CT_I64}  # any other type, by its size: a bitwise copy
+_CT_PROMOTED = {torch.int8: torch.float32, torch.int16: torch.float32, torch.int32: torch.float64,
+                torch.int64: torch.float64}
+
+
+def concat_rows(srcs, chan_maps=None, out_dtype=None):
+    """The device tensors ``srcs[i]`` of shape (C_i, P_i, S_i) or (C_i, P_i, S_i, B), all of one dtype, joined along
+    their second axis into ``out`` (C, sum P_i, max S_i[, B]); rows shorter than the longest are NaN-padded
+    (``epa_concat_rows``: one launch however many tensors, every source byte read once, every output byte written once).
+    ``chan_maps[i][c]``: the channel of ``srcs[i]`` that becomes output channel ``c`` (None: the tensors' own order, all
+    C_i equal).  ``out_dtype`` None: the sources' own type, or, when a pad is needed and they are integers, the float
+    type NumPy would promote them to for a NaN (int8 / int16 -> float32, int32 / int64 -> float64); otherwise the type
+    asked for, which must be the sources' own or that promotion.  A same-type join is a bitwise copy."""
+    srcs = list(srcs)
+    if not srcs:
+        raise ValueError("concat_rows: at least one tensor is needed")
+    t0 = srcs[0]
+    nd = t0.dim()
+    if nd not in (3, 4):
+        raise ValueError(f"concat_rows: tensors of 3 or 4 dimensions are served, got {tuple(t0.shape)}")
+    for t in srcs:
+        if t.dim() != nd or t.dtype != t0.dtype or t.device != t0.device or (nd == 4 and t.shape[3] != t0.shape[3]):
+            raise ValueError(f"concat_rows: the tensors must agree in dtype, device, number of dimensions and trailing "
+                             f"dimension, got {t.dtype} {tuple(t.shape)} on {t.device} next to {t0.dtype} "
+                             f"{tuple(t0.shape)} on {t0.device}")
+        if t.numel() and not (t.is_cuda and t.is_contiguous()):
+            raise ValueError("concat_rows: C-contiguous device tensors are needed")
+    B = int(t0.shape[3]) if nd == 4 else 1
+    if chan_maps is None:
+        if any(t.shape[0] != t0.shape[0] for t in srcs):
+            raise ValueError("concat_rows: tensors with different numbers of channels need chan_maps")
+        chan_maps = [range(int(t0.shape[0]))] * len(srcs)
+    chan = np.ascontiguousarray(np.array([list(m) for m in chan_maps], dtype=np.int32).reshape(len(srcs), -1))
+    if chan.shape[0] != len(srcs) or chan.shape[1] < 1:
+        raise ValueError(f"concat_rows: chan_maps must hold one row of at least one channel per tensor, got {chan.shape}")
+    C = chan.shape[1]
+    S_out = max(int(t.shape[2]) for t in srcs)
+    padded = any(int(t.shape[2]) < S_out for t in srcs)
+    if out_dtype is None:
+        out_dtype = _CT_PROMOTED.get(t0.dtype, t0.dtype) if padded else t0.dtype
+    if out_dtype == t0.dtype:
+        src_ct = out_ct = _CT.get(t0.dtype) if t0.dtype in (torch.float32, torch.float64) else _CT_BITS.get(t0.element_size())
+    else:
+        src_ct, out_ct = _CT.get(t0.dtype), _CT.get(out_dtype)
+    if src_ct is None or out_ct is None:
+        raise ValueError(f"concat_rows: {t0.dtype} -> {out_dtype} is not served")
+    segs = np.zeros((len(srcs), _lib.CONCAT_SEG_WORDS), dtype=np.int64)
+    first = 0
+    for i, t in enumerate(srcs):
+        segs[i] = (t.data_ptr(), t.shape[1], int(t.shape[2]) * B, first, t.shape[0])
+        first += int(t.shape[1])
+    shape = (C, first, S_out) + ((B,) if nd == 4 else ())
+    out = torch.empty(shape, dtype=out_dtype, device=t0.device)
+    # the segment table holds pointers, so its content is new with nearly every call: a plain upload, not the content-keyed
+    # cache; the channel table is the same for every variable and file set of a survey
+    seg_dev, chan_dev = to_device(segs, device=t0.device), to_device_small(chan, device=t0.device)
+    call("epa_concat_rows", segs.ctypes.data_as(ctypes.c_void_p), _p(seg_dev), chan.ctypes.data_as(ctypes.c_void_p),
+         _p(chan_dev), len(srcs), C, S_out * B, src_ct, out_ct, ctypes.c_void_p(out.data_ptr()), _stream())
+    return out
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

@@ -25,13 +25,14 @@ The three deviations of ``coerce_increasing_time``:
 * fewer than 2 times is a no-op.
 
 A reversal in the very first difference has no window to take a median from: ``IndexError``, the reference's own type.
-``create_old_time_array`` and ``orchestrate_reverse_time_check`` (zarr and Provenance plumbing) are not part of this
-package."""
+``create_old_time_array`` and ``orchestrate_reverse_time_check`` are the reference's Provenance plumbing for a combined
+``EchoData`` (qc/api.py:131-267) without its zarr half: this package writes no files, ``zarr_store`` must be ``None``."""
 import logging
 
 import numpy as np
 
 from .. import _lib, ops
+from ..xr_lite import DataArray
 
 logger = logging.getLogger("echopype_amd.qc")
 
@@ -117,4 +118,42 @@ def check_and_correct_reversed_time(combined_group, time_str, ed_group):
     return before
 
 
+def create_old_time_array(group, old_time_in):
+    """The uncorrected time ``old_time_in`` of the ``EchoData`` group ``group`` as the array that goes into the
+    ``Provenance`` group: a copy of the values named ``<group>_old_<time>`` (the group path in lower case, ``-`` and ``/``
+    written ``_``) on the dimension ``<that name>_dim``, with the input's attributes and a ``comment``.  The input is
+    left as it is."""
+    time_name = old_time_in.name
+    name = f"{group.lower().translate(str.maketrans('-/', '__'))}_old_{time_name}"
+    attrs = {**old_time_in.attrs, "comment": f"Uncorrected {time_name} from the combined group {group}."}
+    return DataArray(np.array(old_time_in.values, copy=True), (f"{name}_dim",), attrs=attrs, name=name)
+
+
+def orchestrate_reverse_time_check(ed_comb, zarr_store, possible_time_dims, storage_options, consolidated=True):
+    """Checks every time dimension named in ``possible_time_dims`` of every group of the combined ``ed_comb`` --
+    ``Platform/NMEA`` excepted, as in the reference: its sentences come out of order and are not meant to be repaired --
+    and repairs in place those that step backwards (:func:`check_and_correct_reversed_time`: a resident coordinate stays
+    resident).  The times from before each repair go into the ``Provenance`` group (:func:`create_old_time_array`), whose
+    attribute ``reversed_ping_times`` ends as 1 if anything was repaired and 0 otherwise.  ``zarr_store`` must be ``None``
+    (``NotImplementedError``): this package writes no files, so ``storage_options`` and ``consolidated`` have no effect."""
+    if zarr_store is not None:
+        raise NotImplementedError("orchestrate_reverse_time_check: zarr_store must be None, this package writes no files")
+    provenance = ed_comb["Provenance"]
+    wanted = set(possible_time_dims)
+    repaired = 0
+    for group in ed_comb.group_paths:
+        if group == "Platform/NMEA":
+            continue
+        dataset = ed_comb[group]
+        for time in sorted(wanted.intersection(dataset.dims)):
+            before = check_and_correct_reversed_time(dataset, time, group)
+            if before is None:
+                continue
+            kept = create_old_time_array(group, before)
+            provenance[kept.name] = kept
+            repaired += 1
+    provenance.attrs["reversed_ping_times"] = 1 if repaired else 0
+
+
+# (the two functions above are reached as qc.create_old_time_array / qc.orchestrate_reverse_time_check)
 __all__ = ["exist_reversed_time", "coerce_increasing_time", "check_and_correct_reversed_time"]

@@ -868,6 +868,31 @@ int epa_reversal_medians(const int64_t* t, long long N, int win_len, const int64
 int epa_time_rebuild(const int64_t* t, long long N, const int64_t* facts, const int64_t* sub, int64_t* tile_workspace,
                      int64_t* out, epa_stream_t stream);
 
+/* ---- combine_echodata: the (channel, ping, range_sample[, beam]) cubes of many files joined along ping into one volume ----
+ * (echodata/combine.py:807-817, xr.concat with its outer join on range_sample).  One launch, whatever the number of files:
+ * every source byte is read once and every output byte written once.
+ *   out[c][first_i + p][w] = src_i[chan[i * C + c]][p][w]   for w < W_i,   NaN for W_i <= w < W_out
+ * NaN is NumPy's np.nan bit for bit: 0x7FC00000 (f32), 0x7FF8000000000000 (f64). */
+typedef struct epa_concat_seg {
+  const void* base; /* the file's variable [C_i][P_i][W_i], C-contiguous, on the device */
+  long long P;      /* its pings, >= 1 */
+  long long W;      /* its row width in ELEMENTS (range_sample, or range_sample * beam), 1 .. W_out */
+  long long first;  /* the output ping of its first ping: the sum of the P before it */
+  long long C;      /* its channels (the bound of its chan entries and of the overlap check; the kernel does not read it) */
+} epa_concat_seg;
+enum epa_concat_type { EPA_CT_I8 = 0, EPA_CT_I16, EPA_CT_I32, EPA_CT_I64, EPA_CT_F32, EPA_CT_F64, EPA_CT_COUNT };
+/* segs [nseg] and chan [nseg][C] (output channel -> source channel of that file) on the device; segs_host / chan_host
+ * the same two tables on the host, which the checks below read -- the caller vouches for the pairs being equal.
+ * src_type == out_type: a bitwise copy of 1-, 2-, 4- or 8-byte elements (NaN payloads, integer planes and any other type of
+ * that size pass through untouched); converting: I8 -> F32, I16 -> F32, I32 -> F64, I64 -> F64 (round to nearest even).
+ * out [C][sum P_i][W_out] of out_type.  A wavefront owns whole output rows and streams them in 16-byte chunks aligned in
+ * the output; no access assumes more than element alignment of a source row.
+ * EPA_EINVAL (nothing is launched): a NULL array; nseg, C or W_out < 1; P_i < 1; W_i outside 1 .. W_out; first_i not the sum
+ * of the P before it; a chan entry outside 0 .. C_i-1; a type pair that is not served; W_i < W_out with an integer out_type
+ * (a pad needs NaN); out overlapping a source. */
+int epa_concat_rows(const epa_concat_seg* segs_host, const epa_concat_seg* segs, const int* chan_host, const int* chan,
+                    int nseg, int C, long long W_out, int src_type, int out_type, void* out, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
