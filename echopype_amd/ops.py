@@ -1214,6 +1214,56 @@ def concat_rows(srcs, chan_maps=None, out_dtype=None):
     return out
 
 
+def upload_file_bytes(data, device=None):
+    """The bytes of a file (anything ``np.frombuffer`` takes) -> (uint8 device tensor padded with zeros to a multiple of
+    16 bytes, the number of file bytes): what ``raw0_unpack`` reads.  One upload of the file as it is on disk."""
+    host = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1).view(np.uint8)
+    n = int(host.size)
+    padded = np.zeros(max(16, -(-n // 16) * 16), dtype=np.uint8)
+    padded[:n] = host
+    return to_device(padded, device=device), n
+
+
+_RAW_ANGLES = {None: _lib.RAW_ANGLE_NONE, "int8": _lib.RAW_ANGLE_I8, "float32": _lib.RAW_ANGLE_F32}
+
+
+def raw0_unpack(file_bytes, table, C, P, S, angles="int8", *, n_bytes=None, out=None):
+    """The RAW0 sample blocks of an EK60 .raw file -> (power, athwartship, alongship) device tensors of shape (C, P, S)
+    (``epa_raw0_unpack``: one launch, every file sample byte read once, every output element written exactly once).
+
+    ``file_bytes``: the file as it is on disk, a uint8 device tensor whose length is a multiple of 16 (``upload_file_bytes``
+    pads it; ``n_bytes``: the file's own length, default all of it).  ``table``: int64 host array (C * P, 3), row
+    ``(c, p)``: byte offset of the int16 power block, byte offset of the int8 (athwartship, alongship) pair block -- -1
+    where the row has none -- and the sample count.  power = ``float32(int16) * float32(10 log10(2) / 256)``, NaN behind
+    the count.  ``angles``: "int8" (every row must be full and have angles), "float32" (NaN-padded) or None (the two
+    planes are returned as None).  ``out``: the three tensors to write into instead of new ones (tests: a pre-filled
+    allocation shows that every element is written)."""
+    if angles not in _RAW_ANGLES:
+        raise ValueError(f"raw0_unpack: angles must be 'int8', 'float32' or None, got {angles!r}")
+    if not (isinstance(file_bytes, torch.Tensor) and file_bytes.dtype == torch.uint8 and file_bytes.dim() == 1):
+        raise ValueError("raw0_unpack: file_bytes must be a one-dimensional uint8 tensor")
+    C, P, S = int(C), int(P), int(S)
+    tab = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, 3))
+    if tab.shape[0] != C * P:
+        raise ValueError(f"raw0_unpack: the table has {tab.shape[0]} rows, C * P = {C * P} are needed")
+    dev = file_bytes.device
+    adt = {None: None, "int8": torch.int8, "float32": torch.float32}[angles]
+    if out is None:
+        power = torch.empty((C, P, S), dtype=torch.float32, device=dev)
+        athw = torch.empty((C, P, S), dtype=adt, device=dev) if adt is not None else None
+        along = torch.empty((C, P, S), dtype=adt, device=dev) if adt is not None else None
+    else:
+        power, athw, along = out
+        for t, dt in ((power, torch.float32), (athw, adt), (along, adt)):
+            if (t is None) != (dt is None) or (t is not None and (t.dtype != dt or tuple(t.shape) != (C, P, S))):
+                raise ValueError("raw0_unpack: out must hold (C, P, S) tensors of the types asked for")
+    tab_dev = to_device(tab, device=dev)
+    call("epa_raw0_unpack", _p(file_bytes), int(file_bytes.numel() if n_bytes is None else n_bytes), int(file_bytes.numel()),
+         tab.ctypes.data_as(ctypes.c_void_p), _p(tab_dev), C, P, S, _RAW_ANGLES[angles], _p(power), _p(athw), _p(along),
+         _stream())
+    return power, athw, along
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

@@ -893,6 +893,49 @@ enum epa_concat_type { EPA_CT_I8 = 0, EPA_CT_I16, EPA_CT_I32, EPA_CT_I64, EPA_CT
 int epa_concat_rows(const epa_concat_seg* segs_host, const epa_concat_seg* segs, const int* chan_host, const int* chan,
                     int nseg, int C, long long W_out, int src_type, int out_type, void* out, epa_stream_t stream);
 
+/* ---- convert.open_raw (EK60): a Simrad .raw file unpacked where it lies ----------------------------------------------
+ * (convert/utils/ek_raw_io.py:242-349, ek_raw_parsers.py:1676-1714, parse_base.py:294-302,686-730, set_groups_ek60.py:646-704)
+ * A .raw file is a sequence of [int32 size][body of size bytes][int32 size], little endian; every body starts with
+ * char type[4]; uint32 low_date; uint32 high_date.  One record per datagram: */
+typedef struct epa_raw_record {
+  int64_t offset;     /* byte offset of the BODY (behind the leading size field) */
+  int32_t size;       /* its size in bytes, >= 16 */
+  uint32_t type;      /* the four type characters as one little-endian word ('R' | 'A' << 8 | 'W' << 16 | '0' << 24) */
+  uint32_t low_date;  /* NT time: 100-ns intervals since 1601-01-01, low and high half */
+  uint32_t high_date;
+  uint32_t flags;     /* EPA_RAW_ZERO_TIME */
+  uint32_t reserved;  /* 0 */
+} epa_raw_record;
+#define EPA_RAW_ZERO_TIME 1u /* the time stamp is (0, 0): the caller skips the datagram (ek_raw_io.py:267-275) */
+
+/* The framing walk, on the HOST: no GPU call, no allocation.  Count, then fill: records_out [capacity] (NULL with
+ * capacity 0) receives the first min(capacity, *n_records) records, *n_records is the number of complete datagrams in any
+ * case.  A body or trailer that runs past n_bytes (a file cut while recording) ends the walk: *n_bytes_consumed is the
+ * offset behind the last complete datagram (== n_bytes for a whole file), the datagrams before it stand.  No byte outside
+ * [0, n_bytes) is read, whatever the bytes are.
+ * EPA_EINVAL, with the byte offset in the message and *n_records / *n_bytes_consumed describing the datagrams in front:
+ * a size below 16; a trailing size that differs from the leading one (the reference searches for the next datagram there,
+ * ek_raw_io.py:325-337; this walk does not resynchronise).  Also a NULL argument or a negative length. */
+int epa_raw_index(const uint8_t* bytes_host, long long n_bytes, epa_raw_record* records_out, long long capacity,
+                  long long* n_records, long long* n_bytes_consumed);
+
+/* power [C][P][S] f32 = float32(int16 at bytes[off_p + 2 s]) * float32(10 log10(2) / 256) for s < count, NaN behind it;
+ * athwartship / alongship [C][P][S] = the int8 at bytes[off_a + 2 s] / bytes[off_a + 2 s + 1].  One launch; every
+ * output element is written exactly once, nothing is pre-filled.
+ * bytes: the file as it is on disk, on the device, n_bytes long in an allocation of n_alloc bytes -- 16-byte aligned,
+ * n_alloc a multiple of 16 -- because the samples are read as the aligned dwords that hold them (a block starts at any
+ * byte offset).  table [C * P][3] int64, row (c, p): off_p, off_a (-1: no such block, the row is NaN) and count;
+ * table_host the same on the host, which the checks read -- the caller vouches for the pair being equal.
+ * angle_type EPA_RAW_ANGLE_NONE: the planes are not touched (may be NULL); _I8: int8 planes, every row must have an angle
+ * block of exactly S samples; _F32: float32 planes, NaN behind count and in rows without a block.  NaN is 0x7FC00000.
+ * EPA_EINVAL (nothing is launched): a NULL array; C, P or S < 1; a count outside 0 .. S; a block that leaves
+ * [0, n_bytes); a buffer or plane that is not 16-byte aligned; n_alloc not a multiple of 16 or below n_bytes; _I8 with a
+ * short or missing row. */
+enum epa_raw_angle { EPA_RAW_ANGLE_NONE = 0, EPA_RAW_ANGLE_I8 = 1, EPA_RAW_ANGLE_F32 = 2 };
+int epa_raw0_unpack(const uint8_t* bytes, long long n_bytes, long long n_alloc, const int64_t* table_host,
+                    const int64_t* table, int C, long long P, long long S, int angle_type, float* power,
+                    void* athwartship, void* alongship, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
