@@ -613,7 +613,7 @@ int run_mvbs(ReduceArgs& a, hipStream_t st) {
                                a.n_valid, reinterpret_cast<const double*>(a.coef), a.C, a.P, a.S,
                                a.nspread, a.cal_flags, a.bin_start, a.n_tbins, a.range_bin,
                                a.n_rbins, a.bin_flags, a.fill_value, a.sv_out, a.out, a.sum_out,
-                               a.cnt_out, sizeof(T) == 8 ? EPA_F64 : EPA_F32, pl.tab_off,
+                               a.cnt_out, epa::dtype_of<T>, pl.tab_off,
                                pl.cnt_off, reinterpret_cast<unsigned long long*>(a.range_max_out),
                                reinterpret_cast<unsigned long long*>(a.range_stats_out), a.dscale, a.doffset,
                                a.depth_out, st);
@@ -628,12 +628,12 @@ int run_mvbs(ReduceArgs& a, hipStream_t st) {
     return epa_chain_fast_pass2(a.raw, reinterpret_cast<const double*>(a.coef), a.alpha2, a.noise, a.C, a.P, a.S,
                                 a.nspread, a.noise_ping_num, a.noise_phase, a.snr, a.bin_start, a.n_tbins, a.range_bin,
                                 a.n_rbins, a.fill_value, a.sv_noise_out, a.sv_out, a.out, a.sum_out, a.cnt_out,
-                                sizeof(T) == 8 ? EPA_F64 : EPA_F32, pl.tab_off, pl.cnt_off, a.mm_keys, st);
+                                epa::dtype_of<T>, pl.tab_off, pl.cnt_off, a.mm_keys, st);
   if (SRC == SRC_SV && !a.range && a.coef && !two_stage && pl.vec == 4 && !a.ping_perm &&
       (a.bin_flags & ~EPA_BIN_RANGE_AS_STORED) == EPA_BIN_SKIPNA && !getenv("EPA_NO_FAST_PATH"))
     return epa_mvbs_rows_fast_path(a.sv, reinterpret_cast<const double*>(a.coef), a.C, a.P, a.S, a.bin_start, a.n_tbins,
                                    a.range_bin, a.n_rbins, (a.bin_flags & EPA_BIN_RANGE_AS_STORED) ? 1 : 0,
-                                   a.fill_value, a.out, a.sum_out, a.cnt_out, sizeof(T) == 8 ? EPA_F64 : EPA_F32,
+                                   a.fill_value, a.out, a.sum_out, a.cnt_out, epa::dtype_of<T>,
                                    pl.tab_off, pl.cnt_off, st);
   if (a.raw_i16) {
     epa::set_error("epa_sv_mvbs_fused_i16: int16 ingest is served by the default configuration only "
@@ -806,10 +806,11 @@ static int fused_entry(const float* raw, const int16_t* raw_i16, const int32_t* 
   a.sv_out = sv_out; a.range_out = range_out; a.out = mvbs_out; a.sum_out = sum_out; a.cnt_out = cnt_out;
   a.range_max_out = range_max_out;
   a.range_stats_out = range_stats_out;
-  EPA_CHECK_ARG(dtype == EPA_F64 || dtype == EPA_F32, "epa_sv_mvbs_fused: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_sv_mvbs_fused", dtype);
   if (int rc0 = init_range_outputs(range_max_out, range_stats_out, (hipStream_t)stream)) return rc0;
-  const int rc = dtype == EPA_F64 ? run_mvbs<double, SRC_RAW>(a, (hipStream_t)stream)
-                                  : run_mvbs<float, SRC_RAW>(a, (hipStream_t)stream);
+  const int rc = epa::dispatch_real("epa_sv_mvbs_fused", dtype, [&](auto tag) {
+    return run_mvbs<typename decltype(tag)::type, SRC_RAW>(a, (hipStream_t)stream);
+  });
   epa::note_range_stats_filled(rc == EPA_OK && range_stats_out && a.range_stats_filled ? 1 : 0);
   if (rc == EPA_OK && range_max_out) {
     return decode_range_outputs(range_max_out, range_stats_out, a.range_stats_filled != 0, dtype == EPA_F32 ? 1 : 0,
@@ -835,10 +836,9 @@ extern "C" int epa_mvbs(const void* sv, const void* range, const double* coef, i
   a.n_rbins = n_rbins; a.range_sample_num = 1; a.bin_flags = bin_flags;
   a.fill_value = fill_value; a.noise_max = __builtin_nan("");
   a.out = mvbs_out; a.sum_out = sum_out; a.cnt_out = cnt_out;
-  if (dtype == EPA_F64) return run_mvbs<double, SRC_SV>(a, (hipStream_t)stream);
-  if (dtype == EPA_F32) return run_mvbs<float, SRC_SV>(a, (hipStream_t)stream);
-  epa::set_error("epa_mvbs: bad dtype %d", dtype);
-  return EPA_EINVAL;
+  return epa::dispatch_real("epa_mvbs", dtype, [&](auto tag) {
+    return run_mvbs<typename decltype(tag)::type, SRC_SV>(a, (hipStream_t)stream);
+  });
 }
 
 extern "C" int epa_mvbs_finalize(const void* sum, const uint32_t* cnt, size_t n, double fill_value,
@@ -847,17 +847,12 @@ extern "C" int epa_mvbs_finalize(const void* sum, const uint32_t* cnt, size_t n,
   if (n == 0) return EPA_OK;
   const size_t blocks = (n + epa::kBlock - 1) / epa::kBlock;
   const int grid = (int)(blocks < 4096 ? blocks : 4096);
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(mvbs_finalize_kernel<double>, dim3(grid), dim3(epa::kBlock), 0,
-                       (hipStream_t)stream, (const double*)sum, cnt, n, fill_value, (double*)out);
-  else if (dtype == EPA_F32)
-    hipLaunchKernelGGL(mvbs_finalize_kernel<float>, dim3(grid), dim3(epa::kBlock), 0,
-                       (hipStream_t)stream, (const float*)sum, cnt, n, (float)fill_value, (float*)out);
-  else {
-    epa::set_error("epa_mvbs_finalize: bad dtype %d", dtype);
-    return EPA_EINVAL;
-  }
-  return epa::check_launch("mvbs_finalize_kernel");
+  return epa::dispatch_real("epa_mvbs_finalize", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(mvbs_finalize_kernel<T>, dim3(grid), dim3(epa::kBlock), 0, (hipStream_t)stream, (const T*)sum, cnt,
+                       n, (T)fill_value, (T*)out);
+    return epa::check_launch("mvbs_finalize_kernel");
+  });
 }
 
 namespace {
@@ -918,14 +913,10 @@ extern "C" int epa_mvbs_index(const void* sv, const void* range, int C, int P, i
   EPA_CHECK_ARG(sv && mvbs_out, "epa_mvbs_index: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0 && ping_num > 0 && range_sample_num > 0,
                 "epa_mvbs_index: sizes must be positive");
-  if (dtype == EPA_F64)
-    return run_index<double>(sv, range, C, P, S, ping_num, range_sample_num, mvbs_out, range_min_out,
-                             (hipStream_t)stream);
-  if (dtype == EPA_F32)
-    return run_index<float>(sv, range, C, P, S, ping_num, range_sample_num, mvbs_out, range_min_out,
-                            (hipStream_t)stream);
-  epa::set_error("epa_mvbs_index: bad dtype %d", dtype);
-  return EPA_EINVAL;
+  return epa::dispatch_real("epa_mvbs_index", dtype, [&](auto tag) {
+    return run_index<typename decltype(tag)::type>(sv, range, C, P, S, ping_num, range_sample_num, mvbs_out,
+                                                   range_min_out, (hipStream_t)stream);
+  });
 }
 
 extern "C" int epa_noise_estimate(const void* sv, const void* range, const double* coef,
@@ -941,14 +932,11 @@ extern "C" int epa_noise_estimate(const void* sv, const void* range, const doubl
                 ping_phase, ping_num);
   EPA_CHECK_ARG((edge_sum_out == nullptr) == (edge_cnt_out == nullptr),
                 "epa_noise_estimate: edge_sum_out and edge_cnt_out come together");
-  if (dtype == EPA_F64)
-    return run_noise<double>(sv, range, coef, alpha2, C, P, S, ping_num, range_sample_num, ping_phase,
-                             noise_max, noise_out, edge_sum_out, edge_cnt_out, (hipStream_t)stream);
-  if (dtype == EPA_F32)
-    return run_noise<float>(sv, range, coef, alpha2, C, P, S, ping_num, range_sample_num, ping_phase, noise_max,
-                            noise_out, edge_sum_out, edge_cnt_out, (hipStream_t)stream);
-  epa::set_error("epa_noise_estimate: bad dtype %d", dtype);
-  return EPA_EINVAL;
+  return epa::dispatch_real("epa_noise_estimate", dtype, [&](auto tag) {
+    return run_noise<typename decltype(tag)::type>(sv, range, coef, alpha2, C, P, S, ping_num, range_sample_num,
+                                                   ping_phase, noise_max, noise_out, edge_sum_out, edge_cnt_out,
+                                                   (hipStream_t)stream);
+  });
 }
 
 // merged (sum, count) rows of noise blocks -> noise value per row (clean/api.py:402-422: mean -> dB -> min over
@@ -1017,7 +1005,7 @@ int run_sv_noise(const float* raw, const double* coef, const double* alpha2, int
                                 noise_out, edge_sum_out, edge_cnt_out,
                                 reinterpret_cast<unsigned long long*>(range_max_out),
                                 reinterpret_cast<unsigned long long*>(range_stats_out),
-                                sizeof(T) == 8 ? EPA_F64 : EPA_F32, st);
+                                epa::dtype_of<T>, st);
   }
   return launch_reduce<T, SRC_RAW, OP_NOISE>(a, pl, st);
 }
@@ -1037,17 +1025,16 @@ extern "C" int epa_sv_noise_fused(const float* raw, const double* coef, const do
                 "epa_sv_noise_fused: edge_sum_out and edge_cnt_out come together");
   EPA_CHECK_ARG(cal_type == EPA_CAL_SV || cal_type == EPA_CAL_TS, "epa_sv_noise_fused: bad cal_type");
   const double nspread = cal_type == EPA_CAL_SV ? 20.0 : 40.0;
-  EPA_CHECK_ARG(dtype == EPA_F64 || dtype == EPA_F32, "epa_sv_noise_fused: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_sv_noise_fused", dtype);
   EPA_CHECK_ARG(!range_stats_out || range_max_out, "epa_sv_noise_fused: range_stats_out needs range_max_out");
   if (int rc0 = init_range_outputs(range_max_out, range_stats_out, (hipStream_t)stream)) return rc0;
   int filled = 0;
-  const int rc = dtype == EPA_F64
-      ? run_sv_noise<double>(raw, coef, alpha2, C, P, S, nspread, cal_flags, ping_num, range_sample_num, ping_phase,
-                             noise_max, sv_out, range_out, noise_out, edge_sum_out, edge_cnt_out, range_max_out,
-                             range_stats_out, &filled, (hipStream_t)stream)
-      : run_sv_noise<float>(raw, coef, alpha2, C, P, S, nspread, cal_flags, ping_num, range_sample_num, ping_phase,
-                            noise_max, sv_out, range_out, noise_out, edge_sum_out, edge_cnt_out, range_max_out,
-                            range_stats_out, &filled, (hipStream_t)stream);
+  const int rc = epa::dispatch_real("epa_sv_noise_fused", dtype, [&](auto tag) {
+    return run_sv_noise<typename decltype(tag)::type>(raw, coef, alpha2, C, P, S, nspread, cal_flags, ping_num,
+                                                      range_sample_num, ping_phase, noise_max, sv_out, range_out,
+                                                      noise_out, edge_sum_out, edge_cnt_out, range_max_out,
+                                                      range_stats_out, &filled, (hipStream_t)stream);
+  });
   epa::note_range_stats_filled(rc == EPA_OK && range_stats_out && filled ? 1 : 0);
   if (rc == EPA_OK && range_max_out) {
     // (the fast kernel tracks the values as stored: no rounding left to do)
@@ -1078,10 +1065,9 @@ extern "C" int epa_denoise_mvbs(const void* sv, const void* range, const double*
   a.fill_value = fill_value; a.noise_max = __builtin_nan("");
   a.sv_out = sv_corrected_out; a.sv_noise_out = sv_noise_out;
   a.out = mvbs_out; a.sum_out = sum_out; a.cnt_out = cnt_out;
-  if (dtype == EPA_F64) return run_mvbs<double, SRC_SV_DENOISE>(a, (hipStream_t)stream);
-  if (dtype == EPA_F32) return run_mvbs<float, SRC_SV_DENOISE>(a, (hipStream_t)stream);
-  epa::set_error("epa_denoise_mvbs: bad dtype %d", dtype);
-  return EPA_EINVAL;
+  return epa::dispatch_real("epa_denoise_mvbs", dtype, [&](auto tag) {
+    return run_mvbs<typename decltype(tag)::type, SRC_SV_DENOISE>(a, (hipStream_t)stream);
+  });
 }
 
 extern "C" int epa_sv_denoise_mvbs(const float* raw, const double* coef, const double* alpha2,
@@ -1112,13 +1098,14 @@ extern "C" int epa_sv_denoise_mvbs(const float* raw, const double* coef, const d
   a.sv_out = sv_corrected_out; a.sv_noise_out = sv_noise_out; a.range_out = range_out;
   a.out = mvbs_out; a.sum_out = sum_out; a.cnt_out = cnt_out;
   a.mm_keys = reinterpret_cast<unsigned long long*>(minmax_out);
-  EPA_CHECK_ARG(dtype == EPA_F64 || dtype == EPA_F32, "epa_sv_denoise_mvbs: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_sv_denoise_mvbs", dtype);
   if (minmax_out) {
     hipLaunchKernelGGL(init_minmax_kernel, dim3(1), dim3(4), 0, (hipStream_t)stream, a.mm_keys);
     if (int rc = epa::check_launch("init_minmax_kernel")) return rc;
   }
-  const int rc = dtype == EPA_F64 ? run_mvbs<double, SRC_RAW_DENOISE>(a, (hipStream_t)stream)
-                                  : run_mvbs<float, SRC_RAW_DENOISE>(a, (hipStream_t)stream);
+  const int rc = epa::dispatch_real("epa_sv_denoise_mvbs", dtype, [&](auto tag) {
+    return run_mvbs<typename decltype(tag)::type, SRC_RAW_DENOISE>(a, (hipStream_t)stream);
+  });
   if (rc == EPA_OK && minmax_out) {
     hipLaunchKernelGGL(decode_minmax_kernel, dim3(1), dim3(4), 0, (hipStream_t)stream, minmax_out);
     return epa::check_launch("decode_minmax_kernel");

@@ -1357,8 +1357,9 @@ int epa_chain_fast_pass1(const float* raw, const double* coef, const double* alp
   a.n_pblocks = (P + ping_phase + ping_num - 1) / ping_num; a.n_rblocks = (S + rsn - 1) / rsn;
   a.noise_max = noise_max; a.rmax_key = rmax_key; a.rstat = rmax_key ? rstat : nullptr;
   a.xcd_map = epa::xcd_map_enabled() ? 1 : 0;
-  if (dtype == EPA_F64) return epa_chain::launch_pass1<double>(a, raw, coef, alpha2, sv_out, noise_out, C, st);
-  return epa_chain::launch_pass1<float>(a, raw, coef, alpha2, sv_out, noise_out, C, st);
+  return epa::dispatch_real("epa_chain_fast_pass1", dtype, [&](auto tag) {
+    return epa_chain::launch_pass1<typename decltype(tag)::type>(a, raw, coef, alpha2, sv_out, noise_out, C, st);
+  });
 }
 
 // Called by epa_sv_denoise_mvbs (block_reduce.hip) when the fast path applies.
@@ -1374,9 +1375,9 @@ int epa_chain_fast_pass2(const float* raw, const double* coef, const double* alp
   a.n_tbins = n_tbins; a.n_rbins = n_rbins; a.range_bin = range_bin; a.inv_range_bin = 1.0 / range_bin;
   a.fill_value = fill_value; a.cnt_off = cnt_off; a.mm_keys = mm_keys;
   a.xcd_map = epa::xcd_map_enabled() ? 1 : 0;
-  if (dtype == EPA_F64)
-    return epa_chain::launch_pass2<double>(a, raw, coef, alpha2, noise, bin_start, noise_out, corr_out, mvbs_out,
-                                           sum_out, cnt_out, C, lds_acc_bytes, st);
-  return epa_chain::launch_pass2<float>(a, raw, coef, alpha2, noise, bin_start, noise_out, corr_out, mvbs_out,
-                                        sum_out, cnt_out, C, lds_acc_bytes, st);
+  return epa::dispatch_real("epa_chain_fast_pass2", dtype, [&](auto tag) {
+    return epa_chain::launch_pass2<typename decltype(tag)::type>(a, raw, coef, alpha2, noise, bin_start, noise_out,
+                                                                 corr_out, mvbs_out, sum_out, cnt_out, C, lds_acc_bytes,
+                                                                 st);
+  });
 }

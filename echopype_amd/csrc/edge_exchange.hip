@@ -100,7 +100,7 @@ extern "C" int epa_edge_pack(const void* const* sum_rows, const uint32_t* const*
   EPA_CHECK_ARG(buf != nullptr, "epa_edge_pack: NULL buffer");
   EPA_CHECK_ARG(C > 0 && R > 0 && n_slots > 0 && n_rows >= 0, "epa_edge_pack: C=%d R=%d n_slots=%d n_rows=%d", C, R,
                 n_slots, n_rows);
-  EPA_CHECK_ARG(sum_dtype == EPA_F32 || sum_dtype == EPA_F64, "epa_edge_pack: bad dtype");
+  EPA_CHECK_ARG(epa::is_real(sum_dtype), "epa_edge_pack: bad dtype");
   EPA_CHECK_ARG(n_rows == 0 || (sum_rows && cnt_rows && chan_stride && slots), "epa_edge_pack: NULL row table");
   for (int i = 0; i < n_rows; ++i) {
     EPA_CHECK_ARG(sum_rows[i] && cnt_rows[i], "epa_edge_pack: row %d is NULL", i);
@@ -130,19 +130,18 @@ extern "C" int epa_edge_gather(const double* buf, int n_slots, const int32_t* gr
   EPA_CHECK_ARG(buf && group_off && group_slots, "epa_edge_gather: NULL array argument");
   EPA_CHECK_ARG(C > 0 && R > 0 && n_slots > 0 && n_edges >= 0, "epa_edge_gather: C=%d R=%d n_slots=%d n_edges=%d", C, R,
                 n_slots, n_edges);
-  EPA_CHECK_ARG(sum_dtype == EPA_F32 || sum_dtype == EPA_F64, "epa_edge_gather: bad dtype");
+  EPA_CHECK_ARG(epa::is_real(sum_dtype), "epa_edge_gather: bad dtype");
   EPA_CHECK_ARG(totals_out || sum_out || cnt_out, "epa_edge_gather: no output requested");
   if (n_edges == 0) return EPA_OK;
   const int CR = C * R;
   const dim3 grid((unsigned)((2 * (size_t)CR + epa::kBlock - 1) / epa::kBlock), (unsigned)n_edges);
   hipStream_t st = (hipStream_t)stream;
-  if (sum_dtype == EPA_F32)
-    hipLaunchKernelGGL(edge_gather_kernel<float>, grid, dim3(epa::kBlock), 0, st, buf, group_off, group_slots, CR, totals_out,
-                       static_cast<float*>(sum_out), cnt_out);
-  else
-    hipLaunchKernelGGL(edge_gather_kernel<double>, grid, dim3(epa::kBlock), 0, st, buf, group_off, group_slots, CR,
-                       totals_out, static_cast<double*>(sum_out), cnt_out);
-  return epa::check_launch("edge_gather_kernel");
+  return epa::dispatch_real("epa_edge_gather", sum_dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(edge_gather_kernel<T>, grid, dim3(epa::kBlock), 0, st, buf, group_off, group_slots, CR, totals_out,
+                       static_cast<T*>(sum_out), cnt_out);
+    return epa::check_launch("edge_gather_kernel");
+  });
 }
 
 extern "C" int epa_edge_finalize_mvbs(const double* buf, int n_slots, const int32_t* group_off, const int32_t* group_slots,
@@ -151,7 +150,7 @@ extern "C" int epa_edge_finalize_mvbs(const double* buf, int n_slots, const int3
   EPA_CHECK_ARG(buf && group_off && group_slots, "epa_edge_finalize_mvbs: NULL array argument");
   EPA_CHECK_ARG(C > 0 && R > 0 && n_slots > 0 && n_rows >= 0, "epa_edge_finalize_mvbs: C=%d R=%d n_slots=%d n_rows=%d", C,
                 R, n_slots, n_rows);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_edge_finalize_mvbs: bad dtype");
+  EPA_CHECK_ARG(epa::is_real(dtype), "epa_edge_finalize_mvbs: bad dtype");
   EPA_CHECK_ARG(n_rows == 0 || (edges && dst_rows && chan_stride), "epa_edge_finalize_mvbs: NULL row table");
   for (int i = 0; i < n_rows; ++i) {
     EPA_CHECK_ARG(dst_rows[i] != nullptr && edges[i] >= 0, "epa_edge_finalize_mvbs: bad row %d", i);
@@ -165,9 +164,10 @@ extern "C" int epa_edge_finalize_mvbs(const double* buf, int n_slots, const int3
     for (int i = 0; i < n; ++i) a.row[i] = FinRow{dst_rows[r0 + i], chan_stride[r0 + i], edges[r0 + i], 0};
     a.C = C; a.R = R; a.fill = fill_value; a.buf = buf; a.goff = group_off; a.gslots = group_slots;
     const dim3 grid((unsigned)((CR + epa::kBlock - 1) / epa::kBlock), (unsigned)n);
-    if (dtype == EPA_F32) hipLaunchKernelGGL(edge_finalize_mvbs_kernel<float>, grid, dim3(epa::kBlock), 0, st, a);
-    else hipLaunchKernelGGL(edge_finalize_mvbs_kernel<double>, grid, dim3(epa::kBlock), 0, st, a);
-    const int rc = epa::check_launch("edge_finalize_mvbs_kernel");
+    const int rc = epa::dispatch_real("epa_edge_finalize_mvbs", dtype, [&](auto tag) {
+      hipLaunchKernelGGL(edge_finalize_mvbs_kernel<typename decltype(tag)::type>, grid, dim3(epa::kBlock), 0, st, a);
+      return epa::check_launch("edge_finalize_mvbs_kernel");
+    });
     if (rc != EPA_OK) return rc;
   }
   return EPA_OK;

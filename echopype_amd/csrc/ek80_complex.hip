@@ -509,20 +509,16 @@ static int sv_complex_entry(const void* re, const void* im, int in_dtype, const 
   a.stats_part = stats_part;
   const int taps = replica ? max_taps : 0;
   hipStream_t st = (hipStream_t)stream;
-  if (!replica) {  // CW: the streaming kernel
-    if (in_dtype == EPA_F64 && out_dtype == EPA_F64) return launch_cw<double, double>(a, st);
-    if (in_dtype == EPA_F64 && out_dtype == EPA_F32) return launch_cw<double, float>(a, st);
-    if (in_dtype == EPA_F32 && out_dtype == EPA_F64) return launch_cw<float, double>(a, st);
-    if (in_dtype == EPA_F32 && out_dtype == EPA_F32) return launch_cw<float, float>(a, st);
-    epa::set_error("epa_sv_complex: bad dtype in=%d out=%d", in_dtype, out_dtype);
-    return EPA_EINVAL;
-  }
-  if (in_dtype == EPA_F64 && out_dtype == EPA_F64) return launch<double, double, double>(a, taps, st);
-  if (in_dtype == EPA_F64 && out_dtype == EPA_F32) return launch<double, float, float>(a, taps, st);
-  if (in_dtype == EPA_F32 && out_dtype == EPA_F64) return launch<float, double, double>(a, taps, st);
-  if (in_dtype == EPA_F32 && out_dtype == EPA_F32) return launch<float, float, float>(a, taps, st);
-  epa::set_error("epa_sv_complex: bad dtype in=%d out=%d", in_dtype, out_dtype);
-  return EPA_EINVAL;
+  EPA_CHECK_ARG(epa::is_real(in_dtype) && epa::is_real(out_dtype), "epa_sv_complex: bad dtype in=%d out=%d", in_dtype,
+                out_dtype);
+  return epa::dispatch_real("epa_sv_complex", in_dtype, [&](auto in) {
+    return epa::dispatch_real("epa_sv_complex", out_dtype, [&](auto out) {
+      using InT = typename decltype(in)::type;
+      using T = typename decltype(out)::type;
+      if (!replica) return launch_cw<InT, T>(a, st);  // CW: the streaming kernel
+      return launch<InT, T, T>(a, taps, st);
+    });
+  });
 }
 
 extern "C" int epa_sv_complex(const void* re, const void* im, int in_dtype, const float* replica,

@@ -765,26 +765,25 @@ extern "C" int epa_selftest_correlate(const void* x, int n_tiles, const float* r
                                       int fft_dtype, void* out, double* workspace, epa_stream_t stream) {
   EPA_CHECK_ARG(x && replica && replica_off && out && workspace, "epa_selftest_correlate: NULL array argument");
   EPA_CHECK_ARG(n_tiles > 0, "epa_selftest_correlate: n_tiles=%d", n_tiles);
-  EPA_CHECK_ARG(fft_dtype == EPA_F32 || fft_dtype == EPA_F64, "epa_selftest_correlate: bad fft_dtype %d", fft_dtype);
+  EPA_CHECK_ARG(epa::is_real(fft_dtype), "epa_selftest_correlate: bad fft_dtype %d", fft_dtype);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(replica_prepare_kernel, dim3(1), dim3(epa::kBlock), 0, st, replica, replica_off, 1, workspace, 0,
                      workspace + ws_logtab(1, 1, 1));
   if (int rc = epa::check_launch("replica_prepare_kernel")) return rc;
-  if (fft_dtype == EPA_F32)
-    hipLaunchKernelGGL(selftest_correlate_kernel<float>, dim3((unsigned)n_tiles), dim3(epa::kBlock), 0, st,
-                       reinterpret_cast<const C2<float>*>(x), workspace, reinterpret_cast<C2<float>*>(out));
-  else
-    hipLaunchKernelGGL(selftest_correlate_kernel<double>, dim3((unsigned)n_tiles), dim3(epa::kBlock), 0, st,
-                       reinterpret_cast<const C2<double>*>(x), workspace, reinterpret_cast<C2<double>*>(out));
-  return epa::check_launch("selftest_correlate_kernel");
+  return epa::dispatch_real("epa_selftest_correlate", fft_dtype, [&](auto tag) {
+    using F = typename decltype(tag)::type;
+    hipLaunchKernelGGL(selftest_correlate_kernel<F>, dim3((unsigned)n_tiles), dim3(epa::kBlock), 0, st,
+                       reinterpret_cast<const C2<F>*>(x), workspace, reinterpret_cast<C2<F>*>(out));
+    return epa::check_launch("selftest_correlate_kernel");
+  });
 }
 
 extern "C" int epa_range_complex(const void* re, int in_dtype, const double* ccoef, int C, int P, int S, int B,
                                  void* range_out, int out_dtype, epa_stream_t stream) {
   EPA_CHECK_ARG(re && ccoef && range_out, "epa_range_complex: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0 && B > 0, "epa_range_complex: C=%d P=%d S=%d B=%d", C, P, S, B);
-  EPA_CHECK_ARG((in_dtype == EPA_F32 || in_dtype == EPA_F64) && (out_dtype == EPA_F32 || out_dtype == EPA_F64),
-                "epa_range_complex: bad dtype in=%d out=%d", in_dtype, out_dtype);
+  EPA_CHECK_ARG(epa::is_real(in_dtype) && epa::is_real(out_dtype), "epa_range_complex: bad dtype in=%d out=%d", in_dtype,
+                out_dtype);
   const long long rows = (long long)C * P;
   const int chunks = (S + epa::kBlock - 1) / epa::kBlock;
   long long gx = 16384 / chunks;
@@ -792,15 +791,15 @@ extern "C" int epa_range_complex(const void* re, int in_dtype, const double* cco
   if (gx > rows) gx = rows;
   const dim3 grid((unsigned)gx, (unsigned)chunks);
   hipStream_t st = (hipStream_t)stream;
-#define EPA_RC(IN, OUT)                                                                                          \
-  hipLaunchKernelGGL((range_complex_kernel<IN, OUT>), grid, dim3(epa::kBlock), 0, st, (const IN*)re, ccoef, rows, S, B, \
-                     (OUT*)range_out)
-  if (in_dtype == EPA_F32 && out_dtype == EPA_F64) EPA_RC(float, double);
-  else if (in_dtype == EPA_F32) EPA_RC(float, float);
-  else if (out_dtype == EPA_F64) EPA_RC(double, double);
-  else EPA_RC(double, float);
-#undef EPA_RC
-  return epa::check_launch("range_complex_kernel");
+  return epa::dispatch_real("epa_range_complex", in_dtype, [&](auto in) {
+    return epa::dispatch_real("epa_range_complex", out_dtype, [&](auto out) {
+      using InT = typename decltype(in)::type;
+      using T = typename decltype(out)::type;
+      hipLaunchKernelGGL((range_complex_kernel<InT, T>), grid, dim3(epa::kBlock), 0, st, (const InT*)re, ccoef, rows, S, B,
+                         (T*)range_out);
+      return epa::check_launch("range_complex_kernel");
+    });
+  });
 }
 
 static int sv_complex_fft_entry(const void* re, const void* im, int in_dtype, const float* replica,
@@ -838,8 +837,7 @@ static int sv_complex_fft_entry(const void* re, const void* im, int in_dtype, co
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0 && B > 0, "epa_sv_complex_fft: C=%d P=%d S=%d B=%d", C, P, S, B);
   EPA_CHECK_ARG(B <= kMaxBeams, "epa_sv_complex_fft: at most %d sectors supported (got %d)", kMaxBeams, B);
   EPA_CHECK_ARG(cal_type == EPA_CAL_SV || cal_type == EPA_CAL_TS, "epa_sv_complex_fft: bad cal_type");
-  EPA_CHECK_ARG((in_dtype == EPA_F32 || in_dtype == EPA_F64) && (out_dtype == EPA_F32 || out_dtype == EPA_F64) &&
-                    (fft_dtype == EPA_F32 || fft_dtype == EPA_F64),
+  EPA_CHECK_ARG(epa::is_real(in_dtype) && epa::is_real(out_dtype) && epa::is_real(fft_dtype),
                 "epa_sv_complex_fft: bad dtype in=%d out=%d fft=%d", in_dtype, out_dtype, fft_dtype);
   if (max_taps < 1 || max_taps > kN / 2) {
     epa::set_error("epa_sv_complex_fft: replicas of 1..%d taps only (got %d); use epa_sv_complex", kN / 2, max_taps);
@@ -875,20 +873,14 @@ static int sv_complex_fft_entry(const void* re, const void* im, int in_dtype, co
       if (int rc2 = epa::check_launch("tvg_table_kernel")) return rc2;
     }
   }
-  int rc;
-#define EPA_FFT_CASE(IN, OUT, FF) rc = launch_fft<IN, OUT, FF>(a, st)
-  const int key = (in_dtype == EPA_F64 ? 4 : 0) | (out_dtype == EPA_F64 ? 2 : 0) | (fft_dtype == EPA_F64 ? 1 : 0);
-  switch (key) {
-    case 0: EPA_FFT_CASE(float, float, float); break;
-    case 1: EPA_FFT_CASE(float, float, double); break;
-    case 2: EPA_FFT_CASE(float, double, float); break;
-    case 3: EPA_FFT_CASE(float, double, double); break;
-    case 4: EPA_FFT_CASE(double, float, float); break;
-    case 5: EPA_FFT_CASE(double, float, double); break;
-    case 6: EPA_FFT_CASE(double, double, float); break;
-    default: EPA_FFT_CASE(double, double, double); break;
-  }
-#undef EPA_FFT_CASE
+  const char* who = "epa_sv_complex_fft";
+  const int rc = epa::dispatch_real(who, in_dtype, [&](auto in) {
+    return epa::dispatch_real(who, out_dtype, [&](auto out) {
+      return epa::dispatch_real(who, fft_dtype, [&](auto fft) {
+        return launch_fft<typename decltype(in)::type, typename decltype(out)::type, typename decltype(fft)::type>(a, st);
+      });
+    });
+  });
   if (rc) return rc;
   if (range_stats_out) return epa_minmax_final(a.stats_part, kStatSlots, range_stats_out, st);
   return EPA_OK;

@@ -34,6 +34,37 @@ void set_error(const char* fmt, ...);
     }                                                                                    \
   } while (0)
 
+// ---- element type of the samples (EPA_F32 / EPA_F64), chosen in ONE place ------------------------------------------
+// Kernels are templates on the sample type; an entry instantiates both from one body:
+//   return epa::dispatch_real(who, dtype, [&](auto tag) {
+//     using T = typename decltype(tag)::type;
+//     kernel<T><<<grid, block, 0, st>>>((const T*)x, (T)threshold, ...);
+//     return epa::check_launch("kernel");
+//   });
+template <typename T>
+struct type_tag {
+  using type = T;
+};
+
+// the way back, for a template that calls a C-ABI entry
+template <typename T>
+constexpr int dtype_of = sizeof(T) == 8 ? EPA_F64 : EPA_F32;
+
+inline bool is_real(int dtype) { return dtype == EPA_F32 || dtype == EPA_F64; }
+
+// the argument check, at the place it has among an entry's other checks ("<entry>: bad dtype %d")
+#define EPA_CHECK_REAL(who, dtype) EPA_CHECK_ARG(::epa::is_real(dtype), "%s: bad dtype %d", who, dtype)
+#define EPA_CHECK_REAL_OUT(who, dtype) EPA_CHECK_ARG(::epa::is_real(dtype), "%s: bad output dtype %d", who, dtype)
+
+// f(type_tag<double>{}) or f(type_tag<float>{}); any other dtype is an error, never a silent default
+template <typename F>
+int dispatch_real(const char* who, int dtype, F&& f) {
+  if (dtype == EPA_F64) return f(type_tag<double>{});
+  if (dtype == EPA_F32) return f(type_tag<float>{});
+  set_error("%s: bad dtype %d", who, dtype);
+  return EPA_EINVAL;
+}
+
 // Launch trace (epa_launch_trace in echopype_amd.h): while it is on, every kernel launch notes its name -- the tests
 // assert WHICH kernel served a call (a specialised kernel silently declining a shape otherwise passes every
 // "fast == generic" comparison as generic == generic).

@@ -957,11 +957,10 @@ int epa_mvbs_rows_fast_path(const void* sv, const double* coef, int C, int P, in
   a.fill_value = fill_value;
   a.skipna = 1;
   a.cnt_off = cnt_off;
-  if (dtype == EPA_F64)
-    return epa_fused::launch_sv_rows<double>(a, sv, coef, bin_start, mvbs_out, sum_out, cnt_out, C, lds_bytes,
-                                             as_stored != 0, st);
-  return epa_fused::launch_sv_rows<float>(a, sv, coef, bin_start, mvbs_out, sum_out, cnt_out, C, lds_bytes,
-                                          as_stored != 0, st);
+  return epa::dispatch_real("epa_mvbs_rows_fast_path", dtype, [&](auto tag) {
+    return epa_fused::launch_sv_rows<typename decltype(tag)::type>(a, sv, coef, bin_start, mvbs_out, sum_out, cnt_out, C,
+                                                                   lds_bytes, as_stored != 0, st);
+  });
 }
 
 extern "C" int epa_selftest_lin_from_db(const double* u, double* out, size_t n, epa_stream_t stream) {
@@ -1012,14 +1011,12 @@ int epa_fused_fast_path(const void* raw, int raw_is_i16, const int32_t* n_valid,
   a.skipna = (bin_flags & EPA_BIN_SKIPNA) != 0;
   a.closed_right = (bin_flags & EPA_BIN_CLOSED_RIGHT) != 0;
   a.cnt_off = cnt_off;
-#define EPA_GO(T, RawT)                                                                           \
-  return epa_fused::launch<T, RawT>(a, reinterpret_cast<const RawT*>(raw), n_valid, coef, bin_start, \
-                                    sv_out, mvbs_out, sum_out, cnt_out, C, lds_bytes, st)
-  if (raw_is_i16) {
-    if (dtype == EPA_F64) EPA_GO(double, int16_t);
-    EPA_GO(float, int16_t);
-  }
-  if (dtype == EPA_F64) EPA_GO(double, float);
-  EPA_GO(float, float);
-#undef EPA_GO
+  return epa::dispatch_real("epa_fused_fast_path", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (raw_is_i16)
+      return epa_fused::launch<T, int16_t>(a, reinterpret_cast<const int16_t*>(raw), n_valid, coef, bin_start, sv_out,
+                                           mvbs_out, sum_out, cnt_out, C, lds_bytes, st);
+    return epa_fused::launch<T, float>(a, reinterpret_cast<const float*>(raw), n_valid, coef, bin_start, sv_out, mvbs_out,
+                                       sum_out, cnt_out, C, lds_bytes, st);
+  });
 }

@@ -327,12 +327,13 @@ extern "C" int epa_freq_diff_mask(const void* sv, int C, size_t n, int chan_a, i
   EPA_CHECK_ARG(C > 0 && chan_a >= 0 && chan_a < C && chan_b >= 0 && chan_b < C,
                 "epa_freq_diff_mask: channels %d and %d are not both in 0 .. %d", chan_a, chan_b, C - 1);
   EPA_CHECK_ARG(cmp >= EPA_CMP_GT && cmp <= EPA_CMP_EQ, "epa_freq_diff_mask: bad comparison %d", cmp);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_freq_diff_mask: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_freq_diff_mask", dtype);
   if (n == 0) return EPA_OK;
   static const unsigned kWant[5] = {kWantGT, kWantLT, kWantLT | kWantEQ, kWantGT | kWantEQ, kWantEQ};
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F64) return launch_freq_diff<double>(sv, n, chan_a, chan_b, kWant[cmp], diff, mask_out, st);
-  return launch_freq_diff<float>(sv, n, chan_a, chan_b, kWant[cmp], diff, mask_out, st);
+  return epa::dispatch_real("epa_freq_diff_mask", dtype, [&](auto tag) {
+    return launch_freq_diff<typename decltype(tag)::type>(sv, n, chan_a, chan_b, kWant[cmp], diff, mask_out, st);
+  });
 }
 
 extern "C" int epa_regrid_mask(const uint8_t* mask, const int32_t* group, int T, int P, int D, const double* range,

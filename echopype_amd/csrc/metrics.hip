@@ -279,7 +279,7 @@ int launch_metrics(const MetricsArgs& a, hipStream_t st) {
 extern "C" int epa_echo_metrics(const void* sv, const void* range, int range_per_row, long long R, long long S,
                                 const double* cm_in, void* abundance, void* center_of_mass, void* dispersion,
                                 void* evenness, void* aggregation, int dtype, int max_grid, epa_stream_t stream) {
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_echo_metrics: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_echo_metrics", dtype);
   EPA_CHECK_ARG(R >= 0 && S >= 0, "epa_echo_metrics: bad shape R=%lld S=%lld", R, S);
   EPA_CHECK_ARG(S <= (1LL << 40) && R <= (1LL << 40), "epa_echo_metrics: R=%lld S=%lld is too large", R, S);
   EPA_CHECK_ARG((sv && range) || R * S == 0, "epa_echo_metrics: NULL array argument");
@@ -296,5 +296,7 @@ extern "C" int epa_echo_metrics(const void* sv, const void* range, int range_per
   a.need = ((center_of_mass || (dispersion && !cm_in)) ? kNeedB : 0u) | ((evenness || aggregation) ? kNeedQ : 0u) |
            (dispersion ? kNeedI : 0u);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == EPA_F32 ? launch_metrics<float>(a, st) : launch_metrics<double>(a, st);
+  return epa::dispatch_real("epa_echo_metrics", dtype, [&](auto tag) {
+    return launch_metrics<typename decltype(tag)::type>(a, st);
+  });
 }

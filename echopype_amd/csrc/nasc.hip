@@ -208,7 +208,7 @@ extern "C" int epa_nasc(const void* sv, const void* depth, int C, int P, int S, 
   EPA_CHECK_ARG(sv && depth && bin_start && workspace && nasc_out, "epa_nasc: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0 && n_dbins > 0 && n_rbins > 0, "epa_nasc: sizes must be positive");
   EPA_CHECK_ARG(range_bin > 0, "epa_nasc: range_bin must be positive");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_nasc: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_nasc", dtype);
   EPA_CHECK_ARG(C <= 65535 && n_dbins <= 65535, "epa_nasc: more than 65535 channels / distance bins");
   const bool use_lds = epa::kMathTabBytes + (size_t)n_rbins * 24 <= 156 * 1024;
   const size_t lds = epa::kMathTabBytes + (use_lds ? (size_t)n_rbins * 24 : 0);
@@ -223,22 +223,19 @@ extern "C" int epa_nasc(const void* sv, const void* depth, int C, int P, int S, 
   if (nparts < 1) nparts = 1;
   const dim3 grid((unsigned)nparts, n_dbins, C);
   const int cr = (bin_flags & EPA_BIN_CLOSED_RIGHT) ? 1 : 0, skipna = (bin_flags & EPA_BIN_SKIPNA) ? 1 : 0;
-#define EPA_NASC(T)                                                                                   \
-  do {                                                                                                \
-    auto kern = use_lds ? nasc_accumulate_kernel<T, true> : nasc_accumulate_kernel<T, false>;         \
-    if (lds > 64 * 1024)                                                                              \
-      EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                          \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));       \
-    hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, (const T*)sv, (const T*)depth, P, S,         \
-                       bin_start, n_dbins, (int)nparts, range_bin, 1.0 / range_bin, n_rbins, cr,      \
-                       (Cell*)workspace);                                                             \
-    if (int rc = epa::check_launch("nasc_accumulate_kernel")) return rc;                              \
-    const size_t blocks = (n + kBlock - 1) / kBlock;                                                  \
-    hipLaunchKernelGGL(nasc_finalize_kernel<T>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)),      \
-                       dim3(kBlock), 0, st, (const Cell*)workspace, bin_start, n_dbins, n_rbins, n,   \
-                       skipna, (T*)nasc_out, (T*)sv_mean_out, (T*)h_mean_out);                        \
-  } while (0)
-  if (dtype == EPA_F64) EPA_NASC(double); else EPA_NASC(float);
-#undef EPA_NASC
-  return epa::check_launch("nasc_finalize_kernel");
+  return epa::dispatch_real("epa_nasc", dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    auto kern = use_lds ? nasc_accumulate_kernel<T, true> : nasc_accumulate_kernel<T, false>;
+    if (lds > 64 * 1024)
+      EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, (const T*)sv, (const T*)depth, P, S, bin_start, n_dbins,
+                       (int)nparts, range_bin, 1.0 / range_bin, n_rbins, cr, (Cell*)workspace);
+    if (int rc = epa::check_launch("nasc_accumulate_kernel")) return rc;
+    const size_t blocks = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(nasc_finalize_kernel<T>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, st,
+                       (const Cell*)workspace, bin_start, n_dbins, n_rbins, n, skipna, (T*)nasc_out, (T*)sv_mean_out,
+                       (T*)h_mean_out);
+    return epa::check_launch("nasc_finalize_kernel");
+  });
 }

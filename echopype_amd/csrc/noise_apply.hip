@@ -157,14 +157,11 @@ extern "C" int epa_noise_apply(const void* sv, const void* range, const double* 
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0 && ping_num > 0, "epa_noise_apply: sizes must be positive");
   EPA_CHECK_ARG(ping_phase >= 0 && ping_phase < ping_num, "epa_noise_apply: ping_phase %d not in [0, %d)", ping_phase,
                 ping_num);
-  if (dtype == EPA_F64)
-    return launch<double>(sv, range, coef, nullptr, alpha2, noise, C, P, S, ping_num, ping_phase, snr_threshold,
-                          sv_noise_out, sv_corrected_out, minmax_out, (hipStream_t)stream);
-  if (dtype == EPA_F32)
-    return launch<float>(sv, range, coef, nullptr, alpha2, noise, C, P, S, ping_num, ping_phase, snr_threshold,
-                         sv_noise_out, sv_corrected_out, minmax_out, (hipStream_t)stream);
-  epa::set_error("epa_noise_apply: bad dtype %d", dtype);
-  return EPA_EINVAL;
+  return epa::dispatch_real("epa_noise_apply", dtype, [&](auto tag) {
+    return launch<typename decltype(tag)::type>(sv, range, coef, nullptr, alpha2, noise, C, P, S, ping_num, ping_phase,
+                                                snr_threshold, sv_noise_out, sv_corrected_out, minmax_out,
+                                                (hipStream_t)stream);
+  });
 }
 
 extern "C" int epa_noise_apply_rows(const void* sv, const double* coef, const float* mask_raw, const double* alpha2,
@@ -176,12 +173,9 @@ extern "C" int epa_noise_apply_rows(const void* sv, const double* coef, const fl
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0 && ping_num > 0, "epa_noise_apply_rows: sizes must be positive");
   EPA_CHECK_ARG(ping_phase >= 0 && ping_phase < ping_num, "epa_noise_apply_rows: ping_phase %d not in [0, %d)",
                 ping_phase, ping_num);
-  if (dtype == EPA_F64)
-    return launch<double>(sv, nullptr, coef, mask_raw, alpha2, noise, C, P, S, ping_num, ping_phase, snr_threshold,
-                          sv_noise_out, sv_corrected_out, minmax_out, (hipStream_t)stream);
-  if (dtype == EPA_F32)
-    return launch<float>(sv, nullptr, coef, mask_raw, alpha2, noise, C, P, S, ping_num, ping_phase, snr_threshold,
-                         sv_noise_out, sv_corrected_out, minmax_out, (hipStream_t)stream);
-  epa::set_error("epa_noise_apply_rows: bad dtype %d", dtype);
-  return EPA_EINVAL;
+  return epa::dispatch_real("epa_noise_apply_rows", dtype, [&](auto tag) {
+    return launch<typename decltype(tag)::type>(sv, nullptr, coef, mask_raw, alpha2, noise, C, P, S, ping_num,
+                                                ping_phase, snr_threshold, sv_noise_out, sv_corrected_out, minmax_out,
+                                                (hipStream_t)stream);
+  });
 }

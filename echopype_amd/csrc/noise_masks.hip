@@ -3216,7 +3216,7 @@ extern "C" int epa_range_bin_smooth(const void* sv, const void* range, int C, in
                                     epa_stream_t stream) {
   EPA_CHECK_ARG(sv && up_out, "epa_range_bin_smooth: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_range_bin_smooth: sizes must be positive");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_range_bin_smooth: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_range_bin_smooth", dtype);
   double delta = 1.0;
   if (range) {
     EPA_CHECK_ARG(bin > 0 && nbins > 0 && r0 == r0, "epa_range_bin_smooth: bad bin grid");
@@ -3231,17 +3231,14 @@ extern "C" int epa_range_bin_smooth(const void* sv, const void* range, int C, in
   const size_t lds = epa::kMathTabBytes + (size_t)seg_bins * 12 + 8;
   const long long rows = (long long)C * P;
   hipStream_t st = (hipStream_t)stream;
-#define EPA_RBS(T, BV)                                                                            \
-  do {                                                                                            \
-    auto kern = range_bin_smooth_kernel<T, BV>;                                                   \
-    if (int rc = set_lds(kern, lds)) return rc;                                                   \
-    hipLaunchKernelGGL(kern, dim3(row_grid(rows)), dim3(kBlock), lds, st, (const T*)sv,           \
-                       (const T*)range, rows, S, nper, r0, delta, nbins, seg_bins, (T*)up_out);   \
-  } while (0)
-  if (dtype == EPA_F64) { if (range) EPA_RBS(double, true); else EPA_RBS(double, false); }
-  else { if (range) EPA_RBS(float, true); else EPA_RBS(float, false); }
-#undef EPA_RBS
-  return epa::check_launch("range_bin_smooth_kernel");
+  return epa::dispatch_real("epa_range_bin_smooth", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto kern = range ? range_bin_smooth_kernel<T, true> : range_bin_smooth_kernel<T, false>;
+    if (int rc = set_lds(kern, lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3(row_grid(rows)), dim3(kBlock), lds, st, (const T*)sv, (const T*)range, rows, S, nper,
+                       r0, delta, nbins, seg_bins, (T*)up_out);
+    return epa::check_launch("range_bin_smooth_kernel");
+  });
 }
 
 extern "C" int epa_impulse_mask(const void* up, int C, int P, int S, int num_side_pings,
@@ -3249,16 +3246,15 @@ extern "C" int epa_impulse_mask(const void* up, int C, int P, int S, int num_sid
   EPA_CHECK_ARG(up && mask_out, "epa_impulse_mask: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_impulse_mask: sizes must be positive");
   EPA_CHECK_ARG(num_side_pings >= 1, "epa_impulse_mask: num_side_pings must be >= 1");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_impulse_mask: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_impulse_mask", dtype);
   const long long rows = (long long)C * P;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(impulse_compare_kernel<double>, dim3(row_grid(rows)), dim3(kBlock), 0, st,
-                       (const double*)up, P, S, rows, num_side_pings, threshold, mask_out);
-  else
-    hipLaunchKernelGGL(impulse_compare_kernel<float>, dim3(row_grid(rows)), dim3(kBlock), 0, st,
-                       (const float*)up, P, S, rows, num_side_pings, (float)threshold, mask_out);
-  return epa::check_launch("impulse_compare_kernel");
+  return epa::dispatch_real("epa_impulse_mask", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(impulse_compare_kernel<T>, dim3(row_grid(rows)), dim3(kBlock), 0, st, (const T*)up, P, S, rows,
+                       num_side_pings, (T)threshold, mask_out);
+    return epa::check_launch("impulse_compare_kernel");
+  });
 }
 
 extern "C" int epa_pool_sv(const void* sv, int C, int P, int S, int first_sample, int num_side_pings,
@@ -3270,103 +3266,81 @@ extern "C" int epa_pool_sv(const void* sv, int C, int P, int S, int first_sample
   EPA_CHECK_ARG(first_sample >= 0 && num_side_pings >= 0 && num_side_samples >= 0,
                 "epa_pool_sv: negative window argument");
   EPA_CHECK_ARG(func == EPA_POOL_NANMEAN || func == EPA_POOL_NANMEDIAN, "epa_pool_sv: bad func %d", func);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_pool_sv: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_pool_sv", dtype);
   hipStream_t st = (hipStream_t)stream;
   const int s0 = first_sample < S ? first_sample : S;
   const int n = num_side_pings, m = num_side_samples;
-  if (func == EPA_POOL_NANMEDIAN) {
-    const size_t W = (size_t)(2 * n + 1) * (2 * m + 1);
-    const size_t slide_lds = med_slide_lds(W);
-    if (2 * m + 1 <= kBlock && W <= 65535 && slide_lds + sizeof(SelectScratchT<kMedCap>) + 512 <= kMaxLds) {
-      // the window carried from ping to ping: one workgroup per (channel, ping segment, column)
-      const int nseg = (P + kMedSeg - 1) / kMedSeg;
-      const long long jobs = (long long)C * nseg * S;
-      const int grid = (int)(jobs < (1 << 22) ? jobs : (1 << 22));
-#define EPA_MS(T)                                                                                          \
-  do {                                                                                                     \
-    MedSlideArgs<T> a{};                                                                                   \
-    a.sv = (const T*)sv; a.P = P; a.S = S; a.n = n; a.nseg = nseg; a.jobs = jobs; a.thr = (T)threshold;    \
-    a.pooled = (T*)pooled_out; a.mask = mask_out; a.cap = (int)W; a.s0 = s0; a.m = m;                      \
-    auto kern = pool_median_slide_kernel<T, false>;                                                        \
-    if (int rc = set_lds(kern, slide_lds)) return rc;                                                      \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), slide_lds, st, a);                                  \
-  } while (0)
-      if (dtype == EPA_F64) EPA_MS(double); else EPA_MS(float);
-#undef EPA_MS
-      return epa::check_launch("pool_median_slide_kernel");
+  return epa::dispatch_real("epa_pool_sv", dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    if (func == EPA_POOL_NANMEDIAN) {
+      const size_t W = (size_t)(2 * n + 1) * (2 * m + 1);
+      const size_t slide_lds = med_slide_lds(W);
+      if (2 * m + 1 <= kBlock && W <= 65535 && slide_lds + sizeof(SelectScratchT<kMedCap>) + 512 <= kMaxLds) {
+        // the window carried from ping to ping: one workgroup per (channel, ping segment, column)
+        const int nseg = (P + kMedSeg - 1) / kMedSeg;
+        const long long jobs = (long long)C * nseg * S;
+        const int grid = (int)(jobs < (1 << 22) ? jobs : (1 << 22));
+        MedSlideArgs<T> a{};
+        a.sv = (const T*)sv; a.P = P; a.S = S; a.n = n; a.nseg = nseg; a.jobs = jobs; a.thr = (T)threshold;
+        a.pooled = (T*)pooled_out; a.mask = mask_out; a.cap = (int)W; a.s0 = s0; a.m = m;
+        auto kern = pool_median_slide_kernel<T, false>;
+        if (int rc = set_lds(kern, slide_lds)) return rc;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), slide_lds, st, a);
+        return epa::check_launch("pool_median_slide_kernel");
+      }
+      const long long jobs = (long long)C * P * S;
+      const int grid = (int)(jobs < (1 << 20) ? jobs : (1 << 20));
+      hipLaunchKernelGGL(pool_median_kernel<T>, dim3(grid), dim3(kBlock), 0, st, (const T*)sv, P, S, jobs, s0, n, m,
+                         (T)threshold, (T*)pooled_out, mask_out);
+      return epa::check_launch("pool_median_kernel");
     }
-    const long long jobs = (long long)C * P * S;
-    const int grid = (int)(jobs < (1 << 20) ? jobs : (1 << 20));
-    if (dtype == EPA_F64)
-      hipLaunchKernelGGL(pool_median_kernel<double>, dim3(grid), dim3(kBlock), 0, st, (const double*)sv,
-                         P, S, jobs, s0, n, m, threshold, (double*)pooled_out, mask_out);
-    else
-      hipLaunchKernelGGL(pool_median_kernel<float>, dim3(grid), dim3(kBlock), 0, st, (const float*)sv,
-                         P, S, jobs, s0, n, m, (float)threshold, (float*)pooled_out, mask_out);
-    return epa::check_launch("pool_median_kernel");
-  }
-  EPA_CHECK_ARG(ws_sum && ws_cnt, "epa_pool_sv: nanmean needs the f64 / int32 [C*P*S] workspaces");
-  const size_t nin = (size_t)kRangeTile + 2 * m;
-  const size_t lds1 = epa::kMathTabBytes + (nin + 2) * 8 + (nin / kGroup + 1) * 12;
-  if (lds1 > kMaxLds) {
-    epa::set_error("epa_pool_sv: window %d x %d exceeds the LDS budget", 2 * n + 1, 2 * m + 1);
-    return EPA_EUNSUPPORTED;
-  }
-  const long long rows = (long long)C * P;
-  const int w = 2 * m + 1;
-  if (s0 < S && w >= kScanMinW && w <= kScanMaxW) {
-    const size_t ninp = (size_t)((kScanTile + 2 * m + 2) & ~1);
-    const size_t lds = epa::kMathTabBytes + (2 * ninp + 2 * kBlock) * 8 + (2 * ninp + 2 * kBlock) * 2;
-    const dim3 g1(row_grid(rows) < 16384 ? row_grid(rows) : 16384, (S - s0 + kScanTile - 1) / kScanTile);
-#define EPA_BR(T)                                                                                   \
-  do {                                                                                              \
-    auto kern = box_range_scan_kernel<T>;                                                           \
-    if (int rc = set_lds(kern, lds)) return rc;                                                     \
-    hipLaunchKernelGGL(kern, g1, dim3(kBlock), lds, st, (const T*)sv, rows, S, s0, m, ws_sum, ws_cnt); \
-  } while (0)
-    if (dtype == EPA_F64) EPA_BR(double); else EPA_BR(float);
-#undef EPA_BR
-    if (int rc = epa::check_launch("box_range_scan_kernel")) return rc;
-  } else if (s0 < S) {
-    const dim3 g1(row_grid(rows) < 16384 ? row_grid(rows) : 16384, (S - s0 + kRangeTile - 1) / kRangeTile);
-#define EPA_BR(T)                                                                                   \
-  do {                                                                                              \
-    auto kern = box_range_kernel<T>;                                                                \
-    if (int rc = set_lds(kern, lds1)) return rc;                                                    \
-    hipLaunchKernelGGL(kern, g1, dim3(kBlock), lds1, st, (const T*)sv, rows, S, s0, m, ws_sum, ws_cnt); \
-  } while (0)
-    if (dtype == EPA_F64) EPA_BR(double); else EPA_BR(float);
-#undef EPA_BR
-    if (int rc = epa::check_launch("box_range_kernel")) return rc;
-  }
-  // ping pass: grid = (ping segments, column stripes, channels)
-  const dim3 g2((P + kSlideSeg - 1) / kSlideSeg, (S + kBlock - 1) / kBlock, C);
-  EPA_CHECK_ARG(g2.y <= 65535u && g2.z <= 65535u, "epa_pool_sv: more than 65535 channels or 16.7 M samples per ping");
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(box_ping_slide_kernel<double>, g2, dim3(kBlock), epa::kMathTabBytes + kSlidePad, st,
-                       (const double*)sv, ws_sum, ws_cnt, P, S, s0, n, threshold, (double*)pooled_out, mask_out);
-  else
-    hipLaunchKernelGGL(box_ping_slide_kernel<float>, g2, dim3(kBlock), epa::kMathTabBytes + kSlidePad, st,
-                       (const float*)sv, ws_sum, ws_cnt, P, S, s0, n, (float)threshold, (float*)pooled_out,
-                       mask_out);
-  return epa::check_launch("box_ping_slide_kernel");
+    EPA_CHECK_ARG(ws_sum && ws_cnt, "epa_pool_sv: nanmean needs the f64 / int32 [C*P*S] workspaces");
+    const size_t nin = (size_t)kRangeTile + 2 * m;
+    const size_t lds1 = epa::kMathTabBytes + (nin + 2) * 8 + (nin / kGroup + 1) * 12;
+    if (lds1 > kMaxLds) {
+      epa::set_error("epa_pool_sv: window %d x %d exceeds the LDS budget", 2 * n + 1, 2 * m + 1);
+      return EPA_EUNSUPPORTED;
+    }
+    const long long rows = (long long)C * P;
+    const int w = 2 * m + 1;
+    if (s0 < S && w >= kScanMinW && w <= kScanMaxW) {
+      const size_t ninp = (size_t)((kScanTile + 2 * m + 2) & ~1);
+      const size_t lds = epa::kMathTabBytes + (2 * ninp + 2 * kBlock) * 8 + (2 * ninp + 2 * kBlock) * 2;
+      const dim3 g1(row_grid(rows) < 16384 ? row_grid(rows) : 16384, (S - s0 + kScanTile - 1) / kScanTile);
+      auto kern = box_range_scan_kernel<T>;
+      if (int rc = set_lds(kern, lds)) return rc;
+      hipLaunchKernelGGL(kern, g1, dim3(kBlock), lds, st, (const T*)sv, rows, S, s0, m, ws_sum, ws_cnt);
+      if (int rc = epa::check_launch("box_range_scan_kernel")) return rc;
+    } else if (s0 < S) {
+      const dim3 g1(row_grid(rows) < 16384 ? row_grid(rows) : 16384, (S - s0 + kRangeTile - 1) / kRangeTile);
+      auto kern = box_range_kernel<T>;
+      if (int rc = set_lds(kern, lds1)) return rc;
+      hipLaunchKernelGGL(kern, g1, dim3(kBlock), lds1, st, (const T*)sv, rows, S, s0, m, ws_sum, ws_cnt);
+      if (int rc = epa::check_launch("box_range_kernel")) return rc;
+    }
+    // ping pass: grid = (ping segments, column stripes, channels)
+    const dim3 g2((P + kSlideSeg - 1) / kSlideSeg, (S + kBlock - 1) / kBlock, C);
+    EPA_CHECK_ARG(g2.y <= 65535u && g2.z <= 65535u, "epa_pool_sv: more than 65535 channels or 16.7 M samples per ping");
+    hipLaunchKernelGGL(box_ping_slide_kernel<T>, g2, dim3(kBlock), epa::kMathTabBytes + kSlidePad, st, (const T*)sv, ws_sum,
+                       ws_cnt, P, S, s0, n, (T)threshold, (T*)pooled_out, mask_out);
+    return epa::check_launch("box_ping_slide_kernel");
+  });
 }
 
 extern "C" int epa_range_rows_check(const void* range, int C, int P, int S, int dtype, int32_t* nvalid_out,
                                     int32_t* violations_out, epa_stream_t stream) {
   EPA_CHECK_ARG(range && nvalid_out && violations_out, "epa_range_rows_check: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_range_rows_check: sizes must be positive");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_range_rows_check: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_range_rows_check", dtype);
   hipStream_t st = (hipStream_t)stream;
   EPA_CHECK_HIP(hipMemsetAsync(violations_out, 0, sizeof(int32_t), st));
   const long long rows = (long long)C * P;
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(rows_check_kernel<double>, dim3(row_grid(rows)), dim3(kBlock), 0, st,
-                       (const double*)range, rows, S, nvalid_out, violations_out);
-  else
-    hipLaunchKernelGGL(rows_check_kernel<float>, dim3(row_grid(rows)), dim3(kBlock), 0, st,
-                       (const float*)range, rows, S, nvalid_out, violations_out);
-  return epa::check_launch("rows_check_kernel");
+  return epa::dispatch_real("epa_range_rows_check", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(rows_check_kernel<T>, dim3(row_grid(rows)), dim3(kBlock), 0, st, (const T*)range, rows, S,
+                       nvalid_out, violations_out);
+    return epa::check_launch("rows_check_kernel");
+  });
 }
 
 namespace {
@@ -3563,17 +3537,17 @@ extern "C" int epa_pool_sv_value(const void* sv, const void* range, const int32_
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_pool_sv_value: sizes must be positive");
   EPA_CHECK_ARG(num_side_pings >= 0, "epa_pool_sv_value: num_side_pings must be >= 0");
   EPA_CHECK_ARG(func == EPA_POOL_NANMEAN || func == EPA_POOL_NANMEDIAN, "epa_pool_sv_value: bad func %d", func);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_pool_sv_value: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_pool_sv_value", dtype);
   if (func == EPA_POOL_NANMEDIAN && num_side_pings > kMaxSidePings) {
     epa::set_error("epa_pool_sv_value: nanmedian supports at most %d side pings", kMaxSidePings);
     return EPA_EUNSUPPORTED;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F64)
-    return launch_pool_value<double>(sv, range, nvalid, C, P, S, depth_bin, num_side_pings, exclude_above,
-                                     range_min, range_max, func, threshold, pooled_out, mask_out, ws, st);
-  return launch_pool_value<float>(sv, range, nvalid, C, P, S, depth_bin, num_side_pings, exclude_above,
-                                  range_min, range_max, func, threshold, pooled_out, mask_out, ws, st);
+  return epa::dispatch_real("epa_pool_sv_value", dtype, [&](auto tag) {
+    return launch_pool_value<typename decltype(tag)::type>(sv, range, nvalid, C, P, S, depth_bin, num_side_pings,
+                                                           exclude_above, range_min, range_max, func, threshold,
+                                                           pooled_out, mask_out, ws, st);
+  });
 }
 
 extern "C" int epa_attenuated_mask(const void* sv, const void* range, int C, int P, int S,
@@ -3582,7 +3556,7 @@ extern "C" int epa_attenuated_mask(const void* sv, const void* range, int C, int
   EPA_CHECK_ARG(sv && range && mask_out, "epa_attenuated_mask: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_attenuated_mask: sizes must be positive");
   EPA_CHECK_ARG(num_side_pings >= 0, "epa_attenuated_mask: num_side_pings must be >= 0");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_attenuated_mask: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_attenuated_mask", dtype);
   hipStream_t st = (hipStream_t)stream;
   if (num_side_pings >= 1 && S >= 16 && S % 4 == 0 && (reinterpret_cast<uintptr_t>(mask_out) & 3u) == 0) {
     // block medians carried from ping to ping: layer limits and own median of every ping first (stashed in the mask
@@ -3608,28 +3582,24 @@ extern "C" int epa_attenuated_mask(const void* sv, const void* range, int C, int
     const int ring_cap = 20480;  // u16 bins: 2 n x layer length up to this, longer blocks take both medians from memory
     const size_t wl = epa::kMathTabBytes + (size_t)(kMedBins + kMedCoarse + 4 + 8) * 4 + 2 * kMedSel * 2 + (size_t)ring_cap * 2;
     const dim3 grid((unsigned)((long long)C * nchunks));
-#define EPA_AW(T)                                                                                                     \
-  do {                                                                                                                \
-    hipLaunchKernelGGL(attenuated_prepare_kernel<T>, dim3(row_grid(rows)), dim3(kBlock), 0, st, (const T*)sv,         \
-                       (const T*)range, P, S, rows, (T)upper_limit, (T)lower_limit, num_side_pings, mask_out);        \
-    if (int rc = epa::check_launch("attenuated_prepare_kernel")) return rc;                                           \
-    hipLaunchKernelGGL(attenuated_walk_kernel<T>, grid, dim3(kBlock), wl, st, (const T*)sv, P, S, nchunks, chunk_len, \
-                       num_side_pings, (T)threshold, ring_cap, mask_out);                                             \
-  } while (0)
-    if (dtype == EPA_F64) EPA_AW(double); else EPA_AW(float);
-#undef EPA_AW
-    return epa::check_launch("attenuated_walk_kernel");
+    return epa::dispatch_real("epa_attenuated_mask", dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(attenuated_prepare_kernel<T>, dim3(row_grid(rows)), dim3(kBlock), 0, st, (const T*)sv,
+                         (const T*)range, P, S, rows, (T)upper_limit, (T)lower_limit, num_side_pings, mask_out);
+      if (int rc = epa::check_launch("attenuated_prepare_kernel")) return rc;
+      hipLaunchKernelGGL(attenuated_walk_kernel<T>, grid, dim3(kBlock), wl, st, (const T*)sv, P, S, nchunks, chunk_len,
+                         num_side_pings, (T)threshold, ring_cap, mask_out);
+      return epa::check_launch("attenuated_walk_kernel");
+    });
   }
   const long long rows = (long long)C * P;
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(attenuated_mask_kernel<double>, dim3(row_grid(rows)), dim3(kBlock), 0, st,
-                       (const double*)sv, (const double*)range, P, S, rows, upper_limit, lower_limit,
-                       num_side_pings, threshold, mask_out);
-  else
-    hipLaunchKernelGGL(attenuated_mask_kernel<float>, dim3(row_grid(rows)), dim3(kBlock), 0, st,
-                       (const float*)sv, (const float*)range, P, S, rows, (float)upper_limit,
-                       (float)lower_limit, num_side_pings, (float)threshold, mask_out);
-  return epa::check_launch("attenuated_mask_kernel");
+  return epa::dispatch_real("epa_attenuated_mask", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(attenuated_mask_kernel<T>, dim3(row_grid(rows)), dim3(kBlock), 0, st, (const T*)sv,
+                       (const T*)range, P, S, rows, (T)upper_limit, (T)lower_limit, num_side_pings, (T)threshold,
+                       mask_out);
+    return epa::check_launch("attenuated_mask_kernel");
+  });
 }
 
 extern "C" int epa_apply_mask(const void* src, const uint8_t* mask, size_t n, size_t mask_period,
@@ -3639,20 +3609,17 @@ extern "C" int epa_apply_mask(const void* src, const uint8_t* mask, size_t n, si
   EPA_CHECK_ARG(mask_period > 0 && n % mask_period == 0, "epa_apply_mask: mask does not tile the source");
   EPA_CHECK_ARG(!fill_array || (fill_period > 0 && n % fill_period == 0),
                 "epa_apply_mask: fill array does not tile the source");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_apply_mask: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_apply_mask", dtype);
   if (n == 0) return EPA_OK;
   const size_t blocks = (n + kBlock - 1) / kBlock;
   const int grid = (int)(blocks < 65536 ? blocks : 65536);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(apply_mask_kernel<double>, dim3(grid), dim3(kBlock), 0, st, (const double*)src,
-                       mask, n, mask_period, fill_value, (const double*)fill_array,
-                       fill_array ? fill_period : 1, (double*)out);
-  else
-    hipLaunchKernelGGL(apply_mask_kernel<float>, dim3(grid), dim3(kBlock), 0, st, (const float*)src, mask,
-                       n, mask_period, (float)fill_value, (const float*)fill_array,
-                       fill_array ? fill_period : 1, (float*)out);
-  return epa::check_launch("apply_mask_kernel");
+  return epa::dispatch_real("epa_apply_mask", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(apply_mask_kernel<T>, dim3(grid), dim3(kBlock), 0, st, (const T*)src, mask, n, mask_period,
+                       (T)fill_value, (const T*)fill_array, fill_array ? fill_period : 1, (T*)out);
+    return epa::check_launch("apply_mask_kernel");
+  });
 }
 
 extern "C" int epa_apply_masks(const void* src, const uint8_t* const* masks, const size_t* mask_periods, int n_masks,
@@ -3670,20 +3637,20 @@ extern "C" int epa_apply_masks(const void* src, const uint8_t* const* masks, con
   }
   EPA_CHECK_ARG(!fill_array || (fill_period > 0 && n % fill_period == 0),
                 "epa_apply_masks: fill array does not tile the source");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_apply_masks: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_apply_masks", dtype);
   EPA_CHECK_ARG(!minmax_out || workspace, "epa_apply_masks: minmax_out needs the workspace");
   if (n == 0) return EPA_OK;
   const size_t blocks = (n + kBlock - 1) / kBlock;
   const int grid = (int)(blocks < EPA_APPLY_MASKS_WS_DOUBLES / 2 ? blocks : EPA_APPLY_MASKS_WS_DOUBLES / 2);
   hipStream_t st = (hipStream_t)stream;
   double* part = minmax_out ? workspace : nullptr;
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(apply_masks_kernel<double>, dim3(grid), dim3(kBlock), 0, st, (const double*)src, ms, n,
-                       fill_value, (const double*)fill_array, fill_array ? fill_period : 1, (double*)out, part);
-  else
-    hipLaunchKernelGGL(apply_masks_kernel<float>, dim3(grid), dim3(kBlock), 0, st, (const float*)src, ms, n,
-                       (float)fill_value, (const float*)fill_array, fill_array ? fill_period : 1, (float*)out, part);
-  if (int rc = epa::check_launch("apply_masks_kernel")) return rc;
+  const int rc = epa::dispatch_real("epa_apply_masks", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(apply_masks_kernel<T>, dim3(grid), dim3(kBlock), 0, st, (const T*)src, ms, n, (T)fill_value,
+                       (const T*)fill_array, fill_array ? fill_period : 1, (T*)out, part);
+    return epa::check_launch("apply_masks_kernel");
+  });
+  if (rc) return rc;
   if (minmax_out) {
     hipLaunchKernelGGL(minmax_pairs_kernel, dim3(1), dim3(kBlock), 0, st, part, grid, minmax_out);
     return epa::check_launch("minmax_pairs_kernel");

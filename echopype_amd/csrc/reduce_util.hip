@@ -352,20 +352,24 @@ int epa_rows_piece_launch(const float* mask_raw, const void* x, const double* co
     hipLaunchKernelGGL(piece_slots_init_kernel, dim3(1), dim3(kPieceSlots), 0, st, workspace);
     if (int rc = epa::check_launch("piece_slots_init_kernel")) return rc;
   }
-#define EPA_RP(T, D, M, SRC, ST)                                                                                   \
+  // D: depth (scale and offset) or range; M, SRC: rows masked by mask_raw, range read from x; ST: statistics
+#define EPA_RP(D, M, SRC, ST)                                                                                      \
   hipLaunchKernelGGL((rows_piece_kernel<T, D, M, SRC, ST>), dim3((unsigned)pieces), dim3(epa::kBlock), 0, st,      \
                      mask_raw, (const T*)x, cf, scale, offset, S, chunks, pieces, (T*)out, xm, workspace)
-#define EPA_RP4(T, D)                                                                                              \
+#define EPA_RP4(D)                                                                                                 \
   do {                                                                                                             \
-    if (x) { if (stats) EPA_RP(T, D, false, 1, true); else EPA_RP(T, D, false, 1, false); }                        \
-    else if (mask_raw) { if (stats) EPA_RP(T, D, true, 0, true); else EPA_RP(T, D, true, 0, false); }              \
-    else { if (stats) EPA_RP(T, D, false, 0, true); else EPA_RP(T, D, false, 0, false); }                          \
+    if (x) { if (stats) EPA_RP(D, false, 1, true); else EPA_RP(D, false, 1, false); }                              \
+    else if (mask_raw) { if (stats) EPA_RP(D, true, 0, true); else EPA_RP(D, true, 0, false); }                    \
+    else { if (stats) EPA_RP(D, false, 0, true); else EPA_RP(D, false, 0, false); }                                \
   } while (0)
-  if (dtype == EPA_F64) { if (scale) EPA_RP4(double, 1); else EPA_RP4(double, 0); }
-  else { if (scale) EPA_RP4(float, 1); else EPA_RP4(float, 0); }
+  const int rc = epa::dispatch_real("epa_rows_piece_launch", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (scale) EPA_RP4(1); else EPA_RP4(0);
+    return epa::check_launch("rows_piece_kernel");
+  });
 #undef EPA_RP4
 #undef EPA_RP
-  if (int rc = epa::check_launch("rows_piece_kernel")) return rc;
+  if (rc) return rc;
   if (stats) {
     hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(epa::kBlock), 0, st, workspace, kPieceSlots, stats_out,
                        kPieceSlotStride);
@@ -380,7 +384,7 @@ extern "C" int epa_depth_rows(const void* range, const double* coef, const float
   EPA_CHECK_ARG((range || coef) && scale && offset && out, "epa_depth_rows: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_depth_rows: sizes must be positive");
   EPA_CHECK_ARG(!stats_out || workspace, "epa_depth_rows: the statistics need the workspace");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_depth_rows: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_depth_rows", dtype);
   const long long rows = (long long)C * P;
   const int grid = (int)(rows < 16384 ? rows : 16384);
   hipStream_t st = (hipStream_t)stream;
@@ -391,13 +395,13 @@ extern "C" int epa_depth_rows(const void* range, const double* coef, const float
                                          stats_out, st);
     if (rc >= 0) return rc;
   }
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(depth_rows_kernel<double>, dim3(grid), dim3(epa::kBlock), 0, st, (const double*)range, cf,
-                       mask_raw, scale, offset, rows, S, (double*)out, part);
-  else
-    hipLaunchKernelGGL(depth_rows_kernel<float>, dim3(grid), dim3(epa::kBlock), 0, st, (const float*)range, cf,
-                       mask_raw, scale, offset, rows, S, (float*)out, part);
-  if (int rc = epa::check_launch("depth_rows_kernel")) return rc;
+  const int rc = epa::dispatch_real("epa_depth_rows", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(depth_rows_kernel<T>, dim3(grid), dim3(epa::kBlock), 0, st, (const T*)range, cf, mask_raw, scale,
+                       offset, rows, S, (T*)out, part);
+    return epa::check_launch("depth_rows_kernel");
+  });
+  if (rc) return rc;
   if (stats_out) return epa_minmax_final(workspace, grid, stats_out, st);
   return EPA_OK;
 }
@@ -409,17 +413,12 @@ extern "C" int epa_affine_rows(const void* x, const double* scale, const double*
   const long long rows = (long long)C * P;
   const int grid = (int)(rows < 16384 ? rows : 16384);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(affine_rows_kernel<double>, dim3(grid), dim3(epa::kBlock), 0, st,
-                       (const double*)x, scale, offset, rows, S, (double*)out);
-  else if (dtype == EPA_F32)
-    hipLaunchKernelGGL(affine_rows_kernel<float>, dim3(grid), dim3(epa::kBlock), 0, st,
-                       (const float*)x, scale, offset, rows, S, (float*)out);
-  else {
-    epa::set_error("epa_affine_rows: bad dtype %d", dtype);
-    return EPA_EINVAL;
-  }
-  return epa::check_launch("affine_rows_kernel");
+  return epa::dispatch_real("epa_affine_rows", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(affine_rows_kernel<T>, dim3(grid), dim3(epa::kBlock), 0, st, (const T*)x, scale, offset, rows, S,
+                       (T*)out);
+    return epa::check_launch("affine_rows_kernel");
+  });
 }
 
 // {min, max, NaN count} partials of another kernel (3 doubles per workgroup) -> out[3]; used by sv_power.hip
@@ -431,17 +430,16 @@ int epa_minmax_final(const double* part, int nparts, double* out, hipStream_t st
 extern "C" int epa_nanminmax(const void* x, size_t n, int dtype, double* workspace, double* out,
                              epa_stream_t stream) {
   EPA_CHECK_ARG(x && workspace && out, "epa_nanminmax: NULL array argument");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_nanminmax: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_nanminmax", dtype);
   const size_t blocks = (n + epa::kBlock - 1) / epa::kBlock;
   const int grid = (int)(blocks < 1024 ? (blocks ? blocks : 1) : 1024);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(minmax_partial_kernel<double>, dim3(grid), dim3(epa::kBlock), 0, st,
-                       (const double*)x, n, workspace);
-  else
-    hipLaunchKernelGGL(minmax_partial_kernel<float>, dim3(grid), dim3(epa::kBlock), 0, st,
-                       (const float*)x, n, workspace);
-  if (int rc = epa::check_launch("minmax_partial_kernel")) return rc;
+  const int rc = epa::dispatch_real("epa_nanminmax", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(minmax_partial_kernel<T>, dim3(grid), dim3(epa::kBlock), 0, st, (const T*)x, n, workspace);
+    return epa::check_launch("minmax_partial_kernel");
+  });
+  if (rc) return rc;
   hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(epa::kBlock), 0, st, workspace, grid, out);
   return epa::check_launch("minmax_final_kernel");
 }
@@ -450,17 +448,16 @@ extern "C" int epa_range_step_mean(const void* range, int C, int P, int S, int d
                                    double* out, epa_stream_t stream) {
   EPA_CHECK_ARG(range && workspace && out, "epa_range_step_mean: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_range_step_mean: sizes must be positive");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_range_step_mean: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_range_step_mean", dtype);
   const long long rows = (long long)C * P;
   const int grid = (int)(rows < 16384 ? rows : 16384);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(step_rows_kernel<double>, dim3(grid), dim3(epa::kBlock), 0, st,
-                       (const double*)range, rows, S, workspace);
-  else
-    hipLaunchKernelGGL(step_rows_kernel<float>, dim3(grid), dim3(epa::kBlock), 0, st, (const float*)range,
-                       rows, S, workspace);
-  if (int rc = epa::check_launch("step_rows_kernel")) return rc;
+  const int rc = epa::dispatch_real("epa_range_step_mean", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(step_rows_kernel<T>, dim3(grid), dim3(epa::kBlock), 0, st, (const T*)range, rows, S, workspace);
+    return epa::check_launch("step_rows_kernel");
+  });
+  if (rc) return rc;
   hipLaunchKernelGGL(step_final_kernel, dim3(C), dim3(epa::kBlock), 0, st, workspace, P, out);
   return epa::check_launch("step_final_kernel");
 }
@@ -468,18 +465,17 @@ extern "C" int epa_range_step_mean(const void* range, int C, int P, int S, int d
 extern "C" int epa_first_not_le(const void* x, size_t n, double limit, int dtype, uint64_t* out,
                                 epa_stream_t stream) {
   EPA_CHECK_ARG(x && out, "epa_first_not_le: NULL array argument");
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "epa_first_not_le: bad dtype %d", dtype);
+  EPA_CHECK_REAL("epa_first_not_le", dtype);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(set_u64_kernel, dim3(1), dim3(1), 0, st, (unsigned long long*)out,
                      (unsigned long long)n);
   if (n == 0) return epa::check_launch("set_u64_kernel");
   const size_t blocks = (n + epa::kBlock - 1) / epa::kBlock;
   const int grid = (int)(blocks < 4096 ? blocks : 4096);
-  if (dtype == EPA_F64)
-    hipLaunchKernelGGL(first_not_le_kernel<double>, dim3(grid), dim3(epa::kBlock), 0, st, (const double*)x,
-                       n, limit, (unsigned long long*)out);
-  else
-    hipLaunchKernelGGL(first_not_le_kernel<float>, dim3(grid), dim3(epa::kBlock), 0, st, (const float*)x, n,
-                       (float)limit, (unsigned long long*)out);
-  return epa::check_launch("first_not_le_kernel");
+  return epa::dispatch_real("epa_first_not_le", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(first_not_le_kernel<T>, dim3(grid), dim3(epa::kBlock), 0, st, (const T*)x, n, (T)limit,
+                       (unsigned long long*)out);
+    return epa::check_launch("first_not_le_kernel");
+  });
 }

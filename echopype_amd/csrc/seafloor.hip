@@ -372,13 +372,13 @@ extern "C" int epa_seafloor_depth_uniform(const void* depth, int dtype, long lon
   const char* who = "epa_seafloor_depth_uniform";
   EPA_CHECK_ARG(depth && bad_pings, "%s: NULL array argument", who);
   EPA_CHECK_ARG(P > 0 && S > 0, "%s: P=%lld S=%lld", who, P, S);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "%s: bad dtype %d", who, dtype);
+  EPA_CHECK_REAL(who, dtype);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F32)
-    sf_depth_uniform_kernel<float><<<blocks_for_rows(P), epa::kBlock, 0, st>>>((const float*)depth, P, S, bad_pings);
-  else
-    sf_depth_uniform_kernel<double><<<blocks_for_rows(P), epa::kBlock, 0, st>>>((const double*)depth, P, S, bad_pings);
-  return epa::check_launch("sf_depth_uniform_kernel");
+  return epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sf_depth_uniform_kernel<T><<<blocks_for_rows(P), epa::kBlock, 0, st>>>((const T*)depth, P, S, bad_pings);
+    return epa::check_launch("sf_depth_uniform_kernel");
+  });
 }
 
 extern "C" int epa_seafloor_basic(const void* sv, int dtype, long long P, long long S, long long skip, double tmin,
@@ -387,15 +387,14 @@ extern "C" int epa_seafloor_basic(const void* sv, int dtype, long long P, long l
   EPA_CHECK_ARG(sv && depth0 && out, "%s: NULL array argument", who);
   EPA_CHECK_ARG(P > 0 && S > 0, "%s: P=%lld S=%lld", who, P, S);
   EPA_CHECK_ARG(skip >= 0 && skip < S, "%s: bin_skip %lld outside [0, %lld)", who, skip, S);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "%s: bad dtype %d", who, dtype);
+  EPA_CHECK_REAL(who, dtype);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EPA_F32)
-    sf_basic_kernel<float><<<blocks_for_rows(P), epa::kBlock, 0, st>>>((const float*)sv, P, S, skip, (float)tmin,
-                                                                        (float)tmax, depth0, offset, out);
-  else
-    sf_basic_kernel<double><<<blocks_for_rows(P), epa::kBlock, 0, st>>>((const double*)sv, P, S, skip, tmin, tmax,
-                                                                         depth0, offset, out);
-  return epa::check_launch("sf_basic_kernel");
+  return epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sf_basic_kernel<T><<<blocks_for_rows(P), epa::kBlock, 0, st>>>((const T*)sv, P, S, skip, (T)tmin, (T)tmax, depth0,
+                                                                    offset, out);
+    return epa::check_launch("sf_basic_kernel");
+  });
 }
 
 extern "C" int epa_seafloor_angle_mask(const void* theta, const void* phi, int dtype, long long P, long long S,
@@ -406,18 +405,16 @@ extern "C" int epa_seafloor_angle_mask(const void* theta, const void* phi, int d
   EPA_CHECK_ARG(theta && phi && work && mask && state, "%s: NULL array argument", who);
   EPA_CHECK_ARG(P > 0 && R > 0 && r0 >= 0 && r0 + R <= S, "%s: P=%lld S=%lld crop [%lld, +%lld)", who, P, S, r0, R);
   EPA_CHECK_ARG(wtheta > 0 && wphi > 0, "%s: windows must be positive (%d, %d)", who, wtheta, wphi);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "%s: bad dtype %d", who, dtype);
+  EPA_CHECK_REAL(who, dtype);
   hipStream_t st = (hipStream_t)stream;
   const int nb = blocks_for(P * R);
-  if (dtype == EPA_F32)
-    sf_box_rows_kernel<float><<<nb, epa::kBlock, 0, st>>>((const float*)theta, (const float*)phi, P, S, r0, R, wtheta,
-                                                          wphi, work);
-  else
-    sf_box_rows_kernel<double><<<nb, epa::kBlock, 0, st>>>((const double*)theta, (const double*)phi, P, S, r0, R,
-                                                           wtheta, wphi, work);
-  if (int rc = epa::check_launch("sf_box_rows_kernel")) return rc;
-  sf_box_cols_kernel<<<nb, epa::kBlock, 0, st>>>(work, P, R, wtheta, wphi, ttheta, tphi, mask, state);
-  return epa::check_launch("sf_box_cols_kernel");
+  return epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sf_box_rows_kernel<T><<<nb, epa::kBlock, 0, st>>>((const T*)theta, (const T*)phi, P, S, r0, R, wtheta, wphi, work);
+    if (int rc = epa::check_launch("sf_box_rows_kernel")) return rc;
+    sf_box_cols_kernel<<<nb, epa::kBlock, 0, st>>>(work, P, R, wtheta, wphi, ttheta, tphi, mask, state);
+    return epa::check_launch("sf_box_cols_kernel");
+  });
 }
 
 extern "C" int epa_seafloor_median(const void* sv, int dtype, long long P, long long S, long long r0, long long R,
@@ -426,25 +423,20 @@ extern "C" int epa_seafloor_median(const void* sv, int dtype, long long P, long 
   const char* who = "epa_seafloor_median";
   EPA_CHECK_ARG(sv && mask && state && hist, "%s: NULL array argument", who);
   EPA_CHECK_ARG(P > 0 && R > 0 && r0 >= 0 && r0 + R <= S, "%s: P=%lld S=%lld crop [%lld, +%lld)", who, P, S, r0, R);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "%s: bad dtype %d", who, dtype);
+  EPA_CHECK_REAL(who, dtype);
   hipStream_t st = (hipStream_t)stream;
   const int nb = blocks_for(P * R);
-  const int bits = dtype == EPA_F32 ? 32 : 64;
-  for (int shift = bits - 8; shift >= 0; shift -= 8) {
-    EPA_CHECK_HIP(hipMemsetAsync(hist, 0, 512 * sizeof(unsigned long long), st));
-    if (dtype == EPA_F32)
-      sf_median_hist_kernel<float><<<nb, epa::kBlock, 0, st>>>((const float*)sv, P, S, r0, R, mask, shift, state, hist);
-    else
-      sf_median_hist_kernel<double><<<nb, epa::kBlock, 0, st>>>((const double*)sv, P, S, r0, R, mask, shift, state,
-                                                                hist);
-    if (int rc = epa::check_launch("sf_median_hist_kernel")) return rc;
-    if (dtype == EPA_F32)
-      sf_median_pick_kernel<float><<<1, 64, 0, st>>>(hist, shift, state);
-    else
-      sf_median_pick_kernel<double><<<1, 64, 0, st>>>(hist, shift, state);
-    if (int rc = epa::check_launch("sf_median_pick_kernel")) return rc;
-  }
-  return EPA_OK;
+  return epa::dispatch_real(who, dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    for (int shift = (int)sizeof(T) * 8 - 8; shift >= 0; shift -= 8) {
+      EPA_CHECK_HIP(hipMemsetAsync(hist, 0, 512 * sizeof(unsigned long long), st));
+      sf_median_hist_kernel<T><<<nb, epa::kBlock, 0, st>>>((const T*)sv, P, S, r0, R, mask, shift, state, hist);
+      if (int rc = epa::check_launch("sf_median_hist_kernel")) return rc;
+      sf_median_pick_kernel<T><<<1, 64, 0, st>>>(hist, shift, state);
+      if (int rc = epa::check_launch("sf_median_pick_kernel")) return rc;
+    }
+    return EPA_OK;
+  });
 }
 
 extern "C" int epa_seafloor_components(const void* sv, int dtype, long long P, long long S, long long r0, long long R,
@@ -453,15 +445,16 @@ extern "C" int epa_seafloor_components(const void* sv, int dtype, long long P, l
   const char* who = "epa_seafloor_components";
   EPA_CHECK_ARG(sv && mask && parent && state, "%s: NULL array argument", who);
   EPA_CHECK_ARG(P > 0 && R > 0 && r0 >= 0 && r0 + R <= S, "%s: P=%lld S=%lld crop [%lld, +%lld)", who, P, S, r0, R);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "%s: bad dtype %d", who, dtype);
+  EPA_CHECK_REAL(who, dtype);
   hipStream_t st = (hipStream_t)stream;
   const long long n = P * R;
   const int nb = blocks_for(n);
-  if (dtype == EPA_F32)
-    sf_cc_init_kernel<float><<<nb, epa::kBlock, 0, st>>>((const float*)sv, P, S, r0, R, (float)threshold, parent);
-  else
-    sf_cc_init_kernel<double><<<nb, epa::kBlock, 0, st>>>((const double*)sv, P, S, r0, R, threshold, parent);
-  if (int rc = epa::check_launch("sf_cc_init_kernel")) return rc;
+  const int rc = epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sf_cc_init_kernel<T><<<nb, epa::kBlock, 0, st>>>((const T*)sv, P, S, r0, R, (T)threshold, parent);
+    return epa::check_launch("sf_cc_init_kernel");
+  });
+  if (rc) return rc;
   sf_cc_merge_kernel<<<nb, epa::kBlock, 0, st>>>(parent, P, R, state + kError);
   if (int rc = epa::check_launch("sf_cc_merge_kernel")) return rc;
   sf_cc_compress_kernel<<<nb, epa::kBlock, 0, st>>>(parent, n, state + kError);
@@ -476,13 +469,11 @@ extern "C" int epa_seafloor_bottom(const long long* parent, const unsigned char*
   const char* who = "epa_seafloor_bottom";
   EPA_CHECK_ARG(depth0 && out && (!parent || mask), "%s: NULL array argument", who);
   EPA_CHECK_ARG(P > 0 && (!parent || (R > 0 && r0 >= 0)), "%s: P=%lld R=%lld r0=%lld", who, P, R, r0);
-  EPA_CHECK_ARG(out_dtype == EPA_F32 || out_dtype == EPA_F64, "%s: bad output dtype %d", who, out_dtype);
+  EPA_CHECK_REAL_OUT(who, out_dtype);
   hipStream_t st = (hipStream_t)stream;
-  if (out_dtype == EPA_F32)
-    sf_bottom_kernel<float><<<blocks_for_rows(P), epa::kBlock, 0, st>>>(parent, mask, P, R, r0, depth0, offset,
-                                                                        (float*)out);
-  else
-    sf_bottom_kernel<double><<<blocks_for_rows(P), epa::kBlock, 0, st>>>(parent, mask, P, R, r0, depth0, offset,
-                                                                         (double*)out);
-  return epa::check_launch("sf_bottom_kernel");
+  return epa::dispatch_real(who, out_dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sf_bottom_kernel<T><<<blocks_for_rows(P), epa::kBlock, 0, st>>>(parent, mask, P, R, r0, depth0, offset, (T*)out);
+    return epa::check_launch("sf_bottom_kernel");
+  });
 }

@@ -446,18 +446,17 @@ extern "C" int epa_shoal_threshold_fill(const void* sv, int dtype, long long P, 
   const char* who = "epa_shoal_threshold_fill";
   EPA_CHECK_ARG(sv && plane, "%s: NULL array argument", who);
   EPA_CHECK_ARG(P > 0 && S > 0 && P < 0x7fffffffLL && S < 0x7fffffffLL, "%s: P=%lld S=%lld", who, P, S);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "%s: bad dtype %d", who, dtype);
+  EPA_CHECK_REAL(who, dtype);
   hipStream_t st = (hipStream_t)stream;
   if (maxvgap < 0) maxvgap = 0;  // no run is shorter than one sample,
   if (maxvgap > S) maxvgap = S;  // none longer than the axis
   if (maxhgap > P) maxhgap = P;
-  if (dtype == EPA_F32)
-    sh_threshold_vfill_kernel<float><<<blocks_for_waves(P), epa::kBlock, 0, st>>>((const float*)sv, P, S, thr,
-                                                                                  maxvgap, plane);
-  else
-    sh_threshold_vfill_kernel<double><<<blocks_for_waves(P), epa::kBlock, 0, st>>>((const double*)sv, P, S, thr,
-                                                                                   maxvgap, plane);
-  if (int rc = epa::check_launch("sh_threshold_vfill_kernel")) return rc;
+  const int rc = epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sh_threshold_vfill_kernel<T><<<blocks_for_waves(P), epa::kBlock, 0, st>>>((const T*)sv, P, S, thr, maxvgap, plane);
+    return epa::check_launch("sh_threshold_vfill_kernel");
+  });
+  if (rc) return rc;
   if (maxhgap >= 1 && P > 2) {
     const long long chunks = (P + kHChunk - 1) / kHChunk;
     const dim3 grid((unsigned)((S + epa::kBlock - 1) / epa::kBlock), (unsigned)(chunks > 32768 ? 32768 : chunks));

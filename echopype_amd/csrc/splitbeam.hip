@@ -693,8 +693,8 @@ int complex_common(SbaArgs& a, const void* re, const void* im, int in_dtype, con
                    void* phi, int out_dtype, const char* who) {
   EPA_CHECK_ARG(re && im && theta && phi, "%s: NULL array argument", who);
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "%s: C=%d P=%d S=%d", who, C, P, S);
-  EPA_CHECK_ARG(in_dtype == EPA_F32 || in_dtype == EPA_F64, "%s: bad input dtype %d", who, in_dtype);
-  EPA_CHECK_ARG(out_dtype == EPA_F32 || out_dtype == EPA_F64, "%s: bad output dtype %d", who, out_dtype);
+  EPA_CHECK_ARG(epa::is_real(in_dtype), "%s: bad input dtype %d", who, in_dtype);
+  EPA_CHECK_REAL_OUT(who, out_dtype);
   EPA_CHECK_ARG((replica == nullptr) == (replica_off == nullptr),
                 "%s: replica and replica_off must both be given (pulse compression) or both NULL", who);
   EPA_CHECK_ARG(!replica || max_taps > 0, "%s: max_taps must be positive with a replica", who);
@@ -720,13 +720,15 @@ extern "C" int epa_splitbeam_power(const void* along, const void* athw, int in_d
   a.re = along; a.im = athw; a.C = C; a.P = P; a.S = S; a.B = 1;
   a.theta = theta; a.phi = phi;
   hipStream_t st = (hipStream_t)stream;
-  const bool o64 = out_dtype == EPA_F64;
-  EPA_CHECK_ARG(out_dtype == EPA_F32 || o64, "%s: bad output dtype %d", who, out_dtype);
-  if (in_dtype == EPA_I8) return o64 ? launch_power<int8_t, double>(a, st) : launch_power<int8_t, float>(a, st);
-  if (in_dtype == EPA_F32) return o64 ? launch_power<float, double>(a, st) : launch_power<float, float>(a, st);
-  if (in_dtype == EPA_F64) return o64 ? launch_power<double, double>(a, st) : launch_power<double, float>(a, st);
-  epa::set_error("%s: bad input dtype %d", who, in_dtype);
-  return EPA_EINVAL;
+  EPA_CHECK_REAL_OUT(who, out_dtype);
+  return epa::dispatch_real(who, out_dtype, [&](auto out) -> int {
+    using T = typename decltype(out)::type;
+    if (in_dtype == EPA_I8) return launch_power<int8_t, T>(a, st);
+    if (in_dtype == EPA_F32) return launch_power<float, T>(a, st);
+    if (in_dtype == EPA_F64) return launch_power<double, T>(a, st);
+    epa::set_error("%s: bad input dtype %d", who, in_dtype);
+    return EPA_EINVAL;
+  });
 }
 
 extern "C" int epa_splitbeam_complex(const void* re, const void* im, int in_dtype, const int32_t* beam_type_host,
@@ -734,19 +736,20 @@ extern "C" int epa_splitbeam_complex(const void* re, const void* im, int in_dtyp
                                      const int32_t* replica_off, const int32_t* replica_id, int n_replicas, int max_taps,
                                      int C, int P, int S, int B, void* theta, void* phi, int out_dtype,
                                      epa_stream_t stream) {
+  const char* who = "epa_splitbeam_complex";
   SbaArgs a{};
   if (int rc = complex_common(a, re, im, in_dtype, beam_type_host, params_host, modes_host, replica, replica_off,
-                              replica_id, n_replicas, max_taps, C, P, S, B, theta, phi, out_dtype,
-                              "epa_splitbeam_complex"))
+                              replica_id, n_replicas, max_taps, C, P, S, B, theta, phi, out_dtype, who))
     return rc;
   hipStream_t st = (hipStream_t)stream;
-  const bool i64 = in_dtype == EPA_F64, o64 = out_dtype == EPA_F64;
-  if (!replica) {
-    if (i64) return o64 ? launch_cw<double, double>(a, st) : launch_cw<double, float>(a, st);
-    return o64 ? launch_cw<float, double>(a, st) : launch_cw<float, float>(a, st);
-  }
-  if (i64) return o64 ? launch_direct<double, double>(a, max_taps, st) : launch_direct<double, float>(a, max_taps, st);
-  return o64 ? launch_direct<float, double>(a, max_taps, st) : launch_direct<float, float>(a, max_taps, st);
+  return epa::dispatch_real(who, in_dtype, [&](auto in) {
+    return epa::dispatch_real(who, out_dtype, [&](auto out) {
+      using InT = typename decltype(in)::type;
+      using T = typename decltype(out)::type;
+      if (!replica) return launch_cw<InT, T>(a, st);
+      return launch_direct<InT, T>(a, max_taps, st);
+    });
+  });
 }
 
 extern "C" int epa_splitbeam_complex_fft(const void* re, const void* im, int in_dtype, const int32_t* beam_type_host,
@@ -758,22 +761,19 @@ extern "C" int epa_splitbeam_complex_fft(const void* re, const void* im, int in_
   EPA_CHECK_ARG(replica && replica_off && workspace, "%s: replica, replica_off and workspace are needed", who);
   EPA_CHECK_ARG(max_taps >= 1 && max_taps <= kN / 2, "%s: the FFT form takes replicas of 1 .. %d taps (got %d)", who,
                 kN / 2, max_taps);
-  EPA_CHECK_ARG(fft_dtype == EPA_F32 || fft_dtype == EPA_F64, "%s: bad fft_dtype %d", who, fft_dtype);
+  EPA_CHECK_ARG(epa::is_real(fft_dtype), "%s: bad fft_dtype %d", who, fft_dtype);
   SbaArgs a{};
   if (int rc = complex_common(a, re, im, in_dtype, beam_type_host, params_host, modes_host, replica, replica_off,
                               replica_id, n_replicas, max_taps, C, P, S, B, theta, phi, out_dtype, who))
     return rc;
   const int n_rep = replica_id ? n_replicas : C;
   hipStream_t st = (hipStream_t)stream;
-  const bool i64 = in_dtype == EPA_F64, o64 = out_dtype == EPA_F64, f64 = fft_dtype == EPA_F64;
-#define EPA_SB_FFT(InT, T)                                                                                        \
-  return f64 ? launch_fft<InT, T, double>(a, replica, replica_off, n_rep, max_taps, workspace, st)                \
-             : launch_fft<InT, T, float>(a, replica, replica_off, n_rep, max_taps, workspace, st)
-  if (i64) {
-    if (o64) EPA_SB_FFT(double, double);
-    EPA_SB_FFT(double, float);
-  }
-  if (o64) EPA_SB_FFT(float, double);
-  EPA_SB_FFT(float, float);
-#undef EPA_SB_FFT
+  return epa::dispatch_real(who, in_dtype, [&](auto in) {
+    return epa::dispatch_real(who, out_dtype, [&](auto out) {
+      return epa::dispatch_real(who, fft_dtype, [&](auto fft) {
+        return launch_fft<typename decltype(in)::type, typename decltype(out)::type, typename decltype(fft)::type>(
+            a, replica, replica_off, n_rep, max_taps, workspace, st);
+      });
+    });
+  });
 }

@@ -445,7 +445,7 @@ int launch(const float* raw, const double* coef, int C, int P, int S, int cal_ty
 #undef EPA_LAUNCH
   if (int rc = epa::check_launch("sv_power_kernel")) return rc;
   if (stats_out)  // odd sizes / unaligned buffers: a separate sweep of the echo_range just written
-    return epa_nanminmax(range_out, (size_t)rows * S, sizeof(T) == 8 ? EPA_F64 : EPA_F32, part, stats_out,
+    return epa_nanminmax(range_out, (size_t)rows * S, epa::dtype_of<T>, part, stats_out,
                          (epa_stream_t)st);
   return EPA_OK;
 }
@@ -474,7 +474,7 @@ extern "C" int epa_range_power(const float* raw, const double* coef, int C, int 
   EPA_CHECK_ARG(coef && range_out, "epa_range_power: NULL array argument");
   EPA_CHECK_ARG(raw || !(flags & EPA_FLAG_MASK_RANGE), "epa_range_power: EPA_FLAG_MASK_RANGE needs the raw samples");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_range_power: C=%d P=%d S=%d must be positive", C, P, S);
-  EPA_CHECK_ARG(out_dtype == EPA_F64 || out_dtype == EPA_F32, "epa_range_power: bad out_dtype %d", out_dtype);
+  EPA_CHECK_ARG(epa::is_real(out_dtype), "epa_range_power: bad out_dtype %d", out_dtype);
   const long long rows = (long long)C * P;
   {  // one-piece workgroups (reduce_util.hip) where the shape takes 16-byte accesses
     const int rc = epa_rows_piece_launch((flags & EPA_FLAG_MASK_RANGE) ? raw : nullptr, nullptr, coef, nullptr, nullptr, rows,
@@ -487,13 +487,12 @@ extern "C" int epa_range_power(const float* raw, const double* coef, int C, int 
   if (gx > rows) gx = rows;
   const dim3 grid((unsigned)gx, (unsigned)chunks);
   const epa::CoefRow* cf = reinterpret_cast<const epa::CoefRow*>(coef);
-  if (out_dtype == EPA_F64)
-    hipLaunchKernelGGL(range_power_kernel<double>, grid, dim3(epa::kBlock), 0, (hipStream_t)stream, raw, cf, rows, S,
-                       flags, (double*)range_out);
-  else
-    hipLaunchKernelGGL(range_power_kernel<float>, grid, dim3(epa::kBlock), 0, (hipStream_t)stream, raw, cf, rows, S,
-                       flags, (float*)range_out);
-  return epa::check_launch("range_power_kernel");
+  return epa::dispatch_real("epa_range_power", out_dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(range_power_kernel<T>, grid, dim3(epa::kBlock), 0, (hipStream_t)stream, raw, cf, rows, S, flags,
+                       (T*)range_out);
+    return epa::check_launch("range_power_kernel");
+  });
 }
 
 extern "C" int epa_sv_power(const float* raw, const double* coef, int C, int P, int S, int cal_type,
@@ -503,12 +502,11 @@ extern "C" int epa_sv_power(const float* raw, const double* coef, int C, int P, 
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_sv_power: C=%d P=%d S=%d must be positive", C, P, S);
   EPA_CHECK_ARG(cal_type == EPA_CAL_SV || cal_type == EPA_CAL_TS, "epa_sv_power: bad cal_type %d",
                 cal_type);
-  if (out_dtype == EPA_F64)
-    return launch<double>(raw, coef, C, P, S, cal_type, flags, out, range_out, nullptr, nullptr, (hipStream_t)stream);
-  if (out_dtype == EPA_F32)
-    return launch<float>(raw, coef, C, P, S, cal_type, flags, out, range_out, nullptr, nullptr, (hipStream_t)stream);
-  epa::set_error("epa_sv_power: bad out_dtype %d", out_dtype);
-  return EPA_EINVAL;
+  EPA_CHECK_ARG(epa::is_real(out_dtype), "epa_sv_power: bad out_dtype %d", out_dtype);
+  return epa::dispatch_real("epa_sv_power", out_dtype, [&](auto tag) {
+    return launch<typename decltype(tag)::type>(raw, coef, C, P, S, cal_type, flags, out, range_out, nullptr, nullptr,
+                                                (hipStream_t)stream);
+  });
 }
 
 extern "C" int epa_sv_power_stats(const float* raw, const double* coef, int C, int P, int S, int cal_type,
@@ -517,12 +515,9 @@ extern "C" int epa_sv_power_stats(const float* raw, const double* coef, int C, i
   EPA_CHECK_ARG(raw && coef && out && workspace && range_stats_out, "epa_sv_power_stats: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_sv_power_stats: C=%d P=%d S=%d must be positive", C, P, S);
   EPA_CHECK_ARG(cal_type == EPA_CAL_SV || cal_type == EPA_CAL_TS, "epa_sv_power_stats: bad cal_type %d", cal_type);
-  if (out_dtype == EPA_F64)
-    return launch<double>(raw, coef, C, P, S, cal_type, flags, out, range_out, workspace, range_stats_out,
-                          (hipStream_t)stream);
-  if (out_dtype == EPA_F32)
-    return launch<float>(raw, coef, C, P, S, cal_type, flags, out, range_out, workspace, range_stats_out,
-                         (hipStream_t)stream);
-  epa::set_error("epa_sv_power_stats: bad out_dtype %d", out_dtype);
-  return EPA_EINVAL;
+  EPA_CHECK_ARG(epa::is_real(out_dtype), "epa_sv_power_stats: bad out_dtype %d", out_dtype);
+  return epa::dispatch_real("epa_sv_power_stats", out_dtype, [&](auto tag) {
+    return launch<typename decltype(tag)::type>(raw, coef, C, P, S, cal_type, flags, out, range_out, workspace,
+                                                range_stats_out, (hipStream_t)stream);
+  });
 }

@@ -256,7 +256,7 @@ __global__ __launch_bounds__(kBlock) void tr_matecho_fill_kernel(const uint8_t* 
 int check_cube(const char* who, const void* sv, const void* mask, int dtype, int C, int P, int S) {
   EPA_CHECK_ARG(sv && mask, "%s: NULL array argument", who);
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "%s: C=%d P=%d S=%d", who, C, P, S);
-  EPA_CHECK_ARG(dtype == EPA_F32 || dtype == EPA_F64, "%s: bad dtype %d", who, dtype);
+  EPA_CHECK_REAL(who, dtype);
   return EPA_OK;
 }
 
@@ -273,20 +273,15 @@ extern "C" int epa_transient_fielding(const void* sv, int dtype, int C, int P, i
   hipStream_t st = (hipStream_t)stream;
   const long long rows = (long long)C * P;
   EPA_CHECK_HIP(hipMemsetAsync(count, 0, sizeof(unsigned), st));
-  if (dtype == EPA_F32)
-    tr_fielding_flag_kernel<float><<<grid_for(rows), kBlock, 0, st>>>((const float*)sv, P, S, rows, chan, n, thr0, maxts,
-                                                                      mask, list, count);
-  else
-    tr_fielding_flag_kernel<double><<<grid_for(rows), kBlock, 0, st>>>((const double*)sv, P, S, rows, chan, n, thr0,
-                                                                       maxts, mask, list, count);
-  if (int rc = epa::check_launch("tr_fielding_flag_kernel")) return rc;
-  const unsigned walkers = grid_for(rows < 16384 ? rows : 16384);
-  if (dtype == EPA_F32)
-    tr_fielding_walk_kernel<float><<<walkers, kBlock, 0, st>>>((const float*)sv, P, S, chan, n, thr1, list, count, mask);
-  else
-    tr_fielding_walk_kernel<double><<<walkers, kBlock, 0, st>>>((const double*)sv, P, S, chan, n, thr1, list, count,
-                                                                mask);
-  return epa::check_launch("tr_fielding_walk_kernel");
+  return epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    tr_fielding_flag_kernel<T><<<grid_for(rows), kBlock, 0, st>>>((const T*)sv, P, S, rows, chan, n, thr0, maxts, mask,
+                                                                  list, count);
+    if (int rc = epa::check_launch("tr_fielding_flag_kernel")) return rc;
+    const unsigned walkers = grid_for(rows < 16384 ? rows : 16384);
+    tr_fielding_walk_kernel<T><<<walkers, kBlock, 0, st>>>((const T*)sv, P, S, chan, n, thr1, list, count, mask);
+    return epa::check_launch("tr_fielding_walk_kernel");
+  });
 }
 
 extern "C" int epa_transient_matecho(const void* sv, int dtype, int C, int P, int S, const double* range,
@@ -309,14 +304,13 @@ extern "C" int epa_transient_matecho(const void* sv, int dtype, int C, int P, in
   tr_matecho_rows_kernel<<<grid_for((rows + kBlock - 1) / kBlock), kBlock, 0, st>>>(bottom, bottom_rows, range, P, S, rows,
                                                                                     chan_i, chan_d, half_window, s_hi);
   if (int rc = epa::check_launch("tr_matecho_rows_kernel")) return rc;
-  if (dtype == EPA_F32)
-    tr_matecho_flag_kernel<float><<<grid_for(rows), kBlock, 0, st>>>((const float*)sv, P, S, rows, chan_i, chan_d, s_hi,
-                                                                     half_window, percentile, delta_db, min_window, flag);
-  else
-    tr_matecho_flag_kernel<double><<<grid_for(rows), kBlock, 0, st>>>((const double*)sv, P, S, rows, chan_i, chan_d, s_hi,
-                                                                      half_window, percentile, delta_db, min_window,
-                                                                      flag);
-  if (int rc = epa::check_launch("tr_matecho_flag_kernel")) return rc;
+  const int rc = epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    tr_matecho_flag_kernel<T><<<grid_for(rows), kBlock, 0, st>>>((const T*)sv, P, S, rows, chan_i, chan_d, s_hi,
+                                                                 half_window, percentile, delta_db, min_window, flag);
+    return epa::check_launch("tr_matecho_flag_kernel");
+  });
+  if (rc) return rc;
   tr_matecho_fill_kernel<<<grid_for(rows), kBlock, 0, st>>>(flag, P, S, rows, extend_ping, mask);
   return epa::check_launch("tr_matecho_fill_kernel");
 }

@@ -1,0 +1,61 @@
+#!/usr/bin/env python
+"""Compare the gfx950 device code of two source trees, function by function.
+
+    python scripts/device_code_diff.py OLD_TREE NEW_TREE [file.hip ...]     (default: build.py's SOURCES)
+
+Each file is compiled to device assembly with build.py's FLAGS of its own tree; every function body and every kernel
+descriptor (registers, LDS, scratch) is then compared as text.  Function-local labels carry the function's ordinal in
+the file, which moves when the instantiation order does, so that ordinal is dropped first.  Exit status 1 when a
+symbol is missing, added or different.  Runs on the CPU: nothing is launched.
+"""
+import os
+import re
+import runpy
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+FUNC = re.compile(r"; -- Begin function (\S+)\n(.*?); -- End function", re.S)
+DESC = re.compile(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", re.S)
+LOCAL = re.compile(r"(\.LBB|\bBB|\.Lfunc_begin|\.Lfunc_end|\.LJTI)\d+")
+BLANKS = re.compile(r"[ \t]+")  # a label's comment is aligned to a column: a longer ordinal moves it
+
+
+def device_symbols(tree, name):
+    build = runpy.run_path(os.path.join(tree, "echopype_amd", "build.py"), run_name="build")
+    cmd = [build["_hipcc"](), *build["FLAGS"], "--cuda-device-only", "-S", os.path.join(build["CSRC"], name), "-o", "-"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.exit(f"hipcc failed:\n{' '.join(cmd)}\n{r.stderr}")
+    asm = r.stdout
+    syms = {"func " + m.group(1): BLANKS.sub(" ", LOCAL.sub(r"\1", m.group(2))) for m in FUNC.finditer(asm)}
+    syms.update({"desc " + m.group(1): m.group(2) for m in DESC.finditer(asm)})
+    return syms
+
+
+def main(argv):
+    if len(argv) < 3:
+        sys.exit(__doc__)
+    old, new = argv[1], argv[2]
+    files = argv[3:] or runpy.run_path(os.path.join(new, "echopype_amd", "build.py"), run_name="build")["SOURCES"]
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        olds = list(ex.map(lambda f: device_symbols(old, f), files))
+        news = list(ex.map(lambda f: device_symbols(new, f), files))
+    bad = 0
+    for name, a, b in zip(files, olds, news):
+        missing = sorted(set(a) - set(b))
+        added = sorted(set(b) - set(a))
+        differ = sorted(s for s in set(a) & set(b) if a[s] != b[s])
+        for what, syms in (("missing", missing), ("added", added), ("differs", differ)):
+            for s in syms:
+                print(f"{name}: {what}: {s}")
+        bad += len(missing) + len(added) + len(differ)
+        nfunc = sum(s.startswith("func ") for s in b)
+        print(f"{name}: {nfunc} functions, {len(b) - nfunc} kernel descriptors: "
+              f"{'identical' if not (missing or added or differ) else 'DIFFERENT'}")
+    print(f"{bad} differences in {len(files)} files")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
