@@ -41,6 +41,8 @@ CT_I8, CT_I16, CT_I32, CT_I64, CT_F32, CT_F64 = range(6)  # enum epa_concat_type
 CONCAT_SEG_WORDS = 5  # int64 words of an epa_concat_seg: base, P, W, first, C
 RAW_ANGLE_NONE, RAW_ANGLE_I8, RAW_ANGLE_F32 = range(3)  # enum epa_raw_angle
 RAW_ZERO_TIME = 1  # EPA_RAW_ZERO_TIME
+NMEA_INVALID, NMEA_LAT_FAILED, NMEA_LON_FAILED, NMEA_UNDECIDED = 1, 2, 4, 64  # EPA_NMEA_*: the status byte
+NMEA_TYPE_SHIFT, NMEA_TYPE_MASK = 3, 0x18  # ... and where it carries enum epa_nmea_type (GGA, GLL, RMC)
 RAW_RECORD_BYTES = 32  # sizeof(epa_raw_record): offset i8, size i4, type u4, low_date u4, high_date u4, flags u4, reserved u4
 CCP = ("sample_interval", "tau_nominal", "transmit_power", "sound_speed", "absorption", "gain", "freq_center", "psi",
        "sa_correction", "z_er", "z_et", "angle_offset_alongship", "angle_offset_athwartship", "beamwidth_alongship",
@@ -176,6 +178,7 @@ SIGNATURES = {
     "epa_concat_rows": [_vp, _vp, _vp, _vp, _i, _i, _ll, _i, _i, _vp, _vp],
     "epa_raw_index": [_vp, _ll, _vp, _ll, ctypes.POINTER(_ll), ctypes.POINTER(_ll)],
     "epa_raw0_unpack": [_vp, _ll, _ll, _vp, _vp, _i, _ll, _ll, _i, _vp, _vp, _vp, _vp],
+    "epa_nmea_positions": [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

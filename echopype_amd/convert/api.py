@@ -4,14 +4,20 @@ volumes are unpacked ON the device (echopype convert/api.py:346-546 with parse_e
 The file goes over PCIe once, as it is on disk -- int16 power and int8 angle pairs, 4 B per sample for both --, the
 ``(channel, ping_time, range_sample)`` volumes are written in HBM by one kernel (``ops.raw0_unpack``), and the only host
 work is the walk over the datagram framing (``epa_raw_index``), one gather of the 84-byte ``RAW0`` headers and the
-``CON0`` configuration.
+``CON0`` configuration.  The GGA / GLL / RMC sentences of the ``NME0`` datagrams are parsed into positions by a second
+kernel on the same bytes (``ops.nmea_positions``, 17 bytes back per fix): ``Platform`` carries ``latitude``, ``longitude``
+and ``sentence_type`` on ``time1``, which is what ``consolidate.add_location`` reads.  The rules are restated in
+``parse_nmea`` (the reference calls ``pynmea2``, which has never been run against them); a sentence outside the plain
+form the kernel decides goes through ``parse_nmea.parse_sentence`` on the host.  ``Platform/NMEA`` keeps every sentence.
 
-Scope: EK60 (``CON0`` / ``RAW0`` / ``NME0``).  EK80, AZFP, ``.bot`` / ``.idx`` files, ``use_swap`` and the parsing of NMEA
-sentences into positions are not built: the sentences and their times are kept in ``Platform/NMEA``, ``Platform`` has no
-``latitude`` / ``longitude``.
+Scope: EK60 (``CON0`` / ``RAW0`` / ``NME0``).  EK80, AZFP, ``.bot`` / ``.idx`` files, ``use_swap`` and the positions of
+``MRU1`` / ``IDX`` datagrams are not built.
 
 Deviations from the reference, all on purpose:
 
+* ``sentence_type`` of a sentence that does not parse is ``""`` (the reference: a float NaN among strings), so the
+  variable has one string dtype; its fix is NaN, NaN as there.  A file without a GGA / GLL / RMC sentence has one entry at
+  the earliest ping time: NaN, NaN, ``""``;
 * no resynchronisation -- a trailing datagram size that differs from the leading one, or a size below 16, raises
   ``ValueError`` with the byte offset (the reference searches for the next datagram).  A file that ends inside a
   datagram (cut while recording) keeps the complete datagrams in front and logs a warning, as there;
@@ -33,7 +39,7 @@ from .. import ops
 from ..echodata import BEAM1, EchoData
 from ..utils.prov import echopype_prov_attrs
 from ..xr_lite import DataArray, Dataset, DeviceArray
-from . import parse_ek60
+from . import parse_ek60, parse_nmea
 
 logger = logging.getLogger(__name__)
 
@@ -82,9 +88,56 @@ def _channel_vars(pl, name, dtype=np.float64):
     return np.array([tx[k][name] for k in pl.transceivers], dtype=dtype)
 
 
+def launch_positions(pl, file_dev, n_bytes):
+    """The positions kernel over the selected sentences of the plan, on the file's bytes in HBM -> one uint8 device tensor
+    of 17 bytes per sentence (all latitudes, all longitudes, all status bytes: ONE download), None without a sentence."""
+    import torch
+
+    sel = pl.nmea_selected
+    if sel.size == 0:
+        return None
+    n = int(sel.size)
+    packed = torch.empty(17 * n, dtype=torch.uint8, device=file_dev.device)
+    out = (packed[:8 * n].view(torch.float64), packed[8 * n:16 * n].view(torch.float64), packed[16 * n:])
+    ops.nmea_positions(file_dev, np.stack([pl.nmea_offset[sel], pl.nmea_length[sel]], axis=1), n_bytes=n_bytes, out=out)
+    return packed
+
+
+def positions(pl, packed, raw_file="<memory>"):
+    """(time1, latitude, longitude, sentence_type) of the Platform group from what ``launch_positions`` left: the kernel's
+    answers, ``parse_nmea.parse_sentence`` for the sentences it did not decide, the reference's warning once per file
+    and coordinate for a field that is no ``DDDMM.MMM`` (set_groups_base.py:204-215), the placeholder of a file without
+    a selected sentence."""
+    from .._lib import NMEA_INVALID, NMEA_LAT_FAILED, NMEA_LON_FAILED, NMEA_TYPE_MASK, NMEA_TYPE_SHIFT, NMEA_UNDECIDED
+
+    if packed is None:
+        return parse_nmea.placeholder(pl.ping_time)
+    sel = pl.nmea_selected
+    n = int(sel.size)
+    host = packed.cpu().numpy()
+    lat, lon, code = host[:8 * n].view(np.float64).copy(), host[8 * n:16 * n].view(np.float64).copy(), host[16 * n:]
+    kind = np.where((code == NMEA_INVALID) | (code == NMEA_UNDECIDED), len(parse_nmea.TYPES),
+                    (code & NMEA_TYPE_MASK) >> NMEA_TYPE_SHIFT)
+    stype = np.array(parse_nmea.TYPES + ("",), dtype="<U3")[kind]
+    lat_bad, lon_bad = (code & NMEA_LAT_FAILED) != 0, (code & NMEA_LON_FAILED) != 0
+    decided = code != NMEA_UNDECIDED
+    lat_bad &= decided
+    lon_bad &= decided
+    for i in np.flatnonzero(~decided):
+        lat[i], lon[i], stype[i] = parse_nmea.parse_sentence(pl.nmea[sel[i]])
+        if stype[i]:
+            lat_bad[i], lon_bad[i] = np.isnan(lat[i]), np.isnan(lon[i])
+    for name, bad, field in (("latitude", lat_bad, "lat"), ("longitude", lon_bad, "lon")):
+        if bad.any():
+            first = getattr(parse_nmea.split_sentence(pl.nmea[sel[int(np.flatnonzero(bad)[0])]]), field)
+            logger.warning("%s: " + parse_nmea.WARNING[name], raw_file,
+                           f"Geographic coordinate value '{first}' is not valid DDDMM.MMM")
+    return pl.nmea_time[sel], lat, lon, stype
+
+
 def build_groups(pl, power, athw, along, source_file):
     """The groups of the EchoData from the plan and the three device planes (names, dims and dtypes of
-    set_groups_ek60.py and set_groups_base.set_nmea)."""
+    set_groups_ek60.py and set_groups_base.set_nmea).  ``Platform`` gets its fixes from ``set_fixes``."""
     cfg, ch, pt, S = pl.config, list(pl.channel), pl.ping_time, pl.S
     freq = _channel_vars(pl, "frequency")
     fattrs = {"units": "Hz", "long_name": "Transducer frequency", "valid_min": 0.0, "standard_name": "sound_frequency"}
@@ -175,6 +228,23 @@ def build_groups(pl, power, athw, along, source_file):
             "Sonar": sonar, BEAM1: beam, "Vendor_specific": vend}
 
 
+def set_fixes(plat, fixes):
+    """``latitude``, ``longitude`` and ``sentence_type`` on ``time1`` into the Platform group: the fixes of the GGA / GLL / RMC
+    sentences (set_groups_ek60.py:182-210; the attributes are those of the convention's ``platform_var_default`` and
+    ``platform_coord_default``, restated)."""
+    time1, lat, lon, sentence_type = fixes
+    plat.coords["time1"] = DataArray(np.asarray(time1, dtype="datetime64[ns]"), ("time1",), name="time1",
+                                     attrs={"axis": "T", "long_name": "Timestamps for NMEA datagrams", "standard_name": "time",
+                                            "comment": "Time coordinate corresponding to NMEA position data."})
+    plat["latitude"] = (("time1",), np.asarray(lat, dtype=np.float64),
+                        {"long_name": "Platform latitude", "standard_name": "latitude", "units": "degrees_north",
+                         "valid_range": (-90.0, 90.0)})
+    plat["longitude"] = (("time1",), np.asarray(lon, dtype=np.float64),
+                         {"long_name": "Platform longitude", "standard_name": "longitude", "units": "degrees_east",
+                          "valid_range": (-180.0, 180.0)})
+    plat["sentence_type"] = (("time1",), np.asarray(sentence_type, dtype=str), {"long_name": "NMEA sentence type"})
+
+
 def open_raw(raw_file, sonar_model, xml_path=None, include_bot=False, include_idx=False, convert_params=None,
              storage_options=None, use_swap=False, max_chunk_size="100MB"):
     """Read the EK60 file ``raw_file`` into an :class:`EchoData` whose sample variables are resident in HBM, as after
@@ -198,9 +268,13 @@ def open_raw(raw_file, sonar_model, xml_path=None, include_bot=False, include_id
     pl = host_plan(buf, n_bytes, raw_file)
     file_dev = ops.to_device(buf)  # the file as it is on disk, once
     power, athw, along = ops.raw0_unpack(file_dev, pl.table, pl.C, pl.P, pl.S, angles=pl.angles, n_bytes=n_bytes)
-    # the file's bytes are not needed behind the kernel: the allocator may hand the block out again once the stream has
+    packed = launch_positions(pl, file_dev, n_bytes)  # the NMEA sentences, read where they lie between the sample blocks
+    # the file's bytes are not needed behind the kernels: the allocator may hand the block out again once the stream has
     # passed this point
     file_dev.record_stream(torch.cuda.current_stream(file_dev.device))
     del file_dev
     ed = EchoData("EK60", build_groups(pl, power, athw, along, raw_file), source_file=raw_file)
-    return ed.to_device(power.device)
+    ed = ed.to_device(power.device)
+    # the fixes last: their download waits for the file's upload and both kernels, which the host work above overlaps
+    set_fixes(ed["Platform"], positions(pl, packed, raw_file))
+    return ed

@@ -10,6 +10,7 @@ import struct
 import numpy as np
 
 from .. import _lib
+from . import parse_nmea
 
 RECORD_DTYPE = np.dtype([("offset", "<i8"), ("size", "<i4"), ("type", "S4"), ("low_date", "<u4"), ("high_date", "<u4"),
                          ("flags", "<u4"), ("reserved", "<u4")])
@@ -120,12 +121,23 @@ def gather_raw0(buf, records):
 
 
 def nmea_sentences(buf, records):
-    """(times datetime64[ns], sentences) of the ``NME0`` datagrams: the text behind the 12-byte header, NULs stripped,
-    decoded as ASCII with replacement (ek_raw_parsers.py:442-446).  (One Python step per sentence: they are strings.)"""
+    """(times datetime64[ns], sentences, offsets, lengths) of the ``NME0`` datagrams: the text behind the 12-byte header,
+    NULs stripped, decoded as ASCII with replacement (ek_raw_parsers.py:442-446), and where that stripped text lies in
+    ``buf`` (int64 byte offset and length: leading NULs move the start).  (One Python step per sentence: they are
+    strings.)"""
     times = nt_to_ns(records["low_date"], records["high_date"])
-    text = [str(buf[int(o) + 12:int(o) + int(s)].tobytes().strip(b"\x00"), "ascii", errors="replace")
-            for o, s in zip(records["offset"], records["size"])]
-    return times, text
+    start = records["offset"].astype(np.int64) + 12
+    length = records["size"].astype(np.int64) - 12
+    text = [str(buf[a:a + n].tobytes().strip(b"\x00"), "ascii", errors="replace") for a, n in zip(start.tolist(), length.tolist())]
+    # where the stripped text lies: the whole body unless its first or last byte is a NUL (few sentences, if any)
+    some = np.flatnonzero(length > 0)
+    padded = some[(buf[start[some]] == 0) | (buf[start[some] + length[some] - 1] == 0)]
+    for i in padded.tolist():
+        raw = buf[start[i]:start[i] + length[i]].tobytes()
+        tail = raw.lstrip(b"\x00")
+        start[i] += len(raw) - len(tail)
+        length[i] = len(tail.rstrip(b"\x00"))
+    return times, text, start, length
 
 
 class Ek60Plan:
@@ -148,7 +160,8 @@ def plan(buf, n_bytes=None):
     ``angles``          None, "int8" or "float32": the angle variables exist when a channel records angles on all its
                         pings (set_groups_ek60.py:678); int8 when every row of every channel is present, full and has
                         angles, else float32 with NaN (the rule of ``ops.concat_rows``)
-    ``nmea_time, nmea``  the NME0 sentences
+    ``nmea_time, nmea``  the NME0 sentences; ``nmea_offset, nmea_length``: where each one's stripped text lies in the file;
+                        ``nmea_selected``: the indices of those that carry a position (``parse_nmea.select``, rule R1)
 
     ``ValueError``: no ``CON0`` in front, no ping with power, a RAW0 that does not hold its samples, a channel number
     outside the configuration, a ping time twice in one channel; ``NotImplementedError``: a mode-2 (angle only) ping."""
@@ -163,7 +176,8 @@ def plan(buf, n_bytes=None):
     zero = (rec["flags"] & _lib.RAW_ZERO_TIME) != 0
     out.skipped_zero_time = int(zero[1:].sum())
     live = rec[1:][~zero[1:]]
-    out.nmea_time, out.nmea = nmea_sentences(buf, live[live["type"] == b"NME0"])
+    out.nmea_time, out.nmea, out.nmea_offset, out.nmea_length = nmea_sentences(buf, live[live["type"] == b"NME0"])
+    out.nmea_selected = np.flatnonzero(parse_nmea.select(buf, out.nmea_offset, out.nmea_length))
     raw = live[live["type"] == b"RAW0"]
     hdr = gather_raw0(buf, raw)
     mode, count, chan = hdr["mode"].astype(np.int64), hdr["count"].astype(np.int64), hdr["channel"].astype(np.int64)

@@ -1264,6 +1264,38 @@ def raw0_unpack(file_bytes, table, C, P, S, angles="int8", *, n_bytes=None, out=
     return power, athw, along
 
 
+def nmea_positions(file_bytes, table, *, n_bytes=None, out=None):
+    """Latitude and longitude of NMEA sentences lying in the bytes of an EK60 .raw file -> (lat float64, lon float64,
+    code uint8) device tensors of length n (``epa_nmea_positions``: one launch, a wavefront per sentence).
+
+    ``file_bytes``: as for ``raw0_unpack``.  ``table``: int64 host array (n, 2), byte offset and length of each sentence's
+    text, NULs stripped.  ``code``: 0 or the bits ``_lib.NMEA_LAT_FAILED`` / ``NMEA_LON_FAILED`` (that value is NaN) with
+    the sentence type in ``_lib.NMEA_TYPE_MASK``; ``NMEA_INVALID`` (NaN, NaN); ``NMEA_UNDECIDED``: the kernel decides the
+    plain form only (``convert.parse_nmea.plain_form``), the caller applies ``parse_nmea.parse_sentence`` to the rest.
+    ``n == 0`` launches nothing.  ``out``: the three tensors to write into instead of new ones (tests)."""
+    if not (isinstance(file_bytes, torch.Tensor) and file_bytes.dtype == torch.uint8 and file_bytes.dim() == 1):
+        raise ValueError("nmea_positions: file_bytes must be a one-dimensional uint8 tensor")
+    tab = np.asarray(table, dtype=np.int64)
+    if tab.ndim != 2 or tab.shape[1] != 2:
+        raise ValueError(f"nmea_positions: the table must have the shape (n, 2), got {tab.shape}")
+    tab = np.ascontiguousarray(tab)
+    n, dev = int(tab.shape[0]), file_bytes.device
+    if out is None:
+        lat = torch.empty(n, dtype=torch.float64, device=dev)
+        lon = torch.empty(n, dtype=torch.float64, device=dev)
+        code = torch.empty(n, dtype=torch.uint8, device=dev)
+    else:
+        lat, lon, code = out
+        for t, dt in ((lat, torch.float64), (lon, torch.float64), (code, torch.uint8)):
+            if t.dtype != dt or tuple(t.shape) != (n,) or t.device != dev or not t.is_contiguous():
+                raise ValueError("nmea_positions: out must hold contiguous (n,) tensors of float64, float64 and uint8 on the "
+                                 "file's device")
+    tab_dev = to_device(tab, device=dev) if n else None
+    call("epa_nmea_positions", _p(file_bytes), int(file_bytes.numel() if n_bytes is None else n_bytes), int(file_bytes.numel()),
+         tab.ctypes.data_as(ctypes.c_void_p), _p(tab_dev), n, _p(lat), _p(lon), _p(code), _stream())
+    return lat, lon, code
+
+
 class Timer:
     """HIP-event timer on torch's current stream (epa_timer_*)."""
 

@@ -936,6 +936,36 @@ int epa_raw0_unpack(const uint8_t* bytes, long long n_bytes, long long n_alloc, 
                     const int64_t* table, int C, long long P, long long S, int angle_type, float* power,
                     void* athwartship, void* alongship, epa_stream_t stream);
 
+/* Positions from the NMEA sentences of the file's NME0 datagrams, parsed where they lie in HBM (set_groups_base.py:180-239,
+ * which calls pynmea2.parse once per sentence on the host; the rules are restated in echopype_amd/convert/parse_nmea.py).
+ * bytes / n_bytes / n_alloc: the file as for epa_raw0_unpack.  table [n][2] int64: byte offset and length of the text of
+ * each selected sentence, NULs stripped; table_host the same on the host, which the checks read.  Per sentence:
+ * lat, lon [n] f64 in signed degrees and code [n], a status byte:
+ *   0                       both values written
+ *   EPA_NMEA_INVALID        the checksum does not hold: NaN, NaN
+ *   EPA_NMEA_LAT_FAILED     bit: the latitude field is not DDMM.MMM: NaN        (the type bits are set as well)
+ *   EPA_NMEA_LON_FAILED     bit: the longitude field is not DDDMM.MMM: NaN
+ *   EPA_NMEA_UNDECIDED      not decided here, NaN, NaN: the caller applies the host rules (parse_nmea.parse_sentence)
+ * and, unless the code is EPA_NMEA_INVALID or EPA_NMEA_UNDECIDED, the sentence type (enum epa_nmea_type) in the bits
+ * EPA_NMEA_TYPE_MASK: (code & EPA_NMEA_TYPE_MASK) >> EPA_NMEA_TYPE_SHIFT.  NaN is 0x7FF8000000000000.
+ * The kernel decides only the PLAIN FORM and never guesses: byte 0 is '$'; bytes 1-5 are ASCII letters or digits, byte 1
+ * not 'P' / 'p', bytes 3-5 "GGA", "GLL" or "RMC"; byte 6 is ','; every byte is in 0x20..0x7E apart from a trailing run of
+ * CR / LF / space / tab; at most one '*', then exactly two hex digits (either case) and only that run behind them; without
+ * a '*', the four coordinate fields end at a comma or the run is empty; a latitude / longitude field has at most 64 bytes,
+ * and where it has the form digits "." digits, its degrees and the digits of its minutes are integers below 10^15 with at
+ * most 15 decimals -- under which the result equals Python's float(d) + float(m) / 60 bit for bit.
+ * n == 0 launches nothing.  EPA_EINVAL (nothing is launched): a NULL array with n > 0; a negative n; a row that leaves
+ * [0, n_bytes); n_alloc not a multiple of 16 or below n_bytes.  No reference counterpart as a function. */
+enum epa_nmea_type { EPA_NMEA_GGA = 0, EPA_NMEA_GLL = 1, EPA_NMEA_RMC = 2 };
+#define EPA_NMEA_INVALID 1
+#define EPA_NMEA_LAT_FAILED 2
+#define EPA_NMEA_LON_FAILED 4
+#define EPA_NMEA_TYPE_SHIFT 3
+#define EPA_NMEA_TYPE_MASK 0x18
+#define EPA_NMEA_UNDECIDED 64
+int epa_nmea_positions(const uint8_t* bytes, long long n_bytes, long long n_alloc, const int64_t* table_host,
+                       const int64_t* table, long long n, double* lat, double* lon, uint8_t* code, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

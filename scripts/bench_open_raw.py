@@ -2,7 +2,8 @@
 """``open_raw`` at a survey file's size: an EK60 file of 4 channels x 30 000 pings x 2600 samples, mode 3 (int16 power and
 int8 angle pairs, 4 B per sample), an NME0 sentence behind every ping whose length walks through all residues mod 4 --
 so the sample blocks start at every byte offset mod 4 --, about 1.25 GB.  The file is written here with a few lines of
-``struct`` and NumPy (sample values from a small random pool: the contents do not change what is moved).
+``struct`` and NumPy (scripts/raw_bench_file.py; sample values from a small random pool: the contents do not change what is
+moved).
 
 Per quantity the median, minimum and maximum of ``--reps`` (at least 7) timed runs after 2 warm-up runs:
 
@@ -32,6 +33,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import raw_bench_file  # noqa: E402
 import echopype_amd as ep  # noqa: E402
 from echopype_amd import _lib, ops  # noqa: E402
 from echopype_amd.convert import api, parse_ek60  # noqa: E402
@@ -50,57 +53,18 @@ if args.reps < 7 or args.baseline_reps < 7:
 C, P, S, REPS = args.channels, args.pings, args.samples, args.reps
 K = np.float32(10.0 * np.log10(2.0) / 256.0)
 HBM_PEAK = 8.0e12
-NT0 = (1505260150 + 11644473600) * 10_000_000
 
 
 def summary(ts):
     return {"ms_median": float(np.median(ts)), "ms_min": float(min(ts)), "ms_max": float(max(ts)), "runs": len(ts)}
 
 
-# ---- the file ---------------------------------------------------------------------------------------------------------
-def frame(body):
-    return struct.pack("<l", len(body)) + body + struct.pack("<l", len(body))
-
-
-def con0():
-    body = struct.pack("<4sLL128s128s128s30s98sl", b"CON0", NT0 & 0xFFFFFFFF, NT0 >> 32, b"bench", b"", b"ER60", b"2.4.3", b"", C)
-    for c in range(C):
-        cid = f"GPT {18 + 20 * c:3d} kHz 00907203{c:04x} {c + 1}-1 ES{18 + 20 * c}".encode()
-        tab = [0.000256, 0.000512, 0.001024, 0.002048, 0.004096]
-        body += struct.pack("<128sl15f5f8s5f8s5f8s16s28s", cid, 1, 18000.0 + 20000.0 * c, 25.0, -20.0, 7.0, 7.0, 21.9, 21.9, 0.0,
-                            0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, *tab, b"", *([25.0] * 5), b"", *([-0.5] * 5), b"", b"070413", b"")
-    return frame(body)
+# ---- the file (scripts/raw_bench_file.py, shared with bench_nmea.py) ------------------------------------------------------
+NMEA = [b"$GPGLL,4704.12,N,12503.43,W,234911,A*2" + b"x" * r for r in range(4)]
 
 
 def build_file(path):
-    rng = np.random.default_rng(20261019)
-    pool = [np.concatenate([rng.integers(-12000, -2000, S).astype("<i2").view(np.uint8),
-                            rng.integers(-128, 128, 2 * S).astype(np.int8).view(np.uint8)]) for _ in range(61)]
-    nmea = [b"$GPGLL,4704.12,N,12503.43,W,234911,A*2" + b"x" * r for r in range(4)]
-    head = con0()
-    dg = 8 + 84 + 4 * S
-    total = len(head) + P * C * dg + sum(8 + 12 + len(nmea[p % 4]) for p in range(P))
-    buf = np.empty(total, dtype=np.uint8)
-    buf[:len(head)] = np.frombuffer(head, np.uint8)
-    pos, n = len(head), 0
-    for p in range(P):
-        t = NT0 + p * 10_000_000
-        for c in range(C):
-            hdr = struct.pack("<l4sLLhh13fh6sll", 84 + 4 * S, b"RAW0", t & 0xFFFFFFFF, t >> 32, c + 1, 3, 9.15, 18000.0 + 20000.0 * c,
-                              1000.0, 0.001024, 2425.0, 0.000256, 1480.0 + c, 0.003 * (c + 1), 0.0, 0.0, 0.0, 4.0, 0.0, 0, b"", 0, S)
-            buf[pos:pos + 88] = np.frombuffer(hdr, np.uint8)
-            buf[pos + 88:pos + 88 + 4 * S] = pool[n % len(pool)]
-            buf[pos + 88 + 4 * S:pos + dg] = np.frombuffer(hdr[:4], np.uint8)
-            pos += dg
-            n += 1
-        body = struct.pack("<4sLL", b"NME0", (t + 5) & 0xFFFFFFFF, (t + 5) >> 32) + nmea[p % 4]
-        fr = frame(body)
-        buf[pos:pos + len(fr)] = np.frombuffer(fr, np.uint8)
-        pos += len(fr)
-    assert pos == total
-    with open(path, "wb") as f:
-        f.write(memoryview(buf))
-    return total
+    return raw_bench_file.build_file(path, C, P, S, lambda p: NMEA[p % 4], nme0_delay=5)[0]
 
 
 # ---- the route of today, restated with NumPy ------------------------------------------------------------------------------
