@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..commongrid.api import _coef_rows, _range_stats
+from ..commongrid.api import _binned_through_rows, _coef_rows, _range_stats
 from ..commongrid.utils import _parse_x_bin
 from ..device_view import as_tensor, broadcast_to_dims, device_view
 from ..utils.prov import echopype_prov_attrs, insert_processing_level
@@ -157,23 +157,20 @@ def _denoise_deferred_sv(ds_Sv, ping_num, range_sample_num, nmax, snr, shard=Non
     sv_da, rng_da = ds_Sv["Sv"], ds_Sv["echo_range"] if "echo_range" in ds_Sv else None
     d = sv_da.data
     src = d.source if isinstance(d, LazyDeviceArray) and not d.materialized else None
-    dims = ("channel", "ping_time", "range_sample")
     ctx = None
     if shard is not None:
         from .. import sharding
 
         ctx = shard[2] if shard[2] is not None else sharding.ShardContext(shard[1])
     if src is None or isinstance(src, DenoiseSource) or rng_da is None or src.cal_type != "Sv" \
-            or rng_da.data is not src.echo_range \
-            or tuple(sv_da.dims) != dims or tuple(rng_da.dims) != dims \
-            or src.echo_range.coef_rows() is not src.coef or not src.intact():
+            or not _binned_through_rows(src, sv_da, rng_da, src.echo_range) or not src.intact():
         # (rank-local state -- this rank's Sv already read, its raw samples written to: the other ranks of the file may be
         #  on their way into the vote below, and this one must cast its own before it takes the plain route)
         if ctx is not None:
             ctx.agree(True)
         return None
     C, P, S = d.shape
-    a2 = _alpha2(ds_Sv, dims, C, P)
+    a2 = _alpha2(ds_Sv, _CPS, C, P)
     phase = 0 if shard is None else int(shard[0]) % int(ping_num)
     out = None
     try:

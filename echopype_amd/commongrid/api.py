@@ -13,17 +13,14 @@ import torch
 from .. import _lib, ops
 from ..device_view import as_tensor, broadcast_to_dims
 from ..utils.prov import echopype_prov_attrs, insert_processing_level
-from ..xr_lite import (DataArray, Dataset, DeferredDataset, DeviceArray, LazyDeviceArray, defer_mvbs_enabled, from_xarray,
-                       xarray_io)
+from ..xr_lite import DataArray, Dataset, DeviceArray, LazyDeviceArray, defer_mvbs_enabled, from_xarray, xarray_io
+from .deferred import (CPS, deferred_mvbs, launch_or_decline, n_range_bins, nan_coordinate_warning, range_cap, range_edges,
+                       sorted_time_grid, time_bin_start)
 from .utils import (_parse_x_bin, _set_MVBS_attrs, _setup_and_validate, coarsen_time_mean, get_distance_from_latlon,
                     ping_time_bin_parsing_and_conversion, resample_edges)
 
 logger = logging.getLogger("echopype_amd.commongrid")
 _TORCH_DT = {"float64": torch.float64, "float32": torch.float32}
-
-_AGG_MSG = ("Aggregation may be negatively impacted since Flox will not aggregate any "
-            "```Sv``` values that have corresponding NaN coordinate values. Consider handling "
-            "these values before calling your intended commongrid function.")
 
 
 def _range_stats(da, t):
@@ -144,15 +141,14 @@ def _mvbs_plain(ds_Sv, range_var, range_bin_m, ping_time_bin, skipna, fill_value
         rmax = _parse_x_bin(range_var_max) + 1e-8
     if not np.isfinite(rmax):
         raise ValueError("range bins are empty: the range variable holds no valid values")
-    r_edges = np.arange(0, rmax + range_bin_m, range_bin_m)
+    r_edges = range_edges(rmax, range_bin_m)
     n_r = len(r_edges) - 1  # 0 when the only valid range is 0 (one sample per ping): an empty grid, as in the reference
 
-    # NaN coordinates are not aggregated (utils.py:595-608: same warning text)
     ping_time = np.asarray(ds_Sv["ping_time"].values).astype("datetime64[ns]")
     if np.isnat(ping_time).any():
-        logging.warning(f"The ```ping_time``` coordinate array contain NaNs. {_AGG_MSG}")
+        nan_coordinate_warning("ping_time")
     if n_nan_range > 0:
-        logging.warning(f"The ```{range_var}``` coordinate array contain NaNs. {_AGG_MSG}")
+        nan_coordinate_warning(range_var)
 
     # ping bins: pandas-resample edges, anchored at midnight (api.py:118-128)
     e0, dt, n_t = resample_edges(ping_time, ping_time_bin)
@@ -185,6 +181,19 @@ def _mvbs_plain(ds_Sv, range_var, range_bin_m, ping_time_bin, skipna, fill_value
                           ping_time_bin, closed)
 
 
+def _binned_through_rows(p, sv_da, rng_da, rng_d):
+    """Can a pass over the raw samples of ``p`` (calibrate_base.PowerSource) bin ``sv_da`` on ``rng_da``?  It holds
+    ``rng_d``, both have the samples' dimensions, and p's echo_range still is the function of p's coefficient rows."""
+    return rng_da.data is rng_d and tuple(sv_da.dims) == CPS and tuple(rng_da.dims) == CPS \
+        and p.echo_range.coef_rows() is p.coef
+
+
+def _plain_fallback(range_var, range_bin_m, ping_time_bin, fill_value, range_var_max, skipna=True, closed="left"):
+    """The fallback of a deferred route: the plain route on the snapshot, assembled at once."""
+    return lambda ds: _mvbs_plain(ds, range_var, range_bin_m, ping_time_bin, skipna, fill_value, closed, range_var_max,
+                                  None, allow_defer=False)
+
+
 def _mvbs_of_array_without_waiting(ds_Sv, sv_t, rows, range_var, range_bin_m, ping_time_bin, skipna, fill_value, closed,
                                    range_var_max):
     """The binning of an Sv ARRAY whose range variable is still lazy (``compute_Sv`` on EK80 complex samples; an EK60 Sv
@@ -195,65 +204,23 @@ def _mvbs_of_array_without_waiting(ds_Sv, sv_t, rows, range_var, range_bin_m, pi
     rng_d = ds_Sv[range_var].data
     if not isinstance(rng_d, LazyDeviceArray):
         return None
-    bound = (_parse_x_bin(range_var_max) + 1e-8) if range_var_max is not None else rng_d.reach_bound
-    if bound is None or not np.isfinite(bound):
+    bound = range_cap(range_var_max, rng_d.reach_bound)  # (no bound on the host: no device reduction here)
+    grid = sorted_time_grid(ds_Sv["ping_time"].values, ping_time_bin) if bound is not None else None
+    if grid is None:
         return None
-    ping_time = np.asarray(ds_Sv["ping_time"].values).astype("datetime64[ns]", copy=False)
-    ns, sorted_valid, _ = ops.ping_time_facts(ping_time, want_device=False)
-    if not sorted_valid:  # unsorted pings, NaT
-        return None
-    n_cap = len(np.arange(0, bound + range_bin_m, range_bin_m)) - 1
+    n_cap = n_range_bins(bound, range_bin_m)
     stats = rng_d.stats_async() if n_cap >= 1 else None
     if stats is None:
         return None
-    C, P, S = sv_t.shape
-    e0, dt, n_t = resample_edges(ping_time, ping_time_bin, sorted_valid=True)
-    bin_start = ops.time_bin_offsets(ops.ping_time_facts(ping_time)[2], e0, dt, n_t, closed=closed)
-    try:
-        res = ops.mvbs(sv_t, bin_start, n_t, range_bin_m, n_cap, coef=rows, coef_as_stored=True, skipna=skipna,
-                       closed=closed, fill_value=fill_value)
-    except _lib.EpaError:
+    ping_time, _, e0, dt, n_t = grid
+    bin_start = time_bin_start(ping_time, e0, dt, n_t, closed)
+    got = launch_or_decline(lambda: ops.mvbs(sv_t, bin_start, n_t, range_bin_m, n_cap, coef=rows, coef_as_stored=True,
+                                             skipna=skipna, closed=closed, fill_value=fill_value))
+    if got is None:
         return None
-    dim_0 = tuple(ds_Sv["Sv"].dims)[0]
-    # what the assembly needs is taken NOW: the caller may replace variables or edit attributes of its dataset between
-    # this call and the first use of the result, and the result must not change with them; the kernel's partial sums /
-    # counts are not kept alive by the closure
-    ds_Sv, mv_full = ds_Sv.copy(), res["MVBS"]
-    del res
-
-    def build():
-        lo, hi, n_nan_range = stats.tolist()
-        rmax = hi if range_var_max is None else bound
-        r_edges = np.arange(0, rmax + range_bin_m, range_bin_m) if np.isfinite(rmax) else np.zeros(1)
-        n_r = len(r_edges) - 1
-        if n_r < 1 or n_r > n_cap:  # (no valid range / an empty grid: the plain route raises or returns the reference's)
-            return _mvbs_plain(ds_Sv, range_var, range_bin_m, ping_time_bin, skipna, fill_value, closed, range_var_max, None, allow_defer=False)
-        if n_nan_range > 0:
-            logging.warning(f"The ```{range_var}``` coordinate array contain NaNs. {_AGG_MSG}")
-        mvbs_t = mv_full[..., :n_r].contiguous() if n_r != n_cap else mv_full
-        return _assemble_mvbs(ds_Sv, mvbs_t, dim_0, ping_time, e0, dt, n_t, r_edges, range_var, range_bin_m,
-                              ping_time_bin, closed)
-
-    return DeferredDataset(build)
-
-
-def _shard_assemble(ds_Sv, mv_full, n_cap, rmax, r_cap, range_var_max, n_nan_range, ping_time, e0, dt, n_t, range_var,
-                    range_bin_m, ping_time_bin):
-    """The deferred assembly on a ping shard: ``rmax`` = nanmax(range) over ALL shards (all-reduced in HBM).  No
-    fallback here -- a fallback would be a collective at a time only this rank chooses."""
-    rmax = rmax if range_var_max is None else r_cap
-    if not np.isfinite(rmax):  # no valid range on any rank: the reference's grid does not exist
-        raise ValueError("range bins are empty: the range variable holds no valid values")
-    r_edges = np.arange(0, rmax + range_bin_m, range_bin_m)
-    n_r = len(r_edges) - 1
-    if n_r > n_cap:
-        raise RuntimeError(f"nanmax({range_var}) = {rmax} lies beyond the range grid the shards agreed on "
-                           f"({n_cap} bins of {range_bin_m} m)")
-    if n_nan_range > 0:
-        logging.warning(f"The ```{range_var}``` coordinate array contain NaNs. {_AGG_MSG}")
-    mvbs_t = mv_full[..., :n_r].contiguous() if n_r != n_cap else mv_full
-    return _assemble_mvbs(ds_Sv, mvbs_t, "channel", ping_time, e0, dt, n_t, r_edges, range_var, range_bin_m,
-                          ping_time_bin, "left")
+    plain = _plain_fallback(range_var, range_bin_m, ping_time_bin, fill_value, range_var_max, skipna, closed)
+    return deferred_mvbs(ds_Sv, got[1], n_cap, lambda: stats.tolist()[1:], range_var_max, bound, (ping_time, e0, dt),
+                         range_var, range_bin_m, ping_time_bin, plain, tuple(ds_Sv["Sv"].dims)[0], closed)
 
 
 def _mvbs_of_deferred_sv(ds_Sv, range_var, range_bin_m, ping_time_bin, fill_value, range_var_max, _shard=None, _grid=None):
@@ -271,7 +238,6 @@ def _mvbs_of_deferred_sv(ds_Sv, range_var, range_bin_m, ping_time_bin, fill_valu
     sv_da, rng_da = ds_Sv["Sv"], ds_Sv[range_var]
     d = sv_da.data
     src = d.source if isinstance(d, LazyDeviceArray) and not d.materialized else None
-    dims = ("channel", "ping_time", "range_sample")
     # ``depth`` left lazy by add_depth on this dataset's lazy echo_range (offset + scale * echo_range, row by row): binned
     # inside the same pass (epa_sv_mvbs_fused_depth) -- the three reference calls at the 12 B/sample of the two
     rng_d, depth = rng_da.data, None
@@ -280,104 +246,60 @@ def _mvbs_of_deferred_sv(ds_Sv, range_var, range_bin_m, ping_time_bin, fill_valu
         if aff is not None and aff[0] is getattr(src, "echo_range", None) \
                 and src.flags == (_lib.FLAG_GUARD_POS | _lib.FLAG_MASK_RANGE) and rng_d.dtype == d.dtype:
             depth = aff[1:]
-    if src is None or getattr(src, "cal_type", None) != "Sv" or (depth is None and rng_d is not src.echo_range) \
-            or tuple(sv_da.dims) != dims \
-            or tuple(rng_da.dims) != dims or src.echo_range.coef_rows() is not src.coef or not src.intact():
+    if src is None or getattr(src, "cal_type", None) != "Sv" or not src.intact() \
+            or not _binned_through_rows(src, sv_da, rng_da, src.echo_range if depth is None else rng_d):
         return None  # (also: an Sv deferred by something else than compute_Sv, e.g. remove_background_noise)
-    ping_time = np.asarray(ds_Sv["ping_time"].values).astype("datetime64[ns]", copy=False)
-    # (kept with the array when it is resident data, EchoData.to_device: no O(P) pass, no upload per call)
-    ns, sorted_valid, _ = ops.ping_time_facts(ping_time, want_device=False)
-    if not sorted_valid:  # unsorted, NaT, or no ping at all
+    grid = sorted_time_grid(ds_Sv["ping_time"].values, ping_time_bin)
+    if grid is None:
         return None
-    e0, dt, n_t = resample_edges(ping_time, ping_time_bin, sorted_valid=True)
+    ping_time, ns, e0, dt, n_t = grid
     C, P, S = d.shape
-    if range_var_max is not None:
-        r_cap = _parse_x_bin(range_var_max) + 1e-8
-    elif depth is not None and rng_d.reach_bound is not None:
-        r_cap = rng_d.reach_bound
-    elif depth is None and getattr(src, "reach_bound", None) is not None:
-        r_cap = src.reach_bound  # host-side bound: no device reduction, no wait
-    else:
-        coef = src.coef
-        reach = (S - 1) * coef[..., _lib.CF_RA] * coef[..., _lib.CF_RB] + coef[..., _lib.CF_R0]
-        if depth is not None:  # offset + scale * [r0, reach], whichever end is the deeper one
-            reach = torch.fmax(depth[1] + depth[0] * reach, depth[1] + depth[0] * coef[..., _lib.CF_R0]) * (1 + 1e-6)
-        r_cap = float(torch.nan_to_num(reach, nan=float("-inf")).max().item())
+    # (the host-side bound of the variable that is binned: no device reduction, no wait)
+    r_cap = range_cap(range_var_max, rng_d.reach_bound if depth is not None else getattr(src, "reach_bound", None),
+                      src.coef, S, affine=depth)
     first_bin = last_bin = 0
     if _shard is not None:
         if isinstance(_grid, str):  # "probe": this rank could take the route (_sharded_deferred puts it to the vote)
             return ns, dt, r_cap
         e0, n_t, first_bin, last_bin, r_cap = _grid  # (the whole dataset's: the same on every rank)
-    n_cap = len(np.arange(0, r_cap + range_bin_m, range_bin_m)) - 1 if np.isfinite(r_cap) else 0
+    n_cap = n_range_bins(r_cap, range_bin_m)
     if n_cap < 1:
         return None
-    bin_start = ops.time_bin_offsets(ops.ping_time_facts(ping_time)[2], e0, dt, n_t)
-    res = None
-    try:
+    bin_start = time_bin_start(ping_time, e0, dt, n_t)
+
+    def launch():
         if depth is not None:
             # EPA_DEPTH_WITH_MVBS=1: the depth array is written by this pass as well (+8 B/sample here instead of the
             # 4 + 8 of epa_depth_rows when somebody reads it later); default: it stays lazy
-            res = ops.sv_mvbs_fused_depth(src.raw, src.coef, depth[0], depth[1], bin_start, n_t, range_bin_m, n_cap,
-                                          fill_value=fill_value, dtype=src.dtype, want_partials=_shard is not None,
-                                          want_depth=not rng_d.materialized and os.environ.get("EPA_DEPTH_WITH_MVBS") == "1")
-        else:
-            res = ops.sv_mvbs_fused(src.raw, src.coef, bin_start, n_t, range_bin_m, n_cap, cal_flags=src.flags, skipna=True,
-                                    closed="left", fill_value=fill_value, dtype=src.dtype, want_range_stats=True,
-                                    want_partials=_shard is not None)
-    except _lib.EpaError:  # e.g. a range grid too fine for the LDS accumulators
-        pass
+            return ops.sv_mvbs_fused_depth(src.raw, src.coef, depth[0], depth[1], bin_start, n_t, range_bin_m, n_cap,
+                                           fill_value=fill_value, dtype=src.dtype, want_partials=_shard is not None,
+                                           want_depth=not rng_d.materialized and os.environ.get("EPA_DEPTH_WITH_MVBS") == "1")
+        return ops.sv_mvbs_fused(src.raw, src.coef, bin_start, n_t, range_bin_m, n_cap, cal_flags=src.flags, skipna=True,
+                                 closed="left", fill_value=fill_value, dtype=src.dtype, want_range_stats=True,
+                                 want_partials=_shard is not None)
+
     # served by the generic kernel (a handful of pings, a grid beyond the LDS)?  It leaves no range statistics, which
     # every later step asks for -- K1 does, on the plain route.  (Known on the host: epa_last_range_stats_filled.)
-    declined = res is None or not res["range_stats_filled"]
-    done = None
-    if _shard is not None:  # the plain route runs other collectives: every rank takes it if any has to -- the vote rides
-        done = _shard.finish(None if declined else res, first_bin, last_bin, fill_value,  # with the exchange plan's message
-                             shape=(C, n_t, n_cap), device=src.raw.device)
-        declined = done is None
-    if declined:
+    got = launch_or_decline(launch, served=lambda res: res["range_stats_filled"], shard=_shard,
+                            vote=(first_bin, last_bin, fill_value, (C, n_t, n_cap), src.raw.device))
+    if got is None:
         return None
+    res, mv_full, lo = got
     rng = rng_d if depth is not None else src.echo_range  # (the statistics are the binned variable's)
     d.fulfil(res["Sv"])
     if res.get("depth") is not None:
         rng_d.fulfil(res["depth"])
     # the three numbers start their way to the host now, on a side stream behind THIS kernel: whoever reads them later
-    # (the assembly below, the next reader of the echo_range statistics) does not wait for kernels launched after it
+    # (the assembly, the next reader of the echo_range statistics) does not wait for kernels launched after it
     stats = ops.fetch_async(res["range_stats"])
     rng.set_stats(stats)
-    if _shard is not None:
-        # nanmax(echo_range) of the whole dataset: all-reduced (MAX) where it lies, behind the kernel; cut bins: totals
-        # over all ranks, reported by the lowest holder (one all-reduce in HBM) -- the host waits for neither
-        gmax = ops.fetch_async(_shard.range_max_device(res["range_stats"][1:2].clone())) if range_var_max is None else None
-        mv_full, lo = done
-        e0, n_t = e0 + lo * dt, mv_full.shape[1]
-        ds_Sv = ds_Sv.copy()
-        del res, done
-
-        def build_shard():
-            return _shard_assemble(ds_Sv, mv_full, n_cap, gmax.item() if gmax is not None else r_cap, r_cap,
-                                   range_var_max, stats.tolist()[2], ping_time, e0, dt, n_t, range_var, range_bin_m,
-                                   ping_time_bin)
-
-        return DeferredDataset(build_shard) if defer_mvbs_enabled() else build_shard()
-    ds_Sv, mv_full = ds_Sv.copy(), res["MVBS"]  # (snapshot: see _mvbs_of_array_without_waiting)
-    del res
-
-    def build():
-        lo, hi, n_nan_range = stats.tolist()
-        rmax = hi if range_var_max is None else r_cap
-        r_edges = np.arange(0, rmax + range_bin_m, range_bin_m) if np.isfinite(rmax) else np.zeros(1)
-        n_r = len(r_edges) - 1
-        # no valid range / an empty grid: the plain route raises or returns what the reference would; a maximum beyond the
-        # conservative grid the kernel ran on (it must not happen: the bound is an upper one): binned again, exactly
-        if n_r < 1 or n_r > n_cap:
-            return _mvbs_plain(ds_Sv, range_var, range_bin_m, ping_time_bin, True, fill_value, "left", range_var_max, None, allow_defer=False)
-        if n_nan_range > 0:
-            logging.warning(f"The ```{range_var}``` coordinate array contain NaNs. {_AGG_MSG}")
-        mvbs_t = mv_full[..., :n_r].contiguous() if n_r != n_cap else mv_full
-        return _assemble_mvbs(ds_Sv, mvbs_t, "channel", ping_time, e0, dt, n_t, r_edges, range_var, range_bin_m,
-                              ping_time_bin, "left")
-
-    return DeferredDataset(build) if defer_mvbs_enabled() else build()
+    # on a shard nanmax(echo_range) of the whole dataset: all-reduced (MAX) where it lies, behind the kernel -- no host wait
+    gmax = ops.fetch_async(_shard.range_max_device(res["range_stats"][1:2].clone())) \
+        if _shard is not None and range_var_max is None else None
+    plain = None if _shard is not None else _plain_fallback(range_var, range_bin_m, ping_time_bin, fill_value, range_var_max)
+    return deferred_mvbs(ds_Sv, mv_full, n_cap, lambda: (stats.tolist()[1] if gmax is None else gmax.item(), stats.tolist()[2]),
+                         range_var_max, r_cap, (ping_time, e0 + lo * dt, dt), range_var, range_bin_m, ping_time_bin, plain,
+                         defer=defer_mvbs_enabled())
 
 
 def _mvbs_of_deferred_clean(ds_Sv, range_var, range_bin_m, ping_time_bin, fill_value, range_var_max, _shard=None, _grid=None):
@@ -393,27 +315,17 @@ def _mvbs_of_deferred_clean(ds_Sv, range_var, range_bin_m, ping_time_bin, fill_v
     sv_da, rng_da = ds_Sv["Sv"], ds_Sv[range_var]
     d = sv_da.data
     src = d.source if isinstance(d, LazyDeviceArray) and not d.materialized else None
-    dims = ("channel", "ping_time", "range_sample")
     if not isinstance(src, DenoiseSource) or d is not src.lazy("corrected") or src.minmax is not None or not src.intact():
         return None
     p = src.power
-    if rng_da.data is not p.echo_range or tuple(sv_da.dims) != dims or tuple(rng_da.dims) != dims \
-            or p.echo_range.coef_rows() is not p.coef:
+    if not _binned_through_rows(p, sv_da, rng_da, p.echo_range):
         return None
-    ping_time = np.asarray(ds_Sv["ping_time"].values).astype("datetime64[ns]", copy=False)
-    ns, sorted_valid, _ = ops.ping_time_facts(ping_time, want_device=False)
-    if not sorted_valid:  # unsorted pings, NaT
+    grid = sorted_time_grid(ds_Sv["ping_time"].values, ping_time_bin)
+    if grid is None:
         return None
-    e0, dt, n_t = resample_edges(ping_time, ping_time_bin, sorted_valid=True)
+    ping_time, ns, e0, dt, n_t = grid
     C, P, S = d.shape
-    if range_var_max is not None:
-        r_cap = _parse_x_bin(range_var_max) + 1e-8
-    elif getattr(p, "reach_bound", None) is not None:
-        r_cap = p.reach_bound
-    else:
-        coef = p.coef
-        reach = torch.nan_to_num((S - 1) * coef[..., _lib.CF_RA] * coef[..., _lib.CF_RB] + coef[..., _lib.CF_R0], nan=float("-inf"))
-        r_cap = float(reach.max().item())
+    r_cap = range_cap(range_var_max, getattr(p, "reach_bound", None), p.coef, S)
     first_bin = last_bin = 0
     if _shard is not None:
         if src.global_rmax is None:  # (pass 1 did not run as a shard's: the plain route -- by the vote, if on this rank only)
@@ -421,59 +333,33 @@ def _mvbs_of_deferred_clean(ds_Sv, range_var, range_bin_m, ping_time_bin, fill_v
         if isinstance(_grid, str):  # "probe": see _mvbs_of_deferred_sv
             return ns, dt, r_cap
         e0, n_t, first_bin, last_bin, r_cap = _grid
-    n_cap = len(np.arange(0, r_cap + range_bin_m, range_bin_m)) - 1 if np.isfinite(r_cap) else 0
+    n_cap = n_range_bins(r_cap, range_bin_m)
     if n_cap < 1:
         return None
-    bin_start = ops.time_bin_offsets(ops.ping_time_facts(ping_time)[2], e0, dt, n_t)
-    res = None
-    try:
-        res = ops.sv_denoise_mvbs(p.raw, p.coef, src.a2, src.noise, src.ping_num, float(src.snr), bin_start, n_t,
-                                  range_bin_m, n_cap, flags=p.flags, dtype=p.dtype, skipna=True, closed="left",
-                                  fill_value=fill_value, want_noise=True, want_corrected=True, want_minmax=True,
-                                  minmax_async=True, ping_phase=src.ping_phase, want_partials=_shard is not None)
-    except _lib.EpaError:  # e.g. a range grid too fine for the LDS accumulators
-        pass
-    done = None
-    if _shard is not None:  # (the vote on the fallback rides with the exchange plan's message)
-        done = _shard.finish(res, first_bin, last_bin, fill_value, shape=(C, n_t, n_cap), device=p.raw.device)
-    if (done is None) if _shard is not None else res is None:
+    bin_start = time_bin_start(ping_time, e0, dt, n_t)
+    got = launch_or_decline(
+        lambda: ops.sv_denoise_mvbs(p.raw, p.coef, src.a2, src.noise, src.ping_num, float(src.snr), bin_start, n_t,
+                                    range_bin_m, n_cap, flags=p.flags, dtype=p.dtype, skipna=True, closed="left",
+                                    fill_value=fill_value, want_noise=True, want_corrected=True, want_minmax=True,
+                                    minmax_async=True, ping_phase=src.ping_phase, want_partials=_shard is not None),
+        shard=_shard, vote=(first_bin, last_bin, fill_value, (C, n_t, n_cap), p.raw.device))
+    if got is None:
         return None
+    res, mv_full, lo = got
     src.install(res)
-    rng = p.echo_range
-    if _shard is not None:  # cut bins: totals over all ranks, reported by the lowest holder (one all-reduce in HBM)
-        mv_full, lo = done
-        e0, n_t = e0 + lo * dt, mv_full.shape[1]
-        ds_Sv, gmax = ds_Sv.copy(), src.global_rmax
-        del res, done
+    # the statistics of the range were left by pass 1 and have been on their way to the host since then; on a shard the
+    # maximum is the one over all shards, all-reduced behind pass 1 (-inf: no valid range on any), the NaN count local
+    rng, gmax = p.echo_range, src.global_rmax if _shard is not None else None
 
-        def build_shard():
-            st = rng.cached_stats()  # (local: the NaN-coordinate warning)
-            rmax = float(gmax.item())
-            return _shard_assemble(ds_Sv, mv_full, n_cap, rmax if rmax > float("-inf") else float("nan"), r_cap,
-                                   range_var_max, st[2] if st is not None else 0, ping_time, e0, dt, n_t, range_var,
-                                   range_bin_m, ping_time_bin)
+    def stats():
+        st = rng.cached_stats()
+        if gmax is None:
+            return st[1:] if st is not None else None
+        return float(gmax.item()), st[2] if st is not None else 0
 
-        return DeferredDataset(build_shard) if defer_mvbs_enabled() else build_shard()
-    ds_Sv, mv_full = ds_Sv.copy(), res["MVBS"]  # (snapshot: see _mvbs_of_array_without_waiting)
-    del res
-
-    def build():
-        stats = rng.cached_stats()  # left by pass 1, on their way to the host since then
-        if stats is None:
-            return _mvbs_plain(ds_Sv, range_var, range_bin_m, ping_time_bin, True, fill_value, "left", range_var_max, None, allow_defer=False)
-        lo, hi, n_nan_range = stats
-        rmax = hi if range_var_max is None else r_cap
-        r_edges = np.arange(0, rmax + range_bin_m, range_bin_m) if np.isfinite(rmax) else np.zeros(1)
-        n_r = len(r_edges) - 1
-        if n_r < 1 or n_r > n_cap:
-            return _mvbs_plain(ds_Sv, range_var, range_bin_m, ping_time_bin, True, fill_value, "left", range_var_max, None, allow_defer=False)
-        if n_nan_range > 0:
-            logging.warning(f"The ```{range_var}``` coordinate array contain NaNs. {_AGG_MSG}")
-        mvbs_t = mv_full[..., :n_r].contiguous() if n_r != n_cap else mv_full
-        return _assemble_mvbs(ds_Sv, mvbs_t, "channel", ping_time, e0, dt, n_t, r_edges, range_var, range_bin_m,
-                              ping_time_bin, "left")
-
-    return DeferredDataset(build) if defer_mvbs_enabled() else build()
+    plain = None if _shard is not None else _plain_fallback(range_var, range_bin_m, ping_time_bin, fill_value, range_var_max)
+    return deferred_mvbs(ds_Sv, mv_full, n_cap, stats, range_var_max, r_cap, (ping_time, e0 + lo * dt, dt), range_var,
+                         range_bin_m, ping_time_bin, plain, defer=defer_mvbs_enabled())
 
 
 def _assemble_mvbs(ds_Sv, mvbs_t, dim_0, ping_time, e0, dt, n_t, r_edges, range_var, range_bin_m,

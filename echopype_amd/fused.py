@@ -10,16 +10,17 @@ reads it; ``materialize_echo_range=True`` runs the two calls instead).  The fuse
 calls as well -- same results either way.
 """
 import numpy as np
-import torch
 
 from . import _lib, ops
 from .calibrate.api import CALIBRATOR, _compute_cal, _finalize_cal_ds
 from .clean.api import remove_background_noise
 from .clean.utils import add_remove_background_noise_attrs, extract_dB
 from .commongrid.api import _assemble_mvbs, compute_MVBS
+from .commongrid.deferred import (CPS, deferred_mvbs, launch_or_decline, n_range_bins, range_cap, range_edges,
+                                  sorted_time_grid, time_bin_start)
 from .commongrid.utils import _parse_x_bin, resample_edges
 from .utils.prov import echopype_prov_attrs, insert_processing_level
-from .xr_lite import DataArray, Dataset, DeferredDataset, DeviceArray, defer_mvbs_enabled, xarray_io
+from .xr_lite import DataArray, Dataset, DeviceArray, defer_mvbs_enabled, xarray_io
 
 
 @xarray_io()
@@ -54,27 +55,17 @@ def compute_Sv_MVBS(echodata, *, range_bin="20m", ping_time_bin="20s", skipna=Tr
     cal._check_echodata_backscatter_size()
     raw, coef, flags, tau_eff = cal._power_inputs("Sv")
     C, P, S = raw.shape
-    ping_time = np.asarray(cal.beam["ping_time"].values).astype("datetime64[ns]", copy=False)
-    ns, sorted_valid, _ = ops.ping_time_facts(ping_time, want_device=False)
-    if ns.size and not sorted_valid:  # unsorted, or NaT (INT64_MIN)
+    grid = sorted_time_grid(cal.beam["ping_time"].values, ping_time_bin)
+    if grid is None:  # unsorted pings, NaT (INT64_MIN), no ping at all
         if _shard is not None:
             raise NotImplementedError("a ping shard needs sorted, valid ping times")
-        ds_Sv = _compute_cal("Sv", echodata, **cal_kw)  # unsorted / NaT pings: generic path
+        ds_Sv = _compute_cal("Sv", echodata, **cal_kw)  # generic path
         return ds_Sv, compute_MVBS(ds_Sv, **mv_kw)
-    e0, dt, n_t = resample_edges(ping_time, ping_time_bin, sorted_valid=True)
-    first_bin = 0
+    ping_time, ns, e0, dt, n_t = grid
+    first_bin = last_bin = 0
 
-    # range grid np.arange(0, nanmax(echo_range) + bin, bin) (api.py:108-115): run on a conservative
-    # grid (largest range any row can reach), get nanmax(echo_range) back as a by-product, trim
-    if range_var_max is not None:
-        r_cap = _parse_x_bin(range_var_max) + 1e-8
-    else:
-        r_cap = cal._host_reach_bound(S)  # from host copies of sample_interval / sound_speed: no wait for the GPU
-        if r_cap is None:  # parameters in HBM only: reduced on the device, one scalar comes back
-            reach = (S - 1) * coef[..., _lib.CF_RA] * coef[..., _lib.CF_RB] + coef[..., _lib.CF_R0]
-            reach = torch.nan_to_num(reach, nan=float("-inf"))
-            r_cap = float(reach.max().item())
-            r_cap = r_cap if r_cap > float("-inf") else float("nan")
+    # the conservative range grid (commongrid/deferred.py); the host bound: from host copies of sample_interval / sound_speed
+    r_cap = range_cap(range_var_max, cal._host_reach_bound(S) if range_var_max is None else None, coef, S)
     if _shard is not None:
         # the time grid of the whole dataset (this shard covers global bins first_bin .. last_bin) and its range cap:
         # ONE control message
@@ -83,68 +74,58 @@ def compute_Sv_MVBS(echodata, *, range_bin="20m", ping_time_bin="20s", skipna=Tr
         e0, n_t = e0 + first_bin * dt, last_bin - first_bin + 1
         if range_var_max is None:
             r_cap = g_cap
-    bin_start = ops.time_bin_offsets(ops.ping_time_facts(ping_time)[2], e0, dt, n_t)
-    n_cap = len(np.arange(0, r_cap + range_bin_m, range_bin_m)) - 1 if np.isfinite(r_cap) else 0
-    # degenerate grid (one sample per ping, no valid range) or a kernel that declines (e.g. a range grid too fine for the
-    # LDS accumulators): the two calls deal with it.  On a shard the fallback changes the collectives that follow, so
-    # the decision is taken ONCE, together, before any rank returns: every rank takes it if any rank must.
-    res = None
-    if n_cap >= 1:
-        try:
-            res = ops.sv_mvbs_fused(raw, coef, bin_start, n_t, range_bin_m, n_cap, cal_flags=flags, skipna=True,
-                                    closed="left", fill_value=fill_value, dtype=cal.dtype, want_range_max=True,
-                                    want_partials=_shard is not None)
-        except _lib.EpaError:
-            pass
-    # (on a shard the plan of the cut-bin exchange and the vote on the fallback travel in ONE control message)
-    done = None if _shard is None else _shard.finish(res, first_bin, last_bin, fill_value, shape=(C, n_t, n_cap),
-                                                     device=raw.device)
-    if (res is None) if _shard is None else done is None:
+    bin_start = time_bin_start(ping_time, e0, dt, n_t)
+    n_cap = n_range_bins(r_cap, range_bin_m)
+
+    def launch():  # (a degenerate grid -- one sample per ping, no valid range -- declines like the kernel would)
+        return None if n_cap < 1 else ops.sv_mvbs_fused(
+            raw, coef, bin_start, n_t, range_bin_m, n_cap, cal_flags=flags, skipna=True, closed="left",
+            fill_value=fill_value, dtype=cal.dtype, want_range_max=True, want_partials=_shard is not None)
+
+    # declined: the two calls deal with it (on a shard: every rank, the collectives that follow differ)
+    got = launch_or_decline(launch, shard=_shard, vote=(first_bin, last_bin, fill_value, (C, n_t, n_cap), raw.device))
+    if got is None:
         ds_Sv = _compute_cal("Sv", echodata, _file=_file, **cal_kw)
         return ds_Sv, compute_MVBS(ds_Sv, **mv_kw)
+    res, mv_full, lo = got
     # nanmax(echo_range) stays in HBM: on a shard it is all-reduced (MAX) there, behind the kernel; the host reads it
-    # when the MVBS dataset is first used (DeferredDataset) -- nothing in this call waits for the GPU
+    # when the MVBS dataset is first used -- nothing in this call waits for the GPU
     rmax_t = res["range_max"]
     if _shard is not None and range_var_max is None:
         rmax_t = _shard.range_max_device(rmax_t)
     rmax_f = ops.fetch_async(rmax_t)  # (on its way to the host behind this kernel / all-reduce, on a side stream)
-    if _shard is not None:  # bins cut by a shard edge: totals over all ranks, reported by the lowest holder
-        res["MVBS"], lo = done
-        e0, n_t = e0 + lo * dt, res["MVBS"].shape[1]
 
-    dims = ("channel", "ping_time", "range_sample")
-    ds_Sv = Dataset(coords={k: cal.beam.coords[k] for k in dims})
-    ds_Sv["Sv"] = DataArray(DeviceArray(res["Sv"]), dims)
-    # echo_range is not written: the variable is lazy (coefficient rows + the raw samples' NaN pattern; epa_range_power
-    # on first read), as after compute_Sv
-    ds_Sv.attrs["echo_range_form"] = "echo_range[c,p,s] = s * sample_interval[c,p] * sound_speed[c,p] / 2 (NaN where Sv input was NaN)"
+    # (echo_range is not written: coefficient rows + the raw samples' NaN pattern; epa_range_power on first read)
+    ds_Sv = _sv_dataset(cal, echodata, res["Sv"], None, raw, coef, flags, tau_eff, waveform_mode, encode_mode,
+                        range_last=True)
+    # off a shard a trim that cannot be done bins again from the Sv array, exactly: the public call on the snapshot
+    return ds_Sv, deferred_mvbs(ds_Sv, mv_full, n_cap,
+                                lambda: (float(rmax_f.item()) if range_var_max is None else r_cap, 0), range_var_max,
+                                r_cap, (ping_time, e0 + lo * dt, dt), "echo_range", range_bin_m, ping_time_bin,
+                                fallback=(lambda ds: compute_MVBS(ds, **mv_kw)) if _shard is None else None,
+                                defer=defer_mvbs_enabled())
+
+
+def _sv_dataset(cal, echodata, sv_t, range_t, raw, coef, flags, tau_eff, waveform_mode, encode_mode, range_last=False):
+    """The Sv dataset compute_Sv would return for the array ``sv_t`` of a power-sample calibrator: ``echo_range`` the
+    array ``range_t``, or lazy (None), as after compute_Sv.  (``range_last``: the variable goes in after the
+    parameters, where compute_Sv_MVBS has always had it.)"""
+    ds_Sv = Dataset(coords={k: cal.beam.coords[k] for k in CPS})
+    ds_Sv["Sv"] = DataArray(DeviceArray(sv_t), CPS)
+    echo_range = DataArray(DeviceArray(range_t) if range_t is not None else cal._lazy_power_range(raw, coef, flags), CPS)
+    if not range_last:
+        ds_Sv["echo_range"] = echo_range
+    if range_t is None:
+        ds_Sv.attrs["echo_range_form"] = ("echo_range[c,p,s] = s * sample_interval[c,p] * sound_speed[c,p] / 2 "
+                                          "(NaN where Sv input was NaN)")
     ds_Sv["sample_interval"] = cal.beam["sample_interval"]
     if tau_eff is not None:
         ds_Sv["tau_effective"] = DataArray(np.asarray(tau_eff), ("channel",))
     ds_Sv["frequency_nominal"] = cal.beam["frequency_nominal"]
     ds_Sv = cal._add_params_to_output(ds_Sv)
-    ds_Sv["echo_range"] = DataArray(cal._lazy_power_range(raw, coef, flags), dims)
-    ds_Sv = _finalize_cal_ds(ds_Sv, "Sv", echodata, waveform_mode, encode_mode)
-
-    ds_snap, mv_full = ds_Sv.copy(), res["MVBS"]  # (what the assembly needs, as it is NOW; sums / counts are let go)
-    del res
-
-    def build():
-        rmax = r_cap if range_var_max is not None else float(rmax_f.item())
-        if not np.isfinite(rmax):  # no valid echo_range at all (on any rank): the reference's grid does not exist
-            raise ValueError("range bins are empty: the range variable holds no valid values")
-        r_edges = np.arange(0, rmax + range_bin_m, range_bin_m)
-        n_r = len(r_edges) - 1
-        if n_r > n_cap:  # (it must not happen: r_cap bounds every row's reach from above)
-            if _shard is not None:
-                raise RuntimeError(f"nanmax(echo_range) = {rmax} lies beyond the range grid the shards agreed on "
-                                   f"({n_cap} bins of {range_bin_m} m)")
-            return compute_MVBS(ds_snap, **{**mv_kw, "_shard": None})  # binned again from the Sv array, exactly
-        mvbs_t = mv_full[..., :n_r].contiguous() if n_r != n_cap else mv_full
-        return _assemble_mvbs(ds_snap, mvbs_t, "channel", ping_time, e0, dt, n_t, r_edges, "echo_range", range_bin_m,
-                              ping_time_bin, "left")
-
-    return ds_Sv, (DeferredDataset(build) if defer_mvbs_enabled() else build())
+    if range_last:
+        ds_Sv["echo_range"] = echo_range
+    return _finalize_cal_ds(ds_Sv, "Sv", echodata, waveform_mode, encode_mode)
 
 
 @xarray_io()
@@ -211,13 +192,9 @@ def compute_Sv_clean_MVBS(echodata, ping_num, range_sample_num, *, background_no
         noise_max=float("nan") if nmax is None else float(nmax), want_range_max=True)
     e0, dt, n_t = resample_edges(ping_time, ping_time_bin)
     bin_start = ops.time_bin_offsets(ops.to_device(ns), e0, dt, n_t, closed=closed)
-    if range_var_max is not None:
-        rmax = _parse_x_bin(range_var_max) + 1e-8
-    if not np.isfinite(rmax):
-        return separate_calls()
-    r_edges = np.arange(0, rmax + range_bin_m, range_bin_m)
+    r_edges = range_edges(range_cap(range_var_max, rmax), range_bin_m)  # (rmax: waited for, by design)
     n_r = len(r_edges) - 1
-    if n_r < 1:  # degenerate grid: the separate calls return the empty MVBS the reference would
+    if n_r < 1:  # no valid range, or a degenerate grid: the separate calls raise / return the empty MVBS the reference would
         return separate_calls()
     try:
         res = ops.sv_denoise_mvbs(raw, coef, alpha2, noise, ping_num, float(snr), bin_start, n_t, range_bin_m,
@@ -227,27 +204,14 @@ def compute_Sv_clean_MVBS(echodata, ping_num, range_sample_num, *, background_no
     except _lib.EpaError:  # e.g. a range grid too fine for the LDS accumulators
         return separate_calls()
 
-    dims = ("channel", "ping_time", "range_sample")
-    ds_Sv = Dataset(coords={k: cal.beam.coords[k] for k in dims})
-    ds_Sv["Sv"] = DataArray(DeviceArray(sv_t), dims)
-    have_range = materialize_echo_range
-    ds_Sv["echo_range"] = DataArray(DeviceArray(res["echo_range"]) if have_range else
-                                    cal._lazy_power_range(raw, coef, flags), dims)
-    if not have_range:
-        ds_Sv.attrs["echo_range_form"] = ("echo_range[c,p,s] = s * sample_interval[c,p] * sound_speed[c,p] / 2 "
-                                          "(NaN where Sv input was NaN)")
-    ds_Sv["sample_interval"] = cal.beam["sample_interval"]
-    if tau_eff is not None:
-        ds_Sv["tau_effective"] = DataArray(np.asarray(tau_eff), ("channel",))
-    ds_Sv["frequency_nominal"] = cal.beam["frequency_nominal"]
-    ds_Sv = cal._add_params_to_output(ds_Sv)
-    ds_Sv = _finalize_cal_ds(ds_Sv, "Sv", echodata, waveform_mode, encode_mode)
+    ds_Sv = _sv_dataset(cal, echodata, sv_t, res["echo_range"] if materialize_echo_range else None, raw, coef, flags,
+                        tau_eff, waveform_mode, encode_mode)
     mm = res["minmax"]  # actual_range of both outputs comes out of the kernel: no extra sweep
     outs = [("Sv_corrected", res["Sv_corrected"], "corrected", mm[2:4])]
     if keep_Sv_noise:
         outs.insert(0, ("Sv_noise", res["Sv_noise"], "noise", mm[0:2]))
     for name, t, kind, rng_mm in outs:  # clean/api.py:490-502
-        ds_Sv[name] = add_remove_background_noise_attrs(DataArray(DeviceArray(t), dims), kind, ping_num,
+        ds_Sv[name] = add_remove_background_noise_attrs(DataArray(DeviceArray(t), CPS), kind, ping_num,
                                                         range_sample_num, snr, nmax, rng_mm)
     prov = echopype_prov_attrs(process_type="processing")
     prov["processing_function"] = "clean.remove_background_noise"
