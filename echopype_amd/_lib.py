@@ -48,7 +48,6 @@ CCP = ("sample_interval", "tau_nominal", "transmit_power", "sound_speed", "absor
        "sa_correction", "z_er", "z_et", "angle_offset_alongship", "angle_offset_athwartship", "beamwidth_alongship",
        "beamwidth_athwartship")  # enum epa_ccoef_param
 EK80_NFFT = 2048
-APPLY_MASKS_WS_DOUBLES = 131072  # EPA_APPLY_MASKS_WS_DOUBLES
 SEAFLOOR_STATE_WORDS = 16  # EPA_SEAFLOOR_STATE_WORDS
 SHOAL_STATE_WORDS = 8  # EPA_SHOAL_STATE_WORDS
 SHOAL_QUEUE_BOXES = 4096  # EPA_SHOAL_QUEUE_BOXES
@@ -95,6 +94,10 @@ SIGNATURES = {
     "epa_timer_start": [_vp, _vp],
     "epa_timer_stop": [_vp, _vp],
     "epa_timer_elapsed_ms": [_vp, ctypes.POINTER(ctypes.c_float)],
+    "epa_scratch_bytes": [ctypes.c_char_p, _ll, _ll, _ll, ctypes.POINTER(_sz)],
+    "epa_mvbs_needs_partials": [_i, _i, _i, _i, ctypes.POINTER(_i)],
+    "epa_regrid_needs_global_flags": [_i, ctypes.POINTER(_i)],
+    "epa_sv_power_vectorized": [_vp, _i, _i, ctypes.POINTER(_i)],
     "epa_power_coef_ek": [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp,
                           _vp, _i, _vp, _i, _i, _vp, _vp],
     "epa_pulse_table_lookup": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],

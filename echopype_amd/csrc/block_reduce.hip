@@ -536,6 +536,12 @@ struct Plan {
   unsigned cnt_off, tab_off;
 };
 
+constexpr size_t kAccLdsMax = 128 * 1024;  // the most LDS for the (sum, count) accumulators of one time bin
+constexpr long long kSplitBelowGroups = 1024;  // fewer (channel, time bin) groups: the pings of a bin are split
+// the accumulators of one time bin: sums (rounded up to 16 bytes), then counts
+inline size_t acc_sum_bytes(int n_rbins, size_t esz) { return ((size_t)n_rbins * esz + 15) & ~(size_t)15; }
+inline size_t acc_bytes_needed(int n_rbins, size_t esz) { return acc_sum_bytes(n_rbins, esz) + (size_t)n_rbins * sizeof(uint32_t); }
+
 template <typename T>
 Plan make_plan(int C, int P, int S, int n_tbins, int n_rbins, bool aligned16) {
   Plan pl;
@@ -544,16 +550,16 @@ Plan make_plan(int C, int P, int S, int n_tbins, int n_rbins, bool aligned16) {
     const int v = atoi(e);
     if ((v == 1) || (v == 2 && S % 2 == 0 && aligned16) || (v == 4 && S % 4 == 0 && aligned16)) pl.vec = v;
   }
-  const size_t sum_bytes = ((size_t)n_rbins * sizeof(T) + 15) & ~(size_t)15;
-  const size_t need = sum_bytes + (size_t)n_rbins * sizeof(uint32_t);
-  pl.use_lds = need <= 128 * 1024;
+  const size_t sum_bytes = acc_sum_bytes(n_rbins, sizeof(T));
+  const size_t need = acc_bytes_needed(n_rbins, sizeof(T));
+  pl.use_lds = need <= kAccLdsMax;
   const size_t acc_bytes = pl.use_lds ? (need < 64 ? 64 : need) : 64;
   pl.cnt_off = (unsigned)sum_bytes;
   pl.tab_off = (unsigned)((acc_bytes + 15) & ~(size_t)15);
   pl.lds_bytes = pl.tab_off + epa::kMathTabBytes;
   const long long groups = (long long)C * n_tbins;
   pl.nparts = 1;
-  if (groups < 1024) {
+  if (groups < kSplitBelowGroups) {
     const long long avg = n_tbins > 0 ? (P + n_tbins - 1) / n_tbins : P;
     long long want = (2048 + groups - 1) / groups;
     long long maxp = (avg + 7) / 8;
@@ -671,6 +677,17 @@ int check_bins(const char* fn, const int32_t* bin_start, int n_tbins, double ran
 
 }  // namespace
 
+// MAY the reduction of this grid need the caller's sum / count arrays?  A superset of make_plan's two_stage (few groups do
+// not always split the pings: nparts also depends on P), so a caller that allocates on "yes" is always covered.
+extern "C" int epa_mvbs_needs_partials(int C, int n_tbins, int n_rbins, int dtype, int* yes) {
+  EPA_CHECK_ARG(yes != nullptr, "epa_mvbs_needs_partials: yes is NULL");
+  EPA_CHECK_REAL("epa_mvbs_needs_partials", dtype);
+  *yes = ((long long)C * n_tbins < kSplitBelowGroups ||
+          acc_bytes_needed(n_rbins, dtype == EPA_F64 ? sizeof(double) : sizeof(float)) > kAccLdsMax)
+             ? 1 : 0;
+  return EPA_OK;
+}
+
 namespace {
 // keys [min, max, min, max] -> doubles; untouched slots (min key ~0, max key 0) -> NaN
 __global__ void decode_minmax_kernel(double* p) {
@@ -766,6 +783,11 @@ extern "C" int epa_sv_mvbs_fused_i16(const int16_t* raw, const int32_t* n_valid,
                      range_max_out, nullptr, dtype, stream);
 }
 
+// depth_stats_out of epa_sv_mvbs_fused_depth: the statistics in words 0..2, the maximum's key kDepthKeyWord words on
+constexpr int kDepthStatsWords = 64, kDepthKeyWord = 32;
+static_assert(kDepthKeyWord < kDepthStatsWords, "the key's word lies in depth_stats_out");
+size_t epa::scratch::sv_mvbs_fused_depth_stats(long long, long long, long long) { return sizeof(double) * kDepthStatsWords; }
+
 extern "C" int epa_sv_mvbs_fused_depth(const float* raw, const double* coef, const double* depth_scale,
                                        const double* depth_offset, int C, int P, int S, int cal_type,
                                        const int32_t* bin_start, int n_tbins, double range_bin, int n_rbins,
@@ -773,12 +795,12 @@ extern "C" int epa_sv_mvbs_fused_depth(const float* raw, const double* coef, con
                                        uint32_t* cnt_out, double* depth_stats_out, int dtype, epa_stream_t stream) {
   EPA_CHECK_ARG(raw && depth_scale && depth_offset && depth_stats_out, "epa_sv_mvbs_fused_depth: NULL array argument");
   EPA_CHECK_ARG(!depth_out || sv_out, "epa_sv_mvbs_fused_depth: depth_out needs sv_out");
-  // depth_stats_out[32] is the slot of the maximum's key while the kernel runs (decoded into [1]): 256 bytes from the
+  // depth_stats_out[kDepthKeyWord] is the slot of the maximum's key while the kernel runs (decoded into [1]): 256 bytes from the
   // other keys -- every workgroup sends atomics to these words, and two busy words in one cache line cost the launch
   // 15 % (round 6: identical code, 2.37 against 2.05 ms per 0.8 G samples)
   return fused_entry(raw, nullptr, nullptr, coef, C, P, S, cal_type, EPA_FLAG_GUARD_POS | EPA_FLAG_MASK_RANGE, bin_start,
                      nullptr, n_tbins, range_bin, n_rbins, EPA_BIN_SKIPNA, fill_value, sv_out, nullptr, mvbs_out, sum_out,
-                     cnt_out, depth_stats_out + 32, depth_stats_out, dtype, stream, depth_scale, depth_offset, depth_out);
+                     cnt_out, depth_stats_out + kDepthKeyWord, depth_stats_out, dtype, stream, depth_scale, depth_offset, depth_out);
 }
 
 static int fused_entry(const float* raw, const int16_t* raw_i16, const int32_t* n_valid,

@@ -539,6 +539,12 @@ extern "C" int epa_sv_complex_indexed(const void* re, const void* im, int in_dty
                           range_out, prx_out, out_dtype, nullptr, stream);
 }
 
+// the kCwStatSlots {min, max, NaN count} slots the CW kernel merges into (slot = piece & (kCwStatSlots - 1))
+size_t epa::scratch::sv_complex_cw_stats_workspace(long long, long long, long long) {
+  static_assert(EPA_SV_COMPLEX_CW_STATS_WS_DOUBLES == 3 * kCwStatSlots, "header macro and size function");
+  return 3 * sizeof(double) * kCwStatSlots;
+}
+
 extern "C" int epa_sv_complex_cw_stats(const void* re, const void* im, int in_dtype, const double* ccoef, int C, int P,
                                        int S, int B, int cal_type, void* out, void* range_out, void* prx_out,
                                        int out_dtype, double* workspace, double* range_stats_out,

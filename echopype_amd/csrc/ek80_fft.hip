@@ -62,16 +62,20 @@ __host__ __device__ inline size_t ws_spec64(int C, int c) { return 768 + 4 * (si
 __host__ __device__ inline size_t ws_spec32(int C, int c) { return ws_spec64(C, c) + 2 * kN; }
 //   then                kStatSlots x {min, max, NaN count} of the echo_range (merged by f64 atomics; optional)
 constexpr int kStatSlots = 1024;
-__host__ __device__ inline size_t ws_stats(int C) { return 768 + 4 * (size_t)C + (size_t)C * 3 * kN; }
+__host__ __device__ constexpr size_t ws_stats(int C) { return 768 + 4 * (size_t)C + (size_t)C * 3 * kN; }
 //   then                [1 double] counter of deferred (partly-NaN) tiles, then one bit per tile
-__host__ __device__ inline size_t ws_mixed(int C) { return ws_stats(C) + 3 * kStatSlots; }
+__host__ __device__ constexpr size_t ws_mixed(int C) { return ws_stats(C) + 3 * kStatSlots; }
 //   then                per channel {ra, rb, shift, 2 alpha of its first ping} + S values of the time-varied gain
 //                       n log10(R') + 2 alpha R' (tvg_table_kernel)
-__host__ __device__ inline size_t ws_tvg(int C, int P, int S) {
+__host__ __device__ constexpr size_t ws_tvg(int C, int P, int S) {
   return ws_mixed(C) + 2 + ((size_t)C * (size_t)P * ((size_t)S / (kN / 2 + 1) + 1) + 63) / 64;
 }
 //   then                the 128 x {1/c, log10 c} table of fast_log10 (fast_math.h), copied to LDS by every workgroup
-__host__ __device__ inline size_t ws_logtab(int C, int P, int S) { return ws_tvg(C, P, S) + (size_t)C * ((size_t)S + 4); }
+__host__ __device__ constexpr size_t ws_logtab(int C, int P, int S) { return ws_tvg(C, P, S) + (size_t)C * ((size_t)S + 4); }
+//   and that table: the end of the workspace (epa::scratch::sv_complex_fft_workspace)
+constexpr size_t ws_end(int C, int P, int S) { return ws_logtab(C, P, S) + 2 * epa::kLogTabN; }
+static_assert(ws_end(1, 1, 1) == EPA_EK80_FFT_WS_DOUBLES(1, 1, 1) && ws_end(3, 5, 2100) == EPA_EK80_FFT_WS_DOUBLES(3, 5, 2100),
+              "header macro and workspace layout");
 
 __global__ __launch_bounds__(epa::kBlock) void replica_prepare_kernel(const float* __restrict__ replica,
                                                                       const int32_t* __restrict__ off, int C,
@@ -761,6 +765,10 @@ __global__ __launch_bounds__(epa::kBlock) void selftest_correlate_kernel(const C
 
 }  // namespace
 
+size_t epa::scratch::sv_complex_fft_workspace(long long W, long long P, long long S) {
+  return sizeof(double) * ws_end((int)W, (int)P, (int)S);
+}
+
 extern "C" int epa_selftest_correlate(const void* x, int n_tiles, const float* replica, const int32_t* replica_off,
                                       int fft_dtype, void* out, double* workspace, epa_stream_t stream) {
   EPA_CHECK_ARG(x && replica && replica_off && out && workspace, "epa_selftest_correlate: NULL array argument");
@@ -862,6 +870,9 @@ static int sv_complex_fft_entry(const void* re, const void* im, int in_dtype, co
   a.map_words = (int)((ntiles + 31) / 32);
   a.mixed_cnt = reinterpret_cast<unsigned*>(workspace + ws_mixed(W));
   a.mixed_map = a.mixed_cnt + 2;
+  // (the counter and the map end where the gain tables begin: tiles <= S / (kN / 2 + 1) + 1 for every max_taps served)
+  EPA_CHECK_SCRATCH("epa_sv_complex_fft", "workspace (the map of deferred tiles)",
+                    sizeof(double) * ws_mixed(W) + 8 + 4 * (size_t)a.map_words, sizeof(double) * ws_tvg(W, P, S));
   EPA_CHECK_HIP(hipMemsetAsync(a.mixed_cnt, 0, 8 + 4 * (size_t)a.map_words, st));
   double* tvg = workspace + ws_tvg(W, P, S);
   a.tvg = tvg;

@@ -88,6 +88,7 @@ inline int check_launch(const char* what) {
 }
 
 constexpr int kBlock = 256;  // 4 wavefronts of 64
+constexpr int kMinmaxMaxGrid = 1024;  // the most workgroups (= partials in its workspace) of an epa_nanminmax launch
 
 // ---- device math, templated on the compute type ------------------------------------------------
 template <typename T>
@@ -173,6 +174,44 @@ __device__ __forceinline__ float depth_of(float scale, float offset, float range
   const float prod = scale * range;
   return offset + prod;
 }
+
+// ---- scratch buffers: allocated by the caller, sized HERE (epa_scratch_bytes in echopype_amd.h) ----------------------
+// One function per scratch parameter of the ABI, bytes for the sizes (a, b, c) the header's table names, defined in the
+// translation unit that lays the buffer out and written with the constants and helpers its entry uses.  runtime.hip
+// lists them by name.  An entry whose write extent follows from a launch plan checks it against its own function
+// before it launches (EPA_CHECK_SCRATCH): an internal error, never a write past the buffer.
+namespace scratch {
+size_t sv_power_stats_workspace(long long S, long long, long long);               // sv_power.hip
+size_t depth_rows_workspace(long long, long long, long long);                     // reduce_util.hip
+size_t nanminmax_workspace(long long, long long, long long);                      // reduce_util.hip
+size_t range_step_mean_workspace(long long C, long long P, long long);            // reduce_util.hip
+size_t sv_complex_cw_stats_workspace(long long, long long, long long);            // ek80_complex.hip
+size_t sv_complex_fft_workspace(long long W, long long P, long long S);           // ek80_fft.hip
+size_t splitbeam_complex_fft_workspace(long long n, long long, long long);        // splitbeam.hip
+size_t sv_mvbs_fused_depth_stats(long long, long long, long long);                // block_reduce.hip
+size_t apply_masks_workspace(long long, long long, long long);                    // noise_masks.hip
+size_t pool_sv_sum_ws(long long C, long long P, long long S);                     // noise_masks.hip
+size_t pool_sv_cnt_ws(long long C, long long P, long long S);                     // noise_masks.hip
+size_t pool_sv_value_ws_mean(long long C, long long P, long long S);              // noise_masks.hip
+size_t pool_sv_value_ws_median(long long C, long long S, long long);              // noise_masks.hip
+size_t nasc_workspace(long long C, long long n_dbins, long long n_rbins);         // nasc.hip
+size_t seafloor_state(long long, long long, long long);                           // seafloor.hip
+size_t seafloor_angle_mask_work(long long P, long long R, long long);             // seafloor.hip
+size_t seafloor_median_hist(long long, long long, long long);                     // seafloor.hip
+size_t shoal_state(long long, long long, long long);                              // shoal.hip
+size_t shoal_echoview_link_queue(long long, long long, long long);                // shoal.hip
+size_t transient_fielding_todo(long long C, long long P, long long);              // transient.hip
+size_t transient_fielding_count(long long, long long, long long);                 // transient.hip
+size_t transient_matecho_s_hi(long long C, long long P, long long);               // transient.hip
+size_t transient_matecho_flag(long long C, long long P, long long);               // transient.hip
+size_t time_rebuild_tile_workspace(long long N, long long, long long);            // qc.hip
+size_t regrid_mask_out(long long G, long long n_tbins, long long n_rbins);        // mask_grid.hip
+}  // namespace scratch
+
+// `used` bytes are about to be written to a scratch buffer the caller sized as `have` = its scratch:: function
+#define EPA_CHECK_SCRATCH(who, what, used, have)                                                              \
+  EPA_CHECK_ARG((size_t)(used) <= (size_t)(have), "%s: internal error: the launch plan writes %zu bytes of %s, sized %zu", \
+                who, (size_t)(used), what, (size_t)(have))
 
 }  // namespace epa
 

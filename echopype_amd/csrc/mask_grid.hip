@@ -300,6 +300,7 @@ __global__ __launch_bounds__(kBlock) void regrid_sweep_kernel(RegridArgs a) {
 }
 
 constexpr size_t kRegridLdsMax = 128 * 1024;  // the flags of one time bin, 4 bytes per range bin (block_reduce.hip::make_plan)
+inline bool regrid_flags_in_lds(int n_rbins) { return (size_t)n_rbins * 4 <= kRegridLdsMax; }
 
 template <bool AL, bool PER_PING, bool USE_LDS>
 int launch_regrid_sweep(const RegridArgs& a, dim3 grid, hipStream_t st) {
@@ -334,6 +335,17 @@ extern "C" int epa_freq_diff_mask(const void* sv, int C, size_t n, int chan_a, i
   return epa::dispatch_real("epa_freq_diff_mask", dtype, [&](auto tag) {
     return launch_freq_diff<typename decltype(tag)::type>(sv, n, chan_a, chan_b, kWant[cmp], diff, mask_out, st);
   });
+}
+
+// the output cells as whole 32-bit words: regrid_or_global sets a cell's flags through the word that holds it
+size_t epa::scratch::regrid_mask_out(long long G, long long n_tbins, long long n_rbins) {
+  return ((size_t)G * (size_t)n_tbins * (size_t)n_rbins + 3) / 4 * 4;
+}
+// the flags of one time bin (4 bytes per range bin) do not fit in LDS: the sweep sets them in the output itself
+extern "C" int epa_regrid_needs_global_flags(int n_rbins, int* yes) {
+  EPA_CHECK_ARG(yes != nullptr, "epa_regrid_needs_global_flags: yes is NULL");
+  *yes = regrid_flags_in_lds(n_rbins) ? 0 : 1;
+  return EPA_OK;
 }
 
 extern "C" int epa_regrid_mask(const uint8_t* mask, const int32_t* group, int T, int P, int D, const double* range,
@@ -374,7 +386,7 @@ extern "C" int epa_regrid_mask(const uint8_t* mask, const int32_t* group, int T,
 
   const dim3 grid((unsigned)((P + a.chunk - 1) / a.chunk), (unsigned)ctiles, (unsigned)T);
   const bool al = D % 16 == 0 && reinterpret_cast<uintptr_t>(mask) % 16 == 0;
-  const bool lds = (size_t)n_rbins * 4 <= kRegridLdsMax;
+  const bool lds = regrid_flags_in_lds(n_rbins);
   int rc;
   if (range_per_ping && lds) {
     if ((rc = launch_regrid_sweep<true, true>(a, al, grid, st))) return rc;

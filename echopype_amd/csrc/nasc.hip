@@ -201,6 +201,11 @@ extern "C" int epa_geodesic_steps(const double* lat, const double* lon, int P, d
   return epa::check_launch("geodesic_step_kernel");
 }
 
+// one Cell per (channel, distance bin, range bin)
+size_t epa::scratch::nasc_workspace(long long C, long long n_dbins, long long n_rbins) {
+  return sizeof(Cell) * (size_t)C * (size_t)n_dbins * (size_t)n_rbins;
+}
+
 extern "C" int epa_nasc(const void* sv, const void* depth, int C, int P, int S, const int32_t* bin_start,
                         int n_dbins, double range_bin, int n_rbins, unsigned bin_flags, void* workspace,
                         void* nasc_out, void* sv_mean_out, void* h_mean_out, int dtype,
@@ -214,6 +219,7 @@ extern "C" int epa_nasc(const void* sv, const void* depth, int C, int P, int S, 
   const size_t lds = epa::kMathTabBytes + (use_lds ? (size_t)n_rbins * 24 : 0);
   hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)C * n_dbins * n_rbins;
+  EPA_CHECK_SCRATCH("epa_nasc", "workspace", n * sizeof(Cell), epa::scratch::nasc_workspace(C, n_dbins, n_rbins));
   EPA_CHECK_HIP(hipMemsetAsync(workspace, 0, n * sizeof(Cell), st));
   // enough workgroups for 256 CUs whatever the number of distance bins
   const long long cells = (long long)C * n_dbins;

@@ -3622,6 +3622,24 @@ extern "C" int epa_apply_mask(const void* src, const uint8_t* mask, size_t n, si
   });
 }
 
+namespace {
+constexpr int kApplyMasksMaxGrid = 65536;  // the most workgroups of apply_masks_kernel: one {min, max} pair each
+static_assert(EPA_APPLY_MASKS_WS_DOUBLES == 2 * kApplyMasksMaxGrid, "header macro and size function");
+}  // namespace
+size_t epa::scratch::apply_masks_workspace(long long, long long, long long) {
+  return 2 * sizeof(double) * kApplyMasksMaxGrid;
+}
+// epa_pool_sv, nanmean: the f64 sums and int32 counts of every sample
+size_t epa::scratch::pool_sv_sum_ws(long long C, long long P, long long S) { return sizeof(double) * (size_t)C * P * S; }
+size_t epa::scratch::pool_sv_cnt_ws(long long C, long long P, long long S) { return sizeof(int) * (size_t)C * P * S; }
+// epa_pool_sv_value: the layouts at the head of launch_pool_value (the header's macros spell them out), rounded up to whole 8-byte words for nanmean
+size_t epa::scratch::pool_sv_value_ws_mean(long long C, long long P, long long S) {
+  return (EPA_POOL_VALUE_WS_BYTES(C, P, S) + 7) / 8 * 8;
+}
+size_t epa::scratch::pool_sv_value_ws_median(long long C, long long S, long long) {
+  return EPA_POOL_VALUE_MEDIAN_WS_BYTES(C, S);
+}
+
 extern "C" int epa_apply_masks(const void* src, const uint8_t* const* masks, const size_t* mask_periods, int n_masks,
                                size_t n, double fill_value, const void* fill_array, size_t fill_period, void* out,
                                double* workspace, double* minmax_out, int dtype, epa_stream_t stream) {
@@ -3641,9 +3659,12 @@ extern "C" int epa_apply_masks(const void* src, const uint8_t* const* masks, con
   EPA_CHECK_ARG(!minmax_out || workspace, "epa_apply_masks: minmax_out needs the workspace");
   if (n == 0) return EPA_OK;
   const size_t blocks = (n + kBlock - 1) / kBlock;
-  const int grid = (int)(blocks < EPA_APPLY_MASKS_WS_DOUBLES / 2 ? blocks : EPA_APPLY_MASKS_WS_DOUBLES / 2);
+  const int grid = (int)(blocks < (size_t)kApplyMasksMaxGrid ? blocks : kApplyMasksMaxGrid);
   hipStream_t st = (hipStream_t)stream;
   double* part = minmax_out ? workspace : nullptr;
+  if (part)
+    EPA_CHECK_SCRATCH("epa_apply_masks", "workspace", 2 * sizeof(double) * (size_t)grid,
+                      epa::scratch::apply_masks_workspace(0, 0, 0));
   const int rc = epa::dispatch_real("epa_apply_masks", dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     hipLaunchKernelGGL(apply_masks_kernel<T>, dim3(grid), dim3(kBlock), 0, st, (const T*)src, ms, n, (T)fill_value,

@@ -211,6 +211,11 @@ extern "C" int epa_reversal_medians(const int64_t* t, long long N, int win_len, 
   return epa::check_launch("reversal_medians_kernel");
 }
 
+// one running sum per tile of kTile differences
+size_t epa::scratch::time_rebuild_tile_workspace(long long N, long long, long long) {
+  return sizeof(int64_t) * (size_t)((N - 1 + kTile - 1) / kTile);
+}
+
 extern "C" int epa_time_rebuild(const int64_t* t, long long N, const int64_t* facts, const int64_t* sub,
                                 int64_t* tile_workspace, int64_t* out, epa_stream_t stream) {
   EPA_CHECK_ARG(N >= 2, "epa_time_rebuild: N=%lld times, at least 2 are needed", N);

@@ -378,6 +378,23 @@ int epa_rows_piece_launch(const float* mask_raw, const void* x, const double* co
   return EPA_OK;
 }
 
+namespace {
+constexpr int kRowsMaxGrid = 16384;  // the most workgroups of the kernels that stride over (channel, ping) rows
+inline int rows_grid(long long rows) { return (int)(rows < kRowsMaxGrid ? rows : kRowsMaxGrid); }
+static_assert(kPieceSlots * kPieceSlotStride <= 3 * kRowsMaxGrid, "the one-piece kernel's slots fit depth_rows.workspace");
+static_assert(EPA_DEPTH_ROWS_WS_DOUBLES == 3 * kRowsMaxGrid, "header macro and size function");
+}  // namespace
+// depth_rows_kernel: one {min, max, NaN count} partial per workgroup; the one-piece kernel: kPieceSlots padded slots
+size_t epa::scratch::depth_rows_workspace(long long, long long, long long) { return 3 * sizeof(double) * kRowsMaxGrid; }
+// minmax_partial_kernel: one partial per workgroup
+size_t epa::scratch::nanminmax_workspace(long long, long long, long long) {
+  return 3 * sizeof(double) * epa::kMinmaxMaxGrid;
+}
+// step_rows_kernel: one (sum, count) per (channel, ping) row
+size_t epa::scratch::range_step_mean_workspace(long long C, long long P, long long) {
+  return 2 * sizeof(double) * (size_t)C * (size_t)P;
+}
+
 extern "C" int epa_depth_rows(const void* range, const double* coef, const float* mask_raw, const double* scale,
                               const double* offset, int C, int P, int S, void* out, int dtype, double* workspace,
                               double* stats_out, epa_stream_t stream) {
@@ -386,10 +403,13 @@ extern "C" int epa_depth_rows(const void* range, const double* coef, const float
   EPA_CHECK_ARG(!stats_out || workspace, "epa_depth_rows: the statistics need the workspace");
   EPA_CHECK_REAL("epa_depth_rows", dtype);
   const long long rows = (long long)C * P;
-  const int grid = (int)(rows < 16384 ? rows : 16384);
+  const int grid = rows_grid(rows);
   hipStream_t st = (hipStream_t)stream;
   const epa::CoefRow* cf = reinterpret_cast<const epa::CoefRow*>(coef);
   double* part = stats_out ? workspace : nullptr;
+  if (part)
+    EPA_CHECK_SCRATCH("epa_depth_rows", "workspace", 3 * sizeof(double) * (size_t)grid,
+                      epa::scratch::depth_rows_workspace(0, 0, 0));
   {  // one-piece workgroups where the shape takes 16-byte accesses
     const int rc = epa_rows_piece_launch(range ? nullptr : mask_raw, range, coef, scale, offset, rows, S, out, dtype, workspace,
                                          stats_out, st);
@@ -411,7 +431,7 @@ extern "C" int epa_affine_rows(const void* x, const double* scale, const double*
   EPA_CHECK_ARG(x && scale && offset && out, "epa_affine_rows: NULL array argument");
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_affine_rows: sizes must be positive");
   const long long rows = (long long)C * P;
-  const int grid = (int)(rows < 16384 ? rows : 16384);
+  const int grid = rows_grid(rows);
   hipStream_t st = (hipStream_t)stream;
   return epa::dispatch_real("epa_affine_rows", dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
@@ -432,7 +452,8 @@ extern "C" int epa_nanminmax(const void* x, size_t n, int dtype, double* workspa
   EPA_CHECK_ARG(x && workspace && out, "epa_nanminmax: NULL array argument");
   EPA_CHECK_REAL("epa_nanminmax", dtype);
   const size_t blocks = (n + epa::kBlock - 1) / epa::kBlock;
-  const int grid = (int)(blocks < 1024 ? (blocks ? blocks : 1) : 1024);
+  const int grid = (int)(blocks < (size_t)epa::kMinmaxMaxGrid ? (blocks ? blocks : 1) : epa::kMinmaxMaxGrid);
+  EPA_CHECK_SCRATCH("epa_nanminmax", "workspace", 3 * sizeof(double) * (size_t)grid, epa::scratch::nanminmax_workspace(0, 0, 0));
   hipStream_t st = (hipStream_t)stream;
   const int rc = epa::dispatch_real("epa_nanminmax", dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
@@ -450,7 +471,7 @@ extern "C" int epa_range_step_mean(const void* range, int C, int P, int S, int d
   EPA_CHECK_ARG(C > 0 && P > 0 && S > 0, "epa_range_step_mean: sizes must be positive");
   EPA_CHECK_REAL("epa_range_step_mean", dtype);
   const long long rows = (long long)C * P;
-  const int grid = (int)(rows < 16384 ? rows : 16384);
+  const int grid = rows_grid(rows);
   hipStream_t st = (hipStream_t)stream;
   const int rc = epa::dispatch_real("epa_range_step_mean", dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;

@@ -77,6 +77,52 @@ const char* epa_launch_trace(int mode) {
   return epa::g_trace;
 }
 
+// "<entry>.<parameter>" -> the size function of the translation unit that lays the buffer out (epa_internal.h)
+int epa_scratch_bytes(const char* what, long long a, long long b, long long c, size_t* bytes_out) {
+  namespace s = epa::scratch;
+  static const struct {
+    const char* name;
+    size_t (*bytes)(long long, long long, long long);
+  } kTable[] = {
+      {"sv_power_stats.workspace", s::sv_power_stats_workspace},
+      {"depth_rows.workspace", s::depth_rows_workspace},
+      {"nanminmax.workspace", s::nanminmax_workspace},
+      {"range_step_mean.workspace", s::range_step_mean_workspace},
+      {"sv_complex_cw_stats.workspace", s::sv_complex_cw_stats_workspace},
+      {"sv_complex_fft.workspace", s::sv_complex_fft_workspace},
+      {"sv_complex_fft_indexed.workspace", s::sv_complex_fft_workspace},
+      {"selftest_correlate.workspace", s::sv_complex_fft_workspace},
+      {"splitbeam_complex_fft.workspace", s::splitbeam_complex_fft_workspace},
+      {"sv_mvbs_fused_depth.depth_stats_out", s::sv_mvbs_fused_depth_stats},
+      {"apply_masks.workspace", s::apply_masks_workspace},
+      {"pool_sv.sum_ws", s::pool_sv_sum_ws},
+      {"pool_sv.cnt_ws", s::pool_sv_cnt_ws},
+      {"pool_sv_value.ws_mean", s::pool_sv_value_ws_mean},
+      {"pool_sv_value.ws_median", s::pool_sv_value_ws_median},
+      {"nasc.workspace", s::nasc_workspace},
+      {"seafloor.state", s::seafloor_state},
+      {"seafloor_angle_mask.work", s::seafloor_angle_mask_work},
+      {"seafloor_median.hist", s::seafloor_median_hist},
+      {"shoal.state", s::shoal_state},
+      {"shoal_echoview_link.queue", s::shoal_echoview_link_queue},
+      {"transient_fielding.todo", s::transient_fielding_todo},
+      {"transient_fielding.count", s::transient_fielding_count},
+      {"transient_matecho.s_hi", s::transient_matecho_s_hi},
+      {"transient_matecho.flag", s::transient_matecho_flag},
+      {"time_rebuild.tile_workspace", s::time_rebuild_tile_workspace},
+      {"regrid_mask.out", s::regrid_mask_out},
+  };
+  EPA_CHECK_ARG(what != nullptr && bytes_out != nullptr, "epa_scratch_bytes: NULL argument");
+  EPA_CHECK_ARG(a >= 0 && b >= 0 && c >= 0, "epa_scratch_bytes: %s: negative size (%lld, %lld, %lld)", what, a, b, c);
+  for (const auto& e : kTable)
+    if (strcmp(e.name, what) == 0) {
+      *bytes_out = e.bytes(a, b, c);
+      return EPA_OK;
+    }
+  epa::set_error("epa_scratch_bytes: no scratch buffer is called \"%s\"", what);
+  return EPA_EINVAL;
+}
+
 int epa_device_count(int* n) {
   EPA_CHECK_ARG(n != nullptr, "epa_device_count: n is NULL");
   EPA_CHECK_HIP(hipGetDeviceCount(n));

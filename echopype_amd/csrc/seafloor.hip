@@ -397,6 +397,20 @@ extern "C" int epa_seafloor_basic(const void* sv, int dtype, long long P, long l
   });
 }
 
+namespace {
+constexpr int kMedianHistWords = 512;  // two 256-bin histograms of one radix pass (sf_median_hist_kernel)
+}  // namespace
+size_t epa::scratch::seafloor_state(long long, long long, long long) {
+  return sizeof(unsigned long long) * EPA_SEAFLOOR_STATE_WORDS;
+}
+// the window sums along range of both angles over the crop (sf_box_rows_kernel)
+size_t epa::scratch::seafloor_angle_mask_work(long long P, long long R, long long) {
+  return 2 * sizeof(double) * (size_t)P * (size_t)R;
+}
+size_t epa::scratch::seafloor_median_hist(long long, long long, long long) {
+  return sizeof(unsigned long long) * kMedianHistWords;
+}
+
 extern "C" int epa_seafloor_angle_mask(const void* theta, const void* phi, int dtype, long long P, long long S,
                                        long long r0, long long R, int wtheta, int wphi, double ttheta, double tphi,
                                        double* work, unsigned char* mask, unsigned long long* state,
@@ -429,7 +443,7 @@ extern "C" int epa_seafloor_median(const void* sv, int dtype, long long P, long 
   return epa::dispatch_real(who, dtype, [&](auto tag) -> int {
     using T = typename decltype(tag)::type;
     for (int shift = (int)sizeof(T) * 8 - 8; shift >= 0; shift -= 8) {
-      EPA_CHECK_HIP(hipMemsetAsync(hist, 0, 512 * sizeof(unsigned long long), st));
+      EPA_CHECK_HIP(hipMemsetAsync(hist, 0, epa::scratch::seafloor_median_hist(0, 0, 0), st));
       sf_median_hist_kernel<T><<<nb, epa::kBlock, 0, st>>>((const T*)sv, P, S, r0, R, mask, shift, state, hist);
       if (int rc = epa::check_launch("sf_median_hist_kernel")) return rc;
       sf_median_pick_kernel<T><<<1, 64, 0, st>>>(hist, shift, state);

@@ -517,6 +517,14 @@ extern "C" int epa_shoal_weill_filter(const long long* parent, long long P, long
   return epa::check_launch("sh_final_kernel");
 }
 
+size_t epa::scratch::shoal_state(long long, long long, long long) {
+  return sizeof(unsigned long long) * EPA_SHOAL_STATE_WORDS;
+}
+// the queue of large link boxes: two int32 words per box (sh_link_kernel fills it while it has room)
+size_t epa::scratch::shoal_echoview_link_queue(long long, long long, long long) {
+  return 2 * sizeof(int) * EPA_SHOAL_QUEUE_BOXES;
+}
+
 extern "C" int epa_shoal_echoview_link(const long long* parent, long long P, long long S, int* box, int* group,
                                        int* flag, long long cap, const double* idim, long long ni, const double* jdim,
                                        long long nj, double mincan0, double mincan1, double maxlink0,

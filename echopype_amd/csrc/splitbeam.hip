@@ -461,7 +461,7 @@ __global__ __launch_bounds__(epa::kBlock) void sba_pc_direct_kernel(SbaArgs a) {
 // ------------------------------------------------------------------------------------------------
 __host__ __device__ inline size_t sws_tw64() { return 0; }
 __host__ __device__ inline size_t sws_tw32() { return 512; }
-__host__ __device__ inline size_t sws_spec64(int r) { return 768 + (size_t)r * 3 * kN; }
+__host__ __device__ constexpr size_t sws_spec64(int r) { return 768 + (size_t)r * 3 * kN; }
 __host__ __device__ inline size_t sws_spec32(int r) { return sws_spec64(r) + 2 * kN; }
 
 __global__ __launch_bounds__(epa::kBlock) void sba_replica_spectrum_kernel(const float* __restrict__ replica,
@@ -750,6 +750,12 @@ extern "C" int epa_splitbeam_complex(const void* re, const void* im, int in_dtyp
       return launch_direct<InT, T>(a, max_taps, st);
     });
   });
+}
+
+// twiddles, then the spectra of n replicas: where the spectrum of replica n would begin
+size_t epa::scratch::splitbeam_complex_fft_workspace(long long n, long long, long long) {
+  static_assert(sws_spec64(3) == EPA_SPLITBEAM_FFT_WS_DOUBLES(3), "header macro and workspace layout");
+  return sizeof(double) * sws_spec64((int)n);
 }
 
 extern "C" int epa_splitbeam_complex_fft(const void* re, const void* im, int in_dtype, const int32_t* beam_type_host,

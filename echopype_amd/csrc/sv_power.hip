@@ -334,20 +334,55 @@ __global__ __launch_bounds__(epa::kBlock) void sv_power_scalar_kernel(
   }
 }
 
+// ---- the host-side plan of K1, shared by the launch, the size of its workspace and epa_sv_power_vectorized ------------
+inline bool al16(const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+// the 16-byte path: S a whole number of 16-byte output accesses, every buffer given 16-byte aligned
+inline bool k1_vectorized(int S, size_t out_esz, const void* raw, const void* out, const void* range_out) {
+  const int need = out_esz == 8 ? 2 : 4;  // samples per 16-B output access
+  return (S % need == 0) && al16(raw) && al16(out) && al16(range_out);
+}
+constexpr int kVecChunk = 1024;       // samples of a row per workgroup on the 16-byte path (kBlock on the scalar one)
+constexpr int kRowGridTarget = 8192;  // workgroups aimed at: gx rows of chunks_per_row chunks
+struct K1Plan {
+  int chunk, chunks_per_row;
+  long long gx;
+  constexpr size_t partials() const { return (size_t)gx * chunks_per_row; }  // workgroups = {min, max, NaN count} partials
+};
+constexpr K1Plan k1_plan(int S, long long rows, bool vec) {
+  K1Plan pl{};
+  pl.chunk = vec ? kVecChunk : epa::kBlock;
+  pl.chunks_per_row = (S + pl.chunk - 1) / pl.chunk;
+  pl.gx = kRowGridTarget / pl.chunks_per_row;
+  if (pl.gx < 1) pl.gx = 1;
+  if (pl.gx > rows) pl.gx = rows;
+  return pl;
+}
+// What the statistics leave in the workspace, three 8-byte words per slot: the partials of the strided-rows kernel
+// (16-byte path only: gx * chunks_per_row <= max(kRowGridTarget, ceil(S / kVecChunk))), the kStatSlots keys of the
+// one-piece kernel, or epa_nanminmax's partials for the sweep behind the scalar kernel.
+constexpr size_t k1_stats_slots(long long S) { return (size_t)S / epa::kBlock + kRowGridTarget + epa::kMinmaxMaxGrid; }
+static_assert(kStatSlots <= kRowGridTarget + epa::kMinmaxMaxGrid, "the piece kernel's keys fit the workspace");
+static_assert(k1_stats_slots(1) == EPA_SV_POWER_STATS_WS_DOUBLES(1) / 3 &&
+                  k1_stats_slots(8388609) == EPA_SV_POWER_STATS_WS_DOUBLES(8388609) / 3,
+              "header macro and size function");
+constexpr bool k1_partials_fit(int S) { return k1_plan(S, 1ll << 40, true).partials() <= k1_stats_slots(S); }
+static_assert(k1_partials_fit(1) && k1_partials_fit(1024) && k1_partials_fit(1025) && k1_partials_fit(8388608) &&
+                  k1_partials_fit(8388612) && k1_partials_fit(1 << 30),
+              "the partials of the strided-rows kernel fit the workspace (launch() checks every call)");
+
 template <typename T>
 int launch(const float* raw, const double* coef, int C, int P, int S, int cal_type, unsigned flags,
            void* out, void* range_out, double* part, double* stats_out, hipStream_t st) {
   const long long rows = (long long)C * P;
   const T nspread = cal_type == EPA_CAL_SV ? (T)20 : (T)40;
-  auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
   const int need = sizeof(T) == 8 ? 2 : 4;  // samples per 16-B output access
-  const bool vec = (S % need == 0) && al16(raw) && al16(out) && al16(range_out);
-  const int chunk = vec ? 1024 : epa::kBlock;
-  const int chunks_per_row = (S + chunk - 1) / chunk;
-  long long gx = 8192 / chunks_per_row;
-  if (gx < 1) gx = 1;
-  if (gx > rows) gx = rows;
-  const dim3 grid((unsigned)gx, (unsigned)chunks_per_row);
+  const bool vec = k1_vectorized(S, sizeof(T), raw, out, range_out);
+  const K1Plan plan = k1_plan(S, rows, vec);
+  const int chunks_per_row = plan.chunks_per_row;
+  const dim3 grid((unsigned)plan.gx, (unsigned)chunks_per_row);
+  if (stats_out && vec)
+    EPA_CHECK_SCRATCH("epa_sv_power_stats", "workspace", 3 * sizeof(double) * plan.partials(),
+                      epa::scratch::sv_power_stats_workspace(S, 0, 0));
   const epa::CoefRow* cf = reinterpret_cast<const epa::CoefRow*>(coef);
 #define EPA_LAUNCH(K, R)                                                                        \
   hipLaunchKernelGGL((K<T, R>), grid, dim3(epa::kBlock), 0, st, raw, cf, rows, S, nspread, flags, \
@@ -468,6 +503,17 @@ __global__ __launch_bounds__(epa::kBlock) void range_power_kernel(const float* _
 }
 
 }  // namespace
+
+size_t epa::scratch::sv_power_stats_workspace(long long S, long long, long long) {
+  return 3 * sizeof(double) * k1_stats_slots(S);
+}
+
+extern "C" int epa_sv_power_vectorized(const void* raw, int S, int dtype, int* yes) {
+  EPA_CHECK_ARG(yes != nullptr, "epa_sv_power_vectorized: yes is NULL");
+  EPA_CHECK_REAL_OUT("epa_sv_power_vectorized", dtype);
+  *yes = k1_vectorized(S, dtype == EPA_F64 ? 8 : 4, raw, nullptr, nullptr) ? 1 : 0;
+  return EPA_OK;
+}
 
 extern "C" int epa_range_power(const float* raw, const double* coef, int C, int P, int S, unsigned flags,
                                void* range_out, int out_dtype, epa_stream_t stream) {

@@ -262,6 +262,12 @@ int check_cube(const char* who, const void* sv, const void* mask, int dtype, int
 
 }  // namespace
 
+// Fielding: the list of (channel, ping) rows left to the walk and its length; Matecho: s_hi and the flag of every row
+size_t epa::scratch::transient_fielding_todo(long long C, long long P, long long) { return sizeof(long long) * (size_t)C * P; }
+size_t epa::scratch::transient_fielding_count(long long, long long, long long) { return sizeof(unsigned); }
+size_t epa::scratch::transient_matecho_s_hi(long long C, long long P, long long) { return sizeof(int) * (size_t)C * P; }
+size_t epa::scratch::transient_matecho_flag(long long C, long long P, long long) { return sizeof(uint8_t) * (size_t)C * P; }
+
 extern "C" int epa_transient_fielding(const void* sv, int dtype, int C, int P, int S, const int* chan, int max_rows,
                                       int n, double thr0, double thr1, double maxts, long long* list,
                                       unsigned* count, uint8_t* mask, epa_stream_t stream) {
@@ -272,7 +278,7 @@ extern "C" int epa_transient_fielding(const void* sv, int dtype, int C, int P, i
                 "%s: a block of 2 * n = %lld pings x %d samples does not fit 31 bits", who, 2LL * n, max_rows);
   hipStream_t st = (hipStream_t)stream;
   const long long rows = (long long)C * P;
-  EPA_CHECK_HIP(hipMemsetAsync(count, 0, sizeof(unsigned), st));
+  EPA_CHECK_HIP(hipMemsetAsync(count, 0, epa::scratch::transient_fielding_count(0, 0, 0), st));
   return epa::dispatch_real(who, dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     tr_fielding_flag_kernel<T><<<grid_for(rows), kBlock, 0, st>>>((const T*)sv, P, S, rows, chan, n, thr0, maxts, mask,

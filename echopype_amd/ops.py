@@ -4,7 +4,9 @@ allocation, streams, RCCL), every computation is a call into libechopype_amd.so.
 All functions run on the tensors' device and torch's current stream and return torch tensors.
 """
 import ctypes
+import functools
 import threading
+import weakref
 
 import numpy as np
 import torch
@@ -37,6 +39,38 @@ def torch_dtype(dtype):
     if td not in _DT:
         raise ValueError(f"dtype must be float32 or float64, got {dtype!r}")
     return td
+
+
+# ---- scratch buffers: allocated here, sized by the library ----------------------------------------------------------------
+@functools.lru_cache(maxsize=4096)
+def _ask(name, *args, answer=ctypes.c_int):
+    """A host-side question to the library, asked once per distinct arguments: the size of a scratch buffer, a yes / no
+    about a call yet to be made."""
+    ans = answer()
+    _lib.check(getattr(_lib.lib, name)(*args, ctypes.byref(ans)), name)
+    return ans.value
+
+
+def scratch_bytes(what, a=0, b=0, c=0):
+    """Bytes of the scratch buffer ``what`` ("<entry>.<parameter>", the table at ``epa_scratch_bytes`` in the header)."""
+    return _ask("epa_scratch_bytes", what.encode(), int(a), int(b), int(c), answer=ctypes.c_size_t)
+
+
+def _scratch_alloc(nbytes, dtype, device, zero):
+    """A tensor of ``dtype`` that covers ``nbytes``: the one place scratch memory is allocated (tests wrap it)."""
+    return (torch.zeros if zero else torch.empty)(-(-nbytes // dtype.itemsize), dtype=dtype, device=device)
+
+
+def _scratch(what, device, a=0, b=0, c=0, dtype=torch.float64, zero=False):
+    return _scratch_alloc(scratch_bytes(what, a, b, c), dtype, device, zero)
+
+
+def _partials(want, C, n_tbins, n_rbins, dtype, dev, ask=True):
+    """(sum, count) arrays of a binned reduction when asked for or (``ask``) when the library may need them."""
+    if not (want or (ask and reduce_needs_workspace(C, n_tbins, n_rbins, dtype))):
+        return None, None
+    shape = (C, n_tbins, n_rbins)
+    return torch.empty(shape, dtype=dtype, device=dev), torch.empty(shape, dtype=torch.int32, device=dev)
 
 
 class _Uploader:
@@ -179,7 +213,6 @@ def fetch_async(t):
     return dl.fetch(t)
 
 
-
 def _uploader(dev):
     up = _uploaders.get(dev)
     if up is None:
@@ -254,8 +287,6 @@ def ping_time_facts(ping_time, want_device=True):
     that cannot be written to (``EchoData.to_device`` marks the beam groups' ping_time so -- resident data, like the
     samples) the three are kept with the ARRAY OBJECT: the O(P) look at the time stamps and their 8 P-byte upload are
     then paid once per file, not once per call.  A writeable array is looked at and uploaded every time."""
-    import weakref
-
     pt = np.asarray(ping_time)
     if pt.dtype != np.dtype("datetime64[ns]"):
         pt = pt.astype("datetime64[ns]")
@@ -289,8 +320,6 @@ def register_ping_time(ping_time, tensor, sorted_and_valid):
     device twin ``tensor`` and the verdict ``sorted_and_valid``, both computed on the device already (``qc``: the
     repaired coordinate is the download of ``tensor``).  The next ``ping_time_facts(ping_time)`` on that device then
     neither looks at the times nor uploads them.  The caller vouches for the three belonging together."""
-    import weakref
-
     pt = ping_time
     if not isinstance(pt, np.ndarray) or pt.dtype != np.dtype("datetime64[ns]") or pt.flags.writeable:
         raise ValueError("register_ping_time: a datetime64[ns] ndarray that cannot be written to is needed")
@@ -350,7 +379,8 @@ def pulse_table_lookup(tau_nominal, pulse_length, table):
 
 def sv_power_vectorized(raw, S, dtype):
     """True when K1 takes its 16-byte path on these buffers (needed for range statistics without the range array)."""
-    return S % (2 if dtype == torch.float64 else 4) == 0 and raw.data_ptr() % 16 == 0
+    # (asked once per (alignment, S, dtype): the rule looks at the address's low four bits only)
+    return _ask("epa_sv_power_vectorized", raw.data_ptr() % 16, int(S), _DT.get(dtype, _lib.F32)) != 0
 
 
 def sv_power(raw, coef, *, cal_type="Sv", flags=_lib.FLAG_GUARD_POS | _lib.FLAG_MASK_RANGE,
@@ -367,7 +397,7 @@ def sv_power(raw, coef, *, cal_type="Sv", flags=_lib.FLAG_GUARD_POS | _lib.FLAG_
         range_out = torch.empty((C, P, S), dtype=dtype, device=raw.device)
     ct = _lib.CAL_SV if cal_type == "Sv" else _lib.CAL_TS
     if want_range_stats:
-        ws = torch.empty(3 * (S // 256 + 8192 + 1024), dtype=torch.float64, device=raw.device)
+        ws = _scratch("sv_power_stats.workspace", raw.device, S)
         stats = torch.empty(3, dtype=torch.float64, device=raw.device)
         call("epa_sv_power_stats", _p(raw), _p(coef), C, P, S, ct, flags, _p(out),
              _p(range_out) if want_range else None, _DT[out.dtype], _p(ws), _p(stats), _stream())
@@ -399,11 +429,8 @@ def _bin_flags(skipna, closed):
 
 
 def reduce_needs_workspace(C, n_tbins, n_rbins, dtype):
-    """Mirror of block_reduce.hip::make_plan: the two-stage path (few ping bins, or a range grid
-    too large for LDS) needs caller-provided sum/count workspaces."""
-    esz = 8 if dtype == torch.float64 else 4
-    lds = ((n_rbins * esz + 15) & ~15) + 4 * n_rbins
-    return C * n_tbins < 1024 or lds > 128 * 1024
+    """Few ping bins, or a range grid too large for LDS, MAY need caller-provided sum / count arrays."""
+    return _ask("epa_mvbs_needs_partials", int(C), int(n_tbins), int(n_rbins), _DT.get(dtype, _lib.F32)) != 0
 
 
 def sv_mvbs_fused(raw, coef, bin_start, n_tbins, range_bin, n_rbins, *, cal_type="Sv",
@@ -422,10 +449,7 @@ def sv_mvbs_fused(raw, coef, bin_start, n_tbins, range_bin, n_rbins, *, cal_type
         range_out = torch.empty((C, P, S), dtype=dtype, device=dev)
     if mvbs_out is None:
         mvbs_out = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-    ssum = cnt = None
-    if want_partials or reduce_needs_workspace(C, n_tbins, n_rbins, dtype):
-        ssum = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-        cnt = torch.empty((C, n_tbins, n_rbins), dtype=torch.int32, device=dev)
+    ssum, cnt = _partials(want_partials, C, n_tbins, n_rbins, dtype, dev)
     rmax = torch.empty(1, dtype=torch.float64, device=dev) if want_range_max or want_range_stats else None
     rstats = torch.empty(3, dtype=torch.float64, device=dev) if want_range_stats else None
     call("epa_sv_mvbs_fused", _p(raw), _p(coef), C, P, S,
@@ -451,11 +475,8 @@ def sv_mvbs_fused_depth(raw, coef, depth_scale, depth_offset, bin_start, n_tbins
     depth_out = torch.empty((C, P, S), dtype=dtype, device=dev) if want_depth else None
     if mvbs_out is None:
         mvbs_out = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-    ssum = cnt = None
-    if want_partials:
-        ssum = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-        cnt = torch.empty((C, n_tbins, n_rbins), dtype=torch.int32, device=dev)
-    rstats = torch.empty(64, dtype=torch.float64, device=dev)
+    ssum, cnt = _partials(want_partials, C, n_tbins, n_rbins, dtype, dev, ask=False)
+    rstats = _scratch("sv_mvbs_fused_depth.depth_stats_out", dev)
     call("epa_sv_mvbs_fused_depth", _p(raw), _p(coef), _p(depth_scale), _p(depth_offset), C, P, S,
          _lib.CAL_SV if cal_type == "Sv" else _lib.CAL_TS, _p(bin_start), int(n_tbins), float(range_bin), int(n_rbins),
          float(fill_value), _p(sv_out) if want_sv else None, _p(depth_out), _p(mvbs_out), _p(ssum), _p(cnt), _p(rstats),
@@ -476,10 +497,7 @@ def sv_mvbs_fused_i16(raw_i16, n_valid, coef, bin_start, n_tbins, range_bin, n_r
         sv_out = torch.empty((C, P, S), dtype=dtype, device=dev)
     if mvbs_out is None:
         mvbs_out = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-    ssum = cnt = None
-    if want_partials:
-        ssum = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-        cnt = torch.empty((C, n_tbins, n_rbins), dtype=torch.int32, device=dev)
+    ssum, cnt = _partials(want_partials, C, n_tbins, n_rbins, dtype, dev, ask=False)
     rmax = torch.empty(1, dtype=torch.float64, device=dev) if want_range_max else None
     call("epa_sv_mvbs_fused_i16", _p(raw_i16), _p(n_valid), _p(coef), C, P, S,
          _lib.CAL_SV if cal_type == "Sv" else _lib.CAL_TS, _p(bin_start), int(n_tbins), float(range_bin),
@@ -498,10 +516,7 @@ def mvbs(sv, bin_start, n_tbins, range_bin, n_rbins, *, range=None, coef=None, s
     if range is not None and range.dtype != dtype:
         range = range.to(dtype)
     out = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-    ssum = cnt = None
-    if want_partials or reduce_needs_workspace(C, n_tbins, n_rbins, dtype):
-        ssum = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-        cnt = torch.empty((C, n_tbins, n_rbins), dtype=torch.int32, device=dev)
+    ssum, cnt = _partials(want_partials, C, n_tbins, n_rbins, dtype, dev)
     call("epa_mvbs", _p(sv), _p(range), _p(coef), C, P, S, _p(bin_start), _p(ping_perm), int(n_tbins),
          float(range_bin), int(n_rbins), _bin_flags(skipna, closed) | (_lib.BIN_RANGE_AS_STORED if coef_as_stored else 0),
          float(fill_value), _p(out), _p(ssum), _p(cnt), _DT[dtype], _stream())
@@ -534,8 +549,7 @@ def selftest_correlate(x, replica, fft_dtype=None):
         raise ValueError("fft_dtype is the precision of x")
     xr, rr = torch.view_as_real(x.contiguous()), torch.view_as_real(replica.contiguous())
     off = torch.tensor([0, replica.numel()], dtype=torch.int32, device=x.device)
-    ws = torch.empty(768 + 4 + 3 * _lib.EK80_NFFT + 3 * 1024 + 2 + 1 + 5 + 256, dtype=torch.float64,
-                     device=x.device)  # EPA_EK80_FFT_WS_DOUBLES(1, 1, 1)
+    ws = _scratch("selftest_correlate.workspace", x.device, 1, 1, 1)
     out = torch.empty_like(xr)
     call("epa_selftest_correlate", _p(xr), x.shape[0], _p(rr), _p(off), _DT[fdt], _p(out), _p(ws), _stream())
     return torch.view_as_complex(out)
@@ -568,10 +582,8 @@ def depth_rows(scale, offset, *, range=None, coef=None, mask_raw=None, shape=Non
         C, P, S = shape
         dev = coef.device
     out = torch.empty((C, P, S), dtype=dtype, device=dev)
-    ws = stats = None
-    if want_stats:
-        ws = torch.empty(3 * 16384, dtype=torch.float64, device=dev)  # EPA_DEPTH_ROWS_WS_DOUBLES
-        stats = torch.empty(3, dtype=torch.float64, device=dev)
+    ws = _scratch("depth_rows.workspace", dev) if want_stats else None
+    stats = torch.empty(3, dtype=torch.float64, device=dev) if want_stats else None
     call("epa_depth_rows", _p(range), _p(coef), _p(mask_raw), _p(scale), _p(offset), C, P, S, _p(out), _DT[dtype],
          _p(ws), _p(stats), _stream())
     return out, stats
@@ -579,7 +591,7 @@ def depth_rows(scale, offset, *, range=None, coef=None, mask_raw=None, shape=Non
 
 def nanminmax(x, with_nan_count=False):
     """(nanmin, nanmax[, number of NaNs]) of a device tensor as Python floats (one 24-byte D2H copy)."""
-    ws = torch.empty(3072, dtype=torch.float64, device=x.device)
+    ws = _scratch("nanminmax.workspace", x.device)
     out = torch.empty(3, dtype=torch.float64, device=x.device)
     call("epa_nanminmax", _p(x), x.numel(), _DT[x.dtype], _p(ws), _p(out), _stream())
     lo, hi, nn = out.cpu().tolist()
@@ -717,10 +729,7 @@ def sv_complex(re, im, ccoef, *, replica=None, replica_off=None, max_taps=0, cal
     use_fft = sv_complex_uses_fft(replica, max_taps, method)
     stats = None
     if use_fft:
-        W = max(C, n_rep)
-        n_ws = (768 + 4 * W + 3 * W * _lib.EK80_NFFT + 3 * 1024 + 2
-                + (W * P * (S // (_lib.EK80_NFFT // 2 + 1) + 1) + 63) // 64 + W * (S + 4) + 256)  # EPA_EK80_FFT_WS_DOUBLES(W, P, S)
-        ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
+        ws = _scratch("sv_complex_fft.workspace", dev, max(C, n_rep), P, S)
         fdt = torch_dtype(fft_dtype) if fft_dtype is not None else dtype
         if want_range_stats:
             stats = torch.empty(3, dtype=torch.float64, device=dev)
@@ -733,7 +742,7 @@ def sv_complex(re, im, ccoef, *, replica=None, replica_off=None, max_taps=0, cal
                  _p(replica_id), n_rep, int(max_taps), _p(ccoef), C, P, S, B, cal, _p(out), _p(rng), _p(prx),
                  _DT[dtype], _DT[fdt], _p(ws), _p(stats), _stream())
     elif replica is None and want_range_stats:  # CW: the streaming kernel leaves the statistics as well
-        ws = torch.empty(3072, dtype=torch.float64, device=dev)  # EPA_SV_COMPLEX_CW_STATS_WS_DOUBLES
+        ws = _scratch("sv_complex_cw_stats.workspace", dev)
         stats = torch.empty(3, dtype=torch.float64, device=dev)
         call("epa_sv_complex_cw_stats", _p(re), _p(im), _DT[re.dtype], _p(ccoef), C, P, S, B, cal, _p(out), _p(rng),
              _p(prx), _DT[dtype], _p(ws), _p(stats), _stream())
@@ -744,7 +753,6 @@ def sv_complex(re, im, ccoef, *, replica=None, replica_off=None, max_taps=0, cal
         call("epa_sv_complex", _p(re), _p(im), _DT[re.dtype], _p(replica), _p(replica_off), int(max_taps),
              _p(ccoef), C, P, S, B, cal, _p(out), _p(rng), _p(prx), _DT[dtype], _stream())
     return dict(out=out, echo_range=rng, prx=prx, range_stats=stats)
-
 
 
 # ---- split-beam angles (consolidate.add_splitbeam_angle) ---------------------------------------------------------------
@@ -814,7 +822,7 @@ def splitbeam_complex(re, im, beam_type, params, *, replica=None, replica_off=No
     phi = torch.empty_like(theta)
     bt_p = bt.ctypes.data_as(ctypes.c_void_p)
     if splitbeam_uses_fft(replica, max_taps, method):
-        ws = torch.empty(768 + 3 * n_rep * _lib.EK80_NFFT, dtype=torch.float64, device=dev)  # EPA_SPLITBEAM_FFT_WS_DOUBLES
+        ws = _scratch("splitbeam_complex_fft.workspace", dev, n_rep)
         fdt = torch_dtype(fft_dtype) if fft_dtype is not None else torch.float64
         call("epa_splitbeam_complex_fft", _p(re), _p(im), _DT[re.dtype], bt_p, ptrs, modes, _p(replica),
              _p(replica_off), _p(replica_id), n_rep, int(max_taps), C, P, S, B, _p(theta), _p(phi), _DT[dtype],
@@ -834,7 +842,7 @@ def _plane_dtype(t, what):
 
 def seafloor_state(device):
     """The zeroed u64 state words of one Blackwell call (int64 tensor of EPA_SEAFLOOR_STATE_WORDS)."""
-    return torch.zeros(_lib.SEAFLOOR_STATE_WORDS, dtype=torch.int64, device=device)
+    return _scratch("seafloor.state", device, dtype=torch.int64, zero=True)
 
 
 def seafloor_depth_uniform(depth):
@@ -859,7 +867,7 @@ def seafloor_angle_mask(theta, phi, r0, R, wtheta, wphi, ttheta, tphi, state):
     P, S = theta.shape
     if phi.shape != theta.shape or phi.dtype != theta.dtype:
         raise ValueError("angle_alongship / angle_athwartship: same shape and dtype")
-    work = torch.empty(2 * P * R, dtype=torch.float64, device=theta.device)
+    work = _scratch("seafloor_angle_mask.work", theta.device, P, R)
     mask = torch.empty((P, R), dtype=torch.uint8, device=theta.device)
     call("epa_seafloor_angle_mask", _p(theta), _p(phi), _plane_dtype(theta, "angles"), P, S, int(r0), int(R),
          int(wtheta), int(wphi), float(ttheta), float(tphi), _p(work), _p(mask), _p(state), _stream())
@@ -869,7 +877,7 @@ def seafloor_angle_mask(theta, phi, r0, R, wtheta, wphi, ttheta, tphi, state):
 def seafloor_median(sv, r0, R, mask, state):
     """Radix-select the one or two middle values of the non-NaN ``sv`` crop under ``mask`` into ``state``."""
     P, S = sv.shape
-    hist = torch.empty(512, dtype=torch.int64, device=sv.device)
+    hist = _scratch("seafloor_median.hist", sv.device, dtype=torch.int64)
     call("epa_seafloor_median", _p(sv), _plane_dtype(sv, "Sv"), P, S, int(r0), int(R), _p(mask), _p(state), _p(hist),
          _stream())
 
@@ -902,7 +910,7 @@ def shoal_table_capacity(P, S, connectivity):
 
 def shoal_state(device):
     """The zeroed u64 state words of one shoal call (int64 tensor of EPA_SHOAL_STATE_WORDS): [0] the error word."""
-    return torch.zeros(_lib.SHOAL_STATE_WORDS, dtype=torch.int64, device=device)
+    return _scratch("shoal.state", device, dtype=torch.int64, zero=True)
 
 
 def _gap(v, n):
@@ -951,7 +959,7 @@ def shoal_echoview_link(plane, parent, table, idim, jdim, mincan, maxlink, minsh
     """In place: Echoview's candidate filter, linking and shoal filter on a labelled plane; ``idim`` / ``jdim`` f64
     device vectors."""
     P, S = plane.shape
-    queue = torch.empty(2 * _lib.SHOAL_QUEUE_BOXES, dtype=torch.int32, device=plane.device)
+    queue = _scratch("shoal_echoview_link.queue", plane.device, dtype=torch.int32)
     call("epa_shoal_echoview_link", _p(parent), P, S, _p(table["box"]), _p(table["group"]), _p(table["flag"]),
          table["cap"], _p(idim), int(idim.numel()), _p(jdim), int(jdim.numel()), float(mincan[0]), float(mincan[1]),
          float(maxlink[0]), float(maxlink[1]), float(minsho[0]), float(minsho[1]), _p(queue), _p(state), _p(plane),
@@ -972,8 +980,8 @@ def transient_fielding(sv, chan, n, thr0, thr1, maxts):
     max_rows = int(max(np.max(np.maximum(lw - up, 0)), np.max(np.where(chan[:, 3] < up, chan[:, 3], 0))))
     dev = sv.device
     mask = torch.empty((C, P, S), dtype=torch.bool, device=dev)
-    todo = torch.empty(C * P, dtype=torch.int64, device=dev)
-    count = torch.empty(1, dtype=torch.int32, device=dev)
+    todo = _scratch("transient_fielding.todo", dev, C, P, dtype=torch.int64)
+    count = _scratch("transient_fielding.count", dev, dtype=torch.int32)
     call("epa_transient_fielding", _p(sv), _DT[sv.dtype], C, P, S, _p(to_device_small(chan.astype(np.int32), device=dev)),
          max_rows, int(n), float(thr0), float(thr1), float(maxts), _p(todo), _p(count), _p(mask), _stream())
     return mask
@@ -993,8 +1001,8 @@ def transient_matecho(sv, range_rows, chan_i, chan_d, bottom, half_window, perce
             raise ValueError(f"transient_matecho: bottom must be float64 of shape ({P},) or ({C}, {P}), got "
                              f"{bottom.dtype} {tuple(bottom.shape)}")
     mask = torch.empty((C, P, S), dtype=torch.bool, device=dev)
-    s_hi = torch.empty(C * P, dtype=torch.int32, device=dev)
-    flag = torch.empty(C * P, dtype=torch.uint8, device=dev)
+    s_hi = _scratch("transient_matecho.s_hi", dev, C, P, dtype=torch.int32)
+    flag = _scratch("transient_matecho.flag", dev, C, P, dtype=torch.uint8)
     call("epa_transient_matecho", _p(sv), _DT[sv.dtype], C, P, S,
          _p(to_device(np.ascontiguousarray(range_rows, dtype=np.float64).reshape(C, S), device=dev)),
          _p(to_device_small(chan_i, device=dev)),
@@ -1021,8 +1029,8 @@ def freq_diff_mask(sv, chan_a, chan_b, operator, diff):
 
 
 def regrid_needs_global_flags(n_rbins):
-    """Mirror of mask_grid.hip: the flags of one time bin (4 bytes per range bin) do not fit in LDS."""
-    return 4 * n_rbins > 128 * 1024
+    """The flags of one time bin (4 bytes per range bin) do not fit in LDS (``epa_regrid_needs_global_flags``)."""
+    return _ask("epa_regrid_needs_global_flags", int(n_rbins)) != 0
 
 
 def regrid_mask(mask, range, bin_start, n_tbins, range_bin, n_rbins, *, group=None, n_groups=None, func="logical-AND",
@@ -1040,7 +1048,7 @@ def regrid_mask(mask, range, bin_start, n_tbins, range_bin, n_rbins, *, group=No
                          f"{tuple(range.shape)}")
     G = T if group is None else int(n_groups)
     cells = G * n_tbins * n_rbins
-    buf = torch.empty((cells + 3) // 4 * 4, dtype=torch.uint8, device=mask.device)  # whole 32-bit words (the header)
+    buf = _scratch("regrid_mask.out", mask.device, G, n_tbins, n_rbins, dtype=torch.uint8)  # (whole 32-bit words)
     nonbinary = torch.empty(1, dtype=torch.int32, device=mask.device)
     call("epa_regrid_mask", _p(mask), _p(group), T, P, D, _p(range), int(range.dim() == 2), _p(bin_start), int(n_tbins),
          float(range_bin), int(n_rbins), _lib.BIN_CLOSED_RIGHT if closed == "right" else 0,
@@ -1145,7 +1153,7 @@ def time_rebuild(t, facts, sub):
     if sub.numel() < N - 1 or facts.numel() != _lib.QC_FACTS:
         raise ValueError("time_rebuild: facts and sub must belong to the times")
     out = torch.empty_like(t)
-    work = torch.empty((N - 1 + _lib.QC_SCAN_TILE - 1) // _lib.QC_SCAN_TILE, dtype=torch.int64, device=t.device)
+    work = _scratch("time_rebuild.tile_workspace", t.device, N, dtype=torch.int64)
     call("epa_time_rebuild", _p(t), N, _p(facts), _p(sub), _p(work), _p(out), _stream())
     return out
 
@@ -1355,10 +1363,9 @@ def pool_sv(sv, first_sample, num_side_pings, num_side_samples, func="nanmean", 
     pooled = torch.empty_like(sv) if want_pooled else None
     mask = (mask_out if mask_out is not None else
             torch.empty((C, P, S), dtype=torch.uint8, device=sv.device)) if want_mask else None
-    ws = wc = None
-    if f == _lib.POOL_NANMEAN:
-        ws = torch.empty((C, P, S), dtype=torch.float64, device=sv.device)
-        wc = torch.empty((C, P, S), dtype=torch.int32, device=sv.device)
+    mean = f == _lib.POOL_NANMEAN
+    ws = _scratch("pool_sv.sum_ws", sv.device, C, P, S) if mean else None
+    wc = _scratch("pool_sv.cnt_ws", sv.device, C, P, S, dtype=torch.int32) if mean else None
     call("epa_pool_sv", _p(sv), C, P, S, int(first_sample), int(num_side_pings), int(num_side_samples),
          f, float(threshold), _p(pooled), _p(mask), _p(ws), _p(wc), _DT[sv.dtype], _stream())
     return pooled, mask
@@ -1389,8 +1396,6 @@ def apply_mask(src, mask, fill_value=float("nan"), fill_array=None):
 def apply_masks(src, masks, fill_value=float("nan"), fill_array=None, want_minmax=False):
     """where(AND of ``masks``, src, fill) in one sweep (1 to 4 uint8 masks, each tiling ``src`` over its leading dims)
     -> (out, f64 device tensor {nanmin, nanmax} of out | None)."""
-    import ctypes
-
     if not 1 <= len(masks) <= 4:
         raise ValueError("apply_masks takes 1 to 4 masks (AND further ones with mask_and first)")
     out = torch.empty_like(src)
@@ -1398,10 +1403,8 @@ def apply_masks(src, masks, fill_value=float("nan"), fill_array=None, want_minma
         fill_array = fill_array.to(src.dtype)
     ptrs = (ctypes.c_void_p * len(masks))(*[m.data_ptr() for m in masks])
     periods = (ctypes.c_size_t * len(masks))(*[m.numel() for m in masks])
-    ws = mm = None
-    if want_minmax:
-        ws = torch.empty(_lib.APPLY_MASKS_WS_DOUBLES, dtype=torch.float64, device=src.device)
-        mm = torch.empty(2, dtype=torch.float64, device=src.device)
+    ws = _scratch("apply_masks.workspace", src.device) if want_minmax else None
+    mm = torch.empty(2, dtype=torch.float64, device=src.device) if want_minmax else None
     call("epa_apply_masks", _p(src), ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(periods, ctypes.c_void_p), len(masks),
          src.numel(), float(fill_value), _p(fill_array), fill_array.numel() if fill_array is not None else 1, _p(out),
          _p(ws), _p(mm), _DT[src.dtype], _stream())
@@ -1418,7 +1421,7 @@ def mask_and(a, b):
 def range_step_mean(range):
     """Per-channel nanmean of the sample-to-sample range step -> numpy f64 [C]."""
     C, P, S = range.shape
-    ws = torch.empty(2 * C * P, dtype=torch.float64, device=range.device)
+    ws = _scratch("range_step_mean.workspace", range.device, C, P)
     out = torch.empty(C, dtype=torch.float64, device=range.device)
     call("epa_range_step_mean", _p(range), C, P, S, _DT[range.dtype], _p(ws), _p(out), _stream())
     return out.cpu().numpy()
@@ -1443,8 +1446,8 @@ def range_rows_check(range):
 def pool_sv_value(sv, range, nvalid, depth_bin, num_side_pings, exclude_above, range_min, range_max,
                   func="nanmean", threshold=0.0, want_pooled=True, want_mask=True, running_sums=True):
     """Value-window pooled Sv (pool_Sv) and/or the mask Sv - pooled > threshold.  ``running_sums`` (nanmean):
-    per-row double-double running sums and interval sums in a 40 B/sample workspace instead of summing every window
-    (EPA_POOL_VALUE_WS_BYTES in the header); when that does not fit next to the arrays the workspace-free kernel runs
+    per-row double-double running sums and interval sums in a 40 B/sample workspace instead of summing every window;
+    when that does not fit next to the arrays the workspace-free kernel runs
     (same results, every window summed value by value).  nanmedian: with ``running_sums`` the window is carried from
     ping to ping (a small workspace), without it every window is taken from memory."""
     C, P, S = sv.shape
@@ -1456,11 +1459,11 @@ def pool_sv_value(sv, range, nvalid, depth_bin, num_side_pings, exclude_above, r
     ws = None
     if running_sums and func == "nanmean":
         try:
-            ws = torch.empty((C * P * S * 40 + C * S * 8 + C * 8 + C * P + 7) // 8, dtype=torch.float64, device=sv.device)
+            ws = _scratch("pool_sv_value.ws_mean", sv.device, C, P, S)
         except torch.cuda.OutOfMemoryError:
             ws = None
-    elif running_sums:  # nanmedian: the per-channel sample intervals (EPA_POOL_VALUE_MEDIAN_WS_BYTES)
-        ws = torch.empty(2 * C * S + 2 * C, dtype=torch.int32, device=sv.device)
+    elif running_sums:  # nanmedian: the per-channel sample intervals
+        ws = _scratch("pool_sv_value.ws_median", sv.device, C, S, dtype=torch.int32)
     call("epa_pool_sv_value", _p(sv), _p(range), _p(nvalid), C, P, S, float(depth_bin), int(num_side_pings),
          float(exclude_above), float(range_min), float(range_max), f, float(threshold), _p(pooled),
          _p(mask), _p(ws), _DT[sv.dtype], _stream())
@@ -1483,7 +1486,7 @@ def nasc(sv, depth, bin_start, n_dbins, range_bin, n_rbins, skipna=True, closed=
     C, P, S = sv.shape
     if depth.dtype != sv.dtype:
         depth = depth.to(sv.dtype)
-    ws = torch.empty(C * n_dbins * n_rbins * 3, dtype=torch.float64, device=sv.device)  # 24 B / cell
+    ws = _scratch("nasc.workspace", sv.device, C, n_dbins, n_rbins)
     out = torch.empty((C, n_dbins, n_rbins), dtype=sv.dtype, device=sv.device)
     svm = torch.empty_like(out) if want_parts else None
     hm = torch.empty_like(out) if want_parts else None
@@ -1537,10 +1540,7 @@ def denoise_mvbs(sv, alpha2, noise, ping_num, snr_threshold, bin_start, n_tbins,
     sn = torch.empty_like(sv) if want_noise else None
     sc = torch.empty_like(sv) if want_corrected else None
     out = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-    ssum = cnt = None
-    if want_partials or reduce_needs_workspace(C, n_tbins, n_rbins, dtype):
-        ssum = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-        cnt = torch.empty((C, n_tbins, n_rbins), dtype=torch.int32, device=dev)
+    ssum, cnt = _partials(want_partials, C, n_tbins, n_rbins, dtype, dev)
     call("epa_denoise_mvbs", _p(sv), _p(range), _p(coef), _p(alpha2), _p(noise), C, P, S, int(ping_num),
          float(snr_threshold), _p(bin_start), _p(ping_perm), int(n_tbins), float(range_bin), int(n_rbins),
          _bin_flags(skipna, closed), float(fill_value), _p(sn), _p(sc), _p(out), _p(ssum), _p(cnt),
@@ -1561,10 +1561,7 @@ def sv_denoise_mvbs(raw, coef, alpha2, noise, ping_num, snr_threshold, bin_start
     mk = lambda want: torch.empty((C, P, S), dtype=dtype, device=dev) if want else None  # noqa: E731
     sn, sc, rng = mk(want_noise), mk(want_corrected), mk(want_range)
     out = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-    ssum = cnt = None
-    if want_partials or reduce_needs_workspace(C, n_tbins, n_rbins, dtype):
-        ssum = torch.empty((C, n_tbins, n_rbins), dtype=dtype, device=dev)
-        cnt = torch.empty((C, n_tbins, n_rbins), dtype=torch.int32, device=dev)
+    ssum, cnt = _partials(want_partials, C, n_tbins, n_rbins, dtype, dev)
     mm = torch.empty(4, dtype=torch.float64, device=dev) if want_minmax else None
     call("epa_sv_denoise_mvbs", _p(raw), _p(coef), _p(alpha2), _p(noise), C, P, S,
          _lib.CAL_SV if cal_type == "Sv" else _lib.CAL_TS, flags, int(ping_num), int(ping_phase), float(snr_threshold),

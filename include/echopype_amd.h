@@ -107,6 +107,53 @@ int epa_timer_start(void* timer, epa_stream_t stream);
 int epa_timer_stop(void* timer, epa_stream_t stream);
 int epa_timer_elapsed_ms(void* timer, float* ms); /* synchronises on the stop event */
 
+/* ---- scratch buffers: allocated by the caller, sized by the library ------------------------------------------------
+ * Bytes of the scratch buffer `what` ("<entry>.<parameter>", table below) for the sizes a, b, c the table names (unused
+ * ones 0).  Pure host arithmetic: no HIP call, usable without a GPU.  Unknown name: EPA_EINVAL.
+ *
+ * THESE FUNCTIONS ARE THE AUTHORITY on the size of every scratch parameter: each is defined beside the code that lays
+ * its buffer out, and an entry whose write extent follows from a launch plan checks it against the same function
+ * before launching.  The EPA_*_WS_* macros and the "f64 [n]" remarks further down give the same values and stay for C
+ * callers that size at compile time.
+ *
+ *   what                                   a, b, c                       the buffer
+ *   sv_power_stats.workspace               S                             f64 [EPA_SV_POWER_STATS_WS_DOUBLES(S)]
+ *   depth_rows.workspace                   -                             f64 [EPA_DEPTH_ROWS_WS_DOUBLES]
+ *   nanminmax.workspace                    -                             f64 [3072]
+ *   sv_complex_cw_stats.workspace          -                             f64 [EPA_SV_COMPLEX_CW_STATS_WS_DOUBLES]
+ *   sv_complex_fft.workspace               W = max(C, n_replicas), P, S  f64 [EPA_EK80_FFT_WS_DOUBLES(W, P, S)]
+ *   sv_complex_fft_indexed.workspace       the same
+ *   selftest_correlate.workspace           1, 1, 1                       the same
+ *   splitbeam_complex_fft.workspace        n                             f64 [EPA_SPLITBEAM_FFT_WS_DOUBLES(n)]
+ *   sv_mvbs_fused_depth.depth_stats_out    -                             f64 [64]
+ *   apply_masks.workspace                  -                             f64 [EPA_APPLY_MASKS_WS_DOUBLES]
+ *   range_step_mean.workspace              C, P                          f64 [2*C*P]
+ *   pool_sv.sum_ws / pool_sv.cnt_ws        C, P, S                       f64 [C*P*S] / i32 [C*P*S] (nanmean)
+ *   pool_sv_value.ws_mean                  C, P, S                       EPA_POOL_VALUE_WS_BYTES, rounded up to 8
+ *   pool_sv_value.ws_median                C, S                          EPA_POOL_VALUE_MEDIAN_WS_BYTES
+ *   nasc.workspace                         C, n_dbins, n_rbins           24 bytes per cell
+ *   seafloor.state                         -                             u64 [EPA_SEAFLOOR_STATE_WORDS]
+ *   seafloor_angle_mask.work               P, R                          f64 [2*P*R]
+ *   seafloor_median.hist                   -                             u64 [512]
+ *   shoal.state                            -                             u64 [EPA_SHOAL_STATE_WORDS]
+ *   shoal_echoview_link.queue              -                             i32 [2 * EPA_SHOAL_QUEUE_BOXES]
+ *   transient_fielding.todo / .count       C, P / -                      i64 [C*P] (`list`) / u32 [1]
+ *   transient_matecho.s_hi / .flag         C, P                          i32 [C*P] / u8 [C*P]
+ *   time_rebuild.tile_workspace            N                             i64 [ceil((N-1) / EPA_QC_SCAN_TILE)]
+ *   regrid_mask.out                        G, n_tbins, n_rbins           the G*n_tbins*n_rbins cells, rounded up to 4 bytes
+ */
+int epa_scratch_bytes(const char* what, long long a, long long b, long long c, size_t* bytes_out);
+/* Three decisions a caller has to know BEFORE a call, to allocate for it; each is answered by the rule the entry itself
+ * uses.  Pure host arithmetic, as above.
+ *   epa_mvbs_needs_partials: MAY epa_mvbs / epa_sv_mvbs_fused / epa_denoise_mvbs / epa_sv_denoise_mvbs need sum_out and
+ *     cnt_out for this grid (few ping bins, or accumulators too large for LDS)?  A superset of the cases that do.
+ *   epa_regrid_needs_global_flags: does epa_regrid_mask keep the flags of a time bin in `out` instead of LDS?
+ *   epa_sv_power_vectorized: does epa_sv_power(_stats) take its 16-byte path on this input (needed for range statistics
+ *     without the range array)? */
+int epa_mvbs_needs_partials(int C, int n_tbins, int n_rbins, int dtype, int* yes);
+int epa_regrid_needs_global_flags(int n_rbins, int* yes);
+int epa_sv_power_vectorized(const void* raw, int S, int dtype, int* yes);
+
 /* ---- K0: coefficient table for EK60 / EK80 power samples ------------------------------------------
  * Replaces the per-(channel, ping) arithmetic of
  *   calibrate/range.py:138 (k = sample_interval*sound_speed/2), :176-199 (TVG shift),
