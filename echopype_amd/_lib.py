@@ -32,6 +32,7 @@ BIN_SKIPNA, BIN_CLOSED_RIGHT, BIN_RANGE_AS_STORED = 1, 2, 4
 POOL_NANMEAN, POOL_NANMEDIAN = 0, 1
 CMP_GT, CMP_LT, CMP_LE, CMP_GE, CMP_EQ = range(5)  # enum epa_cmp
 ALIGN_LINEAR, ALIGN_NEAREST = 0, 1  # epa_align_to_ping_time mode
+LINE_CLOSED_RIGHT, LINE_NAN_IGNORE = 1, 2  # EPA_LINE_*: the flags of epa_line_mask
 QC_FACTS = 4  # EPA_QC_FACTS
 QC_FIRST, QC_COUNT, QC_NAT, QC_SLOTS = range(4)  # the words of the facts
 QC_MAX_WIN = 1024  # EPA_QC_MAX_WIN
@@ -173,6 +174,8 @@ SIGNATURES = {
     "epa_transient_matecho": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _d, _vp, _vp, _vp, _vp],
     "epa_freq_diff_mask": [_vp, _i, _sz, _i, _i, _i, _d, _vp, _i, _vp],
     "epa_regrid_mask": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _u, _i, _vp, _vp, _vp],
+    "epa_line_mask": [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _i, _vp, _ll, _ll, _d, _vp, _ll, _ll, _d, _u, _i, _i, _i, _vp,
+                      _vp],
     "epa_echo_metrics": [_vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "epa_align_to_ping_time": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp],
     "epa_time_reversals": [_vp, _ll, _vp, _vp, _vp],

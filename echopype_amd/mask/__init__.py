@@ -1,5 +1,5 @@
 from .api import (METHODS_BOTTOM, METHODS_SHOAL, apply_mask, detect_seafloor, detect_shoal,  # noqa: F401
-                  frequency_differencing, regrid_mask)
+                  frequency_differencing, line_mask, regrid_mask)
 
-__all__ = ["apply_mask", "detect_seafloor", "detect_shoal", "frequency_differencing", "regrid_mask", "METHODS_BOTTOM",
-           "METHODS_SHOAL"]
+__all__ = ["apply_mask", "detect_seafloor", "detect_shoal", "frequency_differencing", "line_mask", "regrid_mask",
+           "METHODS_BOTTOM", "METHODS_SHOAL"]

@@ -452,3 +452,192 @@ def regrid_mask(mask_da, range_da, range_bin="20m", ping_time_bin="20s", third_d
             "range_meter_interval": str(range_bin) + "m",
             "ping_time_interval": ping_time_bin,
         })
+
+
+# ---- the samples between two lines (no counterpart in the reference: there it is ``ds["depth"] < bottom``) -------------
+from numbers import Real  # noqa: E402
+
+from ..device_view import resolve_device  # noqa: E402
+from ..xr_lite import LazyDeviceArray  # noqa: E402
+
+_LINE_DIMS = ("channel", "ping_time")
+
+
+def _check_bound(ds, bound, what, sizes):
+    """A bound of ``line_mask`` checked on the host: None, a float, or the DataArray that holds the line."""
+    if bound is None:
+        return None
+    if isinstance(bound, str):
+        if bound in ds:  # the name of a variable first (the precedent: detect_transient(matecho)'s bottom_var)
+            bound = ds[bound]
+        else:
+            bound = _parse_x_bin(bound)
+    bound = from_xarray(bound)
+    if isinstance(bound, (Real, np.number)) and not isinstance(bound, (bool, np.bool_)):
+        return float(bound)
+    if not isinstance(bound, DataArray):
+        raise TypeError(f"{what} must be a number, a string such as '250.0m', the name of a variable or a DataArray, "
+                        f"got {type(bound).__name__}")
+    dims = tuple(bound.dims)
+    if len(set(dims)) != len(dims) or not set(dims) <= set(_LINE_DIMS):
+        raise ValueError(f"{what} must have dimensions among ('channel', 'ping_time'), got {dims}")
+    for d, n in zip(dims, bound.shape):
+        if d not in sizes:
+            raise ValueError(f"{what} has the dimension {d!r}, which the masked variable lacks")
+        if n != sizes[d]:
+            raise ValueError(f"{what}: dimension {d!r} has length {n}, the dataset has {sizes[d]}")
+    if "ping_time" in dims and "ping_time" in bound.coords and "ping_time" in ds.coords:
+        if not np.array_equal(np.asarray(bound.coords["ping_time"]), np.asarray(ds["ping_time"].values)):
+            raise ValueError(f"{what} lies on another ping_time than the dataset: a line from another dataset")
+    kind = bound.data.tensor.dtype if is_device(bound.data) else np.asarray(bound.data).dtype
+    if (kind.is_complex or kind == torch.bool) if isinstance(kind, torch.dtype) else kind.kind not in "fiu":
+        raise TypeError(f"{what} must hold real numbers, got {kind}")
+    return bound
+
+
+def _bound_tensor(bound, dev):
+    """What ``_check_bound`` returned as a float64 device tensor that broadcasts against (C, P), or None."""
+    if bound is None:
+        return None
+    if isinstance(bound, float):
+        return torch.full((1, 1), bound, dtype=torch.float64, device=dev)
+    if is_device(bound.data):
+        t = bound.data.tensor
+        t = (t if t.device == dev else t.to(dev)).to(torch.float64)
+    else:
+        t = ops.to_device(np.ascontiguousarray(np.asarray(bound.data), dtype=np.float64), device=dev)
+    dims = tuple(bound.dims)
+    if dims == ("ping_time", "channel"):
+        return t.t()  # (a view: the kernel reads the line through its strides)
+    if dims == ("ping_time",):
+        return t.unsqueeze(0)
+    if dims == ("channel",):
+        return t.unsqueeze(1)
+    return t.reshape(1, 1) if dims == () else t
+
+
+def _lazy_range_rows(da, order):
+    """What a still unwritten ``echo_range`` / ``depth`` of ``compute_Sv`` / ``add_depth`` is a function of: (coefficient
+    rows, raw samples whose NaNs are its NaNs, scale, offset) with scale = offset = None for an echo_range.  None when
+    the variable is not of that kind (any longer): it is then read as an array."""
+    d = da.data
+    if not isinstance(d, LazyDeviceArray) or d.materialized or tuple(da.dims) != tuple(order) or len(order) != 3:
+        return None
+    base, scale, offset = d, None, None
+    rows = d.coef_rows()
+    if rows is None:
+        aff = d.affine_of()
+        if aff is None:
+            return None
+        base, scale, offset = aff
+        rows = base.coef_rows()
+    raw = base.nan_source()
+    if rows is None or raw is None or raw.dtype != torch.float32 or tuple(raw.shape) != d.shape \
+            or not raw.is_contiguous() or d.dtype not in (np.dtype("float32"), np.dtype("float64")):
+        return None
+    return rows, raw, scale, offset
+
+
+@xarray_io()
+def line_mask(ds, upper=None, lower=None, range_var="depth", var_name="Sv", closed="left", nan_line="exclude",
+              upper_offset=0.0, lower_offset=0.0, *, device=None):
+    """Boolean mask of the samples of ``ds[var_name]`` that lie between two lines: True where
+    ``upper + upper_offset <= r < lower + lower_offset`` (``closed="left"``) or
+    ``upper + upper_offset < r <= lower + lower_offset`` (``closed="right"``), ``r`` the value of ``ds[range_var]`` at the
+    sample -- what ``(ds["depth"] >= upper) & (ds["depth"] < lower)`` is with xarray.  It is the step between
+    ``detect_seafloor`` and ``apply_mask``: ``line_mask(ds_Sv, upper="10m", lower=bottom, lower_offset=-5.0)``.
+
+    ``upper`` / ``lower``: None (that side is not tested; at least one is given), a number, a string ``"<number>m"``, the
+    name of a variable of ``ds`` (looked up first), or a DataArray over ``()``, ``(ping_time,)``, ``(channel,)`` or
+    ``(channel, ping_time)`` in either order, of any real type, on the host or the device, whose sizes -- and, if it
+    carries one, whose ``ping_time`` coordinate -- are those of ``ds``.  The bound is the line converted to float64 plus
+    the (finite) offset, one float64 addition.  ``ds[var_name]`` gives the dimensions and shape only:
+    ``(channel, ping_time, X)`` or ``(ping_time, X)`` (another order: ``NotImplementedError``).  ``ds[range_var]`` has any
+    subset of them, so the 1-D ``depth`` / ``echo_range`` coordinate of an MVBS dataset serves as well as a cube.
+
+    Every comparison is made in float64 on the value ``ds[range_var]`` holds in its own type (float32 promotes exactly;
+    other types are converted to float64 first): the result is NumPy's, without a tolerance.  A NaN range gives False,
+    infinities compare as numbers.  Where a line is NaN, ``nan_line="exclude"`` makes the whole ping False (what
+    ``depth < NaN`` gives) and ``nan_line="ignore"`` leaves that side untested there (a ping without a detected bottom
+    keeps its column).
+
+    Returns the bool DataArray ``line_mask`` with the dimensions, shape and coordinates of ``ds[var_name]``, its data on
+    the device: it goes straight into ``apply_mask`` or ``regrid_mask``.  Sharded datasets are not supported.
+
+    Device work: one launch (``epa_line_mask``), 1 byte written per sample.  A range array is read where it lies, a
+    lower-dimensional one through zero strides.  An ``echo_range`` / ``depth`` that ``compute_Sv`` / ``add_depth`` left
+    unwritten is evaluated from its coefficient rows with the arithmetic that would write it, rounding to its type
+    included, so the decisions are those on the written array, which stays unwritten.  Host synchronisations: none."""
+    ds = from_xarray(ds)
+    if closed not in ("left", "right"):
+        raise ValueError(f"{closed} is not a valid option. Options are 'left' or 'right'.")
+    if nan_line not in ("exclude", "ignore"):
+        raise ValueError(f"{nan_line} is not a valid option. Options are 'exclude' or 'ignore'.")
+    if upper is None and lower is None:
+        raise ValueError("At least one of upper and lower must be given.")
+    for name, off in (("upper_offset", upper_offset), ("lower_offset", lower_offset)):
+        if isinstance(off, (bool, np.bool_)) or not isinstance(off, (Real, np.number)) or not np.isfinite(off):
+            raise ValueError(f"{name} must be a finite number, got {off!r}")
+    for name, v in (("var_name", var_name), ("range_var", range_var)):
+        if not isinstance(v, str):
+            raise TypeError(f"The input {name} must be a string!")
+        if v not in ds:
+            raise ValueError(f"The Dataset ds does not contain the variable {v}!")
+    src = ds[var_name]
+    order = tuple(src.dims)
+    has_chan = "channel" in order
+    if not ((len(order) == 3 and order[:2] == _LINE_DIMS) or (len(order) == 2 and order[0] == "ping_time")):
+        raise NotImplementedError(f"the dimensions of {var_name} must be (channel, ping_time, X) or (ping_time, X), "
+                                  f"got {order}")
+    shape = tuple(src.shape)
+    C, P, S = ((1,) + shape) if not has_chan else shape
+    sizes = dict(zip(order, shape))
+    rng = ds[range_var]
+    rdims = tuple(rng.dims)
+    if len(set(rdims)) != len(rdims) or not set(rdims) <= set(order):
+        raise ValueError(f"The dimensions of {range_var}, {rdims}, must be among those of {var_name}, {order}.")
+    if any(n != sizes[d] for d, n in zip(rdims, rng.shape)):
+        raise ValueError(f"The shape of {range_var}, {dict(zip(rdims, rng.shape))}, does not match {var_name}, {sizes}.")
+
+    if not is_device(rng.data) and np.asarray(rng.data).dtype.kind not in "fiu":
+        raise TypeError(f"{range_var} must hold real numbers, got {np.asarray(rng.data).dtype}")
+    upper, lower = _check_bound(ds, upper, "upper", sizes), _check_bound(ds, lower, "lower", sizes)
+
+    lazy = _lazy_range_rows(rng, order)
+    if lazy is not None:
+        dev = lazy[0].device
+    elif is_device(rng.data):
+        dev = rng.data.tensor.device
+    elif is_device(src.data) and not isinstance(src.data, LazyDeviceArray):
+        dev = src.data.tensor.device
+    else:
+        dev = resolve_device(device)
+    up_t, lo_t = _bound_tensor(upper, dev), _bound_tensor(lower, dev)
+
+    kw = dict(upper=up_t, lower=lo_t, upper_offset=float(upper_offset), lower_offset=float(lower_offset), closed=closed,
+              nan_line=nan_line)
+    if lazy is not None:
+        rows, raw, scale, offset = lazy
+        out = ops.line_mask((C, P, S), coef=rows, nan_raw=raw, scale=scale, offset=offset,
+                            dtype=torch.float64 if rng.data.dtype == np.dtype("float64") else torch.float32, **kw)
+    else:
+        if is_device(rng.data):
+            r_t = rng.data.tensor
+        else:
+            a = np.asarray(rng.data)
+            r_t = ops.to_device(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64),
+                                device=dev).reshape(a.shape)
+        if r_t.dtype not in (torch.float32, torch.float64):
+            r_t = r_t.double()
+        # the dimensions in the order of the cube (a view), a broadcast axis of length 1 for those the range lacks
+        r_t = r_t.permute([rdims.index(d) for d in order if d in rdims])
+        for i, d in enumerate(order):
+            if d not in rdims:
+                r_t = r_t.unsqueeze(i)
+        out = ops.line_mask((C, P, S), range=r_t if has_chan else r_t.unsqueeze(0), **kw)
+    if not has_chan:
+        out = out[0]
+    return DataArray(
+        DeviceArray(out), order, coords=dict(src.coords), name="line_mask",
+        attrs={"mask_type": "line", "range_var": range_var, "closed": closed, "nan_line": nan_line,
+               "upper_offset": float(upper_offset), "lower_offset": float(lower_offset)})

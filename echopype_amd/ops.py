@@ -1056,8 +1056,75 @@ def regrid_mask(mask, range, bin_start, n_tbins, range_bin, n_rbins, *, group=No
     return buf[:cells].view(G, n_tbins, n_rbins), nonbinary
 
 
+def _line_of(line, C, P, dev, what):
+    """A bound of ``line_mask`` as (pointer, channel stride, ping stride): a float64 device tensor of shape (C, P), or one
+    that broadcasts to it -- expanded, not copied, so a broadcast dimension has stride 0."""
+    if line is None:
+        return None, 0, 0
+    if line.dtype != torch.float64 or not line.is_cuda or line.device != dev:
+        raise ValueError(f"line_mask: {what} must be a float64 tensor on {dev}, got {line.dtype} on {line.device}")
+    try:
+        v = line.expand(C, P)
+    except RuntimeError:
+        raise ValueError(f"line_mask: {what} of shape {tuple(line.shape)} does not broadcast to ({C}, {P})") from None
+    return ctypes.c_void_p(v.data_ptr()), v.stride(0), v.stride(1)
+
+
+def line_mask(shape, *, range=None, coef=None, nan_raw=None, scale=None, offset=None, dtype=None, upper=None, lower=None,
+              upper_offset=0.0, lower_offset=0.0, closed="left", nan_line="exclude"):
+    """bool (C, P, S) = ``shape``: True where ``upper + upper_offset <= r < lower + lower_offset`` (``closed="right"``:
+    ``<`` and ``<=``), compared in float64 (``epa_line_mask``).  The range ``r`` is either the float32 / float64 tensor
+    ``range``, of that shape or broadcasting to it (read through its strides: nothing is copied), or what a lazy array
+    would hold: ``coef`` (C, P, 8) coefficient rows, NaN where ``nan_raw`` (C, P, S) float32 is, times ``scale`` plus
+    ``offset`` (C, P) float64 for a depth, rounded to ``dtype``.  ``upper`` / ``lower``: float64 device tensors that
+    broadcast to (C, P), or None (not tested).  ``nan_line``: a NaN bound empties its row ("exclude") or is not tested
+    there ("ignore")."""
+    C, P, S = (int(n) for n in shape)
+    if closed not in ("left", "right"):
+        raise ValueError(f"line_mask: closed must be 'left' or 'right', got {closed!r}")
+    if nan_line not in ("exclude", "ignore"):
+        raise ValueError(f"line_mask: nan_line must be 'exclude' or 'ignore', got {nan_line!r}")
+    if upper is None and lower is None:
+        raise ValueError("line_mask: at least one of upper and lower must be given")
+    if (range is None) == (coef is None):
+        raise ValueError("line_mask: the range comes as an array or as coefficient rows, one of the two")
+    flags = (_lib.LINE_CLOSED_RIGHT if closed == "right" else 0) | (_lib.LINE_NAN_IGNORE if nan_line == "ignore" else 0)
+    if range is not None:
+        if range.dtype not in _DT or not range.is_cuda:
+            raise ValueError(f"line_mask: range must be a float32 / float64 device tensor, got {range.dtype} on {range.device}")
+        dev, dtype = range.device, range.dtype
+        try:
+            rv = range.expand(C, P, S)
+        except RuntimeError:
+            raise ValueError(f"line_mask: range of shape {tuple(range.shape)} does not broadcast to {(C, P, S)}") from None
+        r_args = (ctypes.c_void_p(rv.data_ptr()), *rv.stride(), None, None, None, None)
+    else:
+        dev = coef.device
+        if coef.dtype != torch.float64 or tuple(coef.shape) != (C, P, _lib.NCOEF):
+            raise ValueError(f"line_mask: coef must be float64 of shape {(C, P, _lib.NCOEF)}, got {coef.dtype} "
+                             f"{tuple(coef.shape)}")
+        if nan_raw is not None and (nan_raw.dtype != torch.float32 or tuple(nan_raw.shape) != (C, P, S)):
+            raise ValueError(f"line_mask: nan_raw must be float32 of shape {(C, P, S)}, got {nan_raw.dtype} "
+                             f"{tuple(nan_raw.shape)}")
+        if (scale is None) != (offset is None):
+            raise ValueError("line_mask: scale and offset come together")
+        for name, t in (("scale", scale), ("offset", offset)):
+            if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (C, P)):
+                raise ValueError(f"line_mask: {name} must be float64 of shape {(C, P)}, got {t.dtype} {tuple(t.shape)}")
+        dtype = torch_dtype(dtype)
+        r_args = (None, 0, 0, 0, _p(coef), _p(nan_raw), _p(scale), _p(offset))
+    up, up_c, up_p = _line_of(upper, C, P, dev, "upper")
+    lo, lo_c, lo_p = _line_of(lower, C, P, dev, "lower")
+    out = torch.empty((C, P, S), dtype=torch.bool, device=dev)
+    if out.numel() == 0:
+        return out
+    call("epa_line_mask", *r_args, _DT[dtype], up, up_c, up_p, float(upper_offset), lo, lo_c, lo_p, float(lower_offset),
+         flags, C, P, S, _p(out), _stream())
+    return out
+
+
 # ---- echo summary statistics per row (metrics.*) ------------------------------------------------------------------------
-METRICS = ("abundance", "center_of_mass", "dispersion", "evenness", "aggregation")
+METRICS =("abundance", "center_of_mass", "dispersion", "evenness", "aggregation")
 
 
 def echo_metrics(sv, range, *, cm=None, want=METRICS, _max_grid=0):

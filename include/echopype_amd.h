@@ -848,6 +848,30 @@ int epa_regrid_mask(const uint8_t* mask, const int32_t* group, int T, int P, int
                     int range_per_ping, const int32_t* bin_start, int n_tbins, double range_bin, int n_rbins,
                     unsigned bin_flags, int func, uint8_t* out, int32_t* nonbinary_out, epa_stream_t stream);
 
+/* ---- mask.line_mask: the samples between two lines ---------------------------------------------------------------------
+ * out[c, p, s] = ub <= r < lb, or ub < r <= lb with EPA_LINE_CLOSED_RIGHT, for r the range of sample (c, p, s) and
+ * ub = upper[c, p] + upper_offset, lb = lower[c, p] + lower_offset (one float64 addition each).  out u8 [C*P*S],
+ * contiguous, any alignment; one launch, no scratch.  All comparisons are float64 on r promoted exactly from dtype, so
+ * the result is NumPy's for r.astype(float64) against the float64 bounds: r NaN gives 0, +-inf compare as numbers.
+ *   upper, lower : f64 on the device, element (c, p) at [c*stride_c + p*stride_p], a stride of 0 broadcasts (a scalar
+ *            bound: one element, both strides 0); NULL: that bound is not tested (at least one is given).  A bound
+ *            that is NaN at (c, p) makes the whole row 0, or, with EPA_LINE_NAN_IGNORE, is not tested in that row.
+ *   the range, one of two forms:
+ *     range : an array of dtype (F32 / F64), element (c, p, s) at [c*range_stride_c + p*range_stride_p +
+ *            s*range_stride_s], a stride of 0 broadcasts: (S,), (C, S), (P, S) and (C, P, S) ranges are read where they lie
+ *     coef  : f64 [C*P*EPA_NCOEF] power-sample coefficient rows: r = (dtype)(fl(fl(s*ra)*rb) + r0), NaN where nan_raw
+ *            (f32 [C*P*S], or NULL) is NaN, then, when scale and offset (f64 [C*P], both or neither) are given,
+ *            r = (dtype)offset + fl((dtype)scale * r) in dtype: the values epa_range_power / epa_depth_rows write, bit for
+ *            bit, so the decisions are those on the written array, which is not needed
+ * Negative strides, S > 2^30 and a NaN offset are refused. */
+#define EPA_LINE_CLOSED_RIGHT 1u /* (ub, lb] instead of [ub, lb) */
+#define EPA_LINE_NAN_IGNORE 2u   /* a NaN bound is not tested instead of emptying its row */
+int epa_line_mask(const void* range, long long range_stride_c, long long range_stride_p, long long range_stride_s,
+                  const double* coef, const float* nan_raw, const double* scale, const double* offset, int dtype,
+                  const double* upper, long long upper_stride_c, long long upper_stride_p, double upper_offset,
+                  const double* lower, long long lower_stride_c, long long lower_stride_p, double lower_offset,
+                  unsigned flags, int C, int P, int S, uint8_t* out, epa_stream_t stream);
+
 /* ---- echo summary statistics per row: metrics.abundance / center_of_mass / dispersion / evenness / aggregation --------
  * (metrics/summary_statistics.py).  sv [R*S] and range of dtype F32 / F64; range is [R*S] when range_per_row != 0,
  * else [S], shared by all rows.  For j = 1 .. S-1: dz_j = range_j - range_{j-1} rounded in dtype, 0 -> NaN;
