@@ -52,6 +52,11 @@ EK80_NFFT = 2048
 SEAFLOOR_STATE_WORDS = 16  # EPA_SEAFLOOR_STATE_WORDS
 SHOAL_STATE_WORDS = 8  # EPA_SHOAL_STATE_WORDS
 SHOAL_QUEUE_BOXES = 4096  # EPA_SHOAL_QUEUE_BOXES
+SHOAL_STATE_ERROR, SHOAL_STATE_COUNT = 0, 1  # EPA_SHOAL_STATE_ERROR, EPA_SHOAL_STATE_COUNT
+REGION_FIELDS = ("n_valid", "n_range", "sv_max", "range_min", "range_max", "sum_sv", "sum_range", "sum_sv_range",
+                 "sum_sv_at_range", "sum_dz", "sum_sv_dz")  # enum epa_region_word, in its order
+REGION_WORDS = 11  # EPA_REGION_WORDS
+REGION_ID_SAMPLES, REGION_ID_FIRST, REGION_ID_WORDS = 0, 1, 2  # EPA_REGION_ID_*
 
 
 class EpaError(RuntimeError):
@@ -185,6 +190,8 @@ SIGNATURES = {
     "epa_raw_index": [_vp, _ll, _vp, _ll, ctypes.POINTER(_ll), ctypes.POINTER(_ll)],
     "epa_raw0_unpack": [_vp, _ll, _ll, _vp, _vp, _i, _ll, _ll, _i, _vp, _vp, _vp, _vp],
     "epa_nmea_positions": [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _vp],
+    "epa_region_stats": [_vp, _ll, _ll, _vp, _vp, _i, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp],
+    "epa_region_labels": [_vp, _ll, _ll, _vp, _ll, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

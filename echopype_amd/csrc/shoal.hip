@@ -45,8 +45,8 @@ constexpr int kBigBlocks = 2048;
 
 // state words (EPA_SHOAL_STATE_WORDS u64, zeroed by the caller)
 enum : int {
-  kError = 0,  // union-find loops that reached their bound, component ids beyond the table
-  kCount = 1,  // components numbered
+  kError = EPA_SHOAL_STATE_ERROR,  // union-find loops that reached their bound, component ids beyond the table
+  kCount = EPA_SHOAL_STATE_COUNT,  // components numbered
   kBig = 2,    // link boxes queued for the whole-grid scan
 };
 

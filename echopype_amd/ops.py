@@ -967,6 +967,79 @@ def shoal_echoview_link(plane, parent, table, idim, jdim, mincan, maxlink, minsh
     return plane
 
 
+# ---- region tables (mask.label_regions, mask.region_statistics) --------------------------------------------------------
+def region_stats(code, n, state, sv=None, range=None):
+    """One sweep over the code plane ``code`` (P, S) of ``shoal_label`` with ``n`` components, and over ``sv``
+    (C, P, S) with its ``range`` (same float type, (C, P, S) or broadcasting to it: read through its strides, samples
+    adjacent) -> (``stats`` int64 (C, n, 11), ``ids`` int64 (n, 2)), the zero-initialised tables of ``epa_region_stats``;
+    ``region_tables`` names their words.  ``sv`` None: ``ids`` alone (``stats`` has C = 0).  A code that names no id
+    below ``n`` counts into ``state[0]``."""
+    P, S = code.shape
+    n = int(n)
+    dev = code.device
+    if code.dtype != torch.int64:
+        raise ValueError(f"region_stats: the code plane of shoal_label (int64) expected, got {code.dtype}")
+    if sv is None:
+        C, dt, sv_p, r_p, rs_c, rs_p = 0, _lib.F64, None, None, 0, 0
+    else:
+        if sv.dim() != 3 or tuple(sv.shape[1:]) != (P, S) or sv.dtype not in _DT:
+            raise ValueError(f"region_stats: sv must be float32 / float64 of shape (C, {P}, {S}), got {sv.dtype} "
+                             f"{tuple(sv.shape)}")
+        if range is None or range.dtype != sv.dtype or not range.is_cuda:
+            raise ValueError("region_stats: range must be a device tensor of sv's type")
+        C = sv.shape[0]
+        try:
+            rv = range.expand(C, P, S)
+        except RuntimeError:
+            raise ValueError(f"region_stats: range of shape {tuple(range.shape)} does not broadcast to {(C, P, S)}") from None
+        if S > 1 and rv.stride(2) != 1:  # (samples apart, or no sample axis: the one case copied)
+            rv = rv.contiguous()
+        dt, sv_p, r_p = _DT[sv.dtype], _p(sv), ctypes.c_void_p(rv.data_ptr())
+        rs_c, rs_p = (rv.stride(0) if C > 1 else 0), (rv.stride(1) if P > 1 else 0)
+    stats = torch.zeros((C, n, _lib.REGION_WORDS), dtype=torch.int64, device=dev)
+    ids = torch.zeros((n, _lib.REGION_ID_WORDS), dtype=torch.int64, device=dev)
+    call("epa_region_stats", _p(code), P, S, sv_p, r_p, dt, C, rs_c, rs_p, n, _p(stats) if C else None, _p(ids),
+         _p(state), _stream())
+    return stats, ids
+
+
+def _unkey(k):
+    """The float64 values of order-preserving u64 keys (``epa_region_word``); key 0 (nothing seen) -> NaN."""
+    k = np.ascontiguousarray(k).view(np.uint64)
+    top = np.uint64(1) << np.uint64(63)
+    bits = np.where(k & top, k & ~top, ~k)
+    return np.where(k == 0, np.nan, bits.view(np.float64))
+
+
+def region_tables(stats, ids, n_pix):
+    """The downloaded tables of ``region_stats`` (int64 NumPy arrays (C, n, 11) and (n, 2)) by name -> dict: the
+    int64 counts ``n_valid`` / ``n_range`` (C, n) and ``n_samples`` (n,), ``first`` (n,) the smallest linear pixel
+    index, the float64 extrema ``sv_max`` / ``range_min`` / ``range_max`` (NaN: none seen) and the float64 raw sums
+    ``sum_*`` (C, n)."""
+    stats, ids = np.ascontiguousarray(stats), np.ascontiguousarray(ids)
+    out = {"n_samples": ids[:, _lib.REGION_ID_SAMPLES].copy(), "first": int(n_pix) - ids[:, _lib.REGION_ID_FIRST]}
+    for j, name in enumerate(_lib.REGION_FIELDS):
+        w = np.ascontiguousarray(stats[:, :, j])
+        if name.startswith("n_"):
+            out[name] = w
+        elif name.startswith("sum_"):
+            out[name] = w.view(np.float64)
+        else:
+            out[name] = _unkey(w)
+    out["range_min"] = -out["range_min"]
+    return out
+
+
+def region_labels(code, rank):
+    """int32 (P, S): ``rank[id]`` on the pixels of component id of the code plane ``code``, 0 on background."""
+    P, S = code.shape
+    if rank.dtype != torch.int32 or rank.dim() != 1 or rank.numel() == 0:
+        raise ValueError(f"region_labels: rank must be a non-empty int32 vector, got {rank.dtype} {tuple(rank.shape)}")
+    labels = torch.empty((P, S), dtype=torch.int32, device=code.device)
+    call("epa_region_labels", _p(code), P, S, _p(rank), rank.numel(), _p(labels), _stream())
+    return labels
+
+
 # ---- transient-noise detectors (clean.detect_transient) --------------------------------------------------------------
 def transient_fielding(sv, chan, n, thr0, thr1, maxts):
     """Fielding's transient-noise mask of a (C, P, S) cube -> bool (C, P, S), True = valid.  ``chan``: host int (C, 4)

@@ -764,6 +764,9 @@ int epa_seafloor_bottom(const long long* parent, const unsigned char* mask, long
  * [0] union-find loops that reached their bound (non-zero: the result is not to be trusted), [1] components. */
 #define EPA_SHOAL_STATE_WORDS 8
 #define EPA_SHOAL_QUEUE_BOXES 4096
+/* the two state words a caller reads: [0] and [1] above */
+#define EPA_SHOAL_STATE_ERROR 0
+#define EPA_SHOAL_STATE_COUNT 1
 
 /* plane = sv > thr (compared in f64: thr is not rounded to dtype; NaN background); then along range in every ping, runs of background of at
  * most maxvgap samples with foreground on both sides become foreground; then, on that result, the same along pings
@@ -792,6 +795,51 @@ int epa_shoal_echoview_link(const long long* parent, long long P, long long S, i
                             double mincan0, double mincan1, double maxlink0, double maxlink1, double minsho0,
                             double minsho1, int* queue, unsigned long long* state, unsigned char* plane,
                             epa_stream_t stream);
+
+/* ---- region tables: mask.label_regions, mask.region_statistics (mask/regions.py) -------------------------------------
+ * code: the parent plane epa_shoal_label left, i64 [P*S]: -(id + 2) on the pixels of component id, -1 on background.
+ * n: the number of components, state[EPA_SHOAL_STATE_COUNT] as the host read it (1 .. min(P*S, 0x70000000)).
+ *
+ * The per-(channel, id) table: EPA_REGION_WORDS 64-bit words per entry, counts as u64, sums as f64 bits, extrema as
+ * order-preserving keys (key 0: nothing seen; else the f64 bits with the sign bit set for v >= 0, all bits inverted
+ * for v < 0).  With sv = 10^(Sv / 10) in f64, r the range and dz[s] = r[s] - r[s-1] (dz[0] = dz[1]; NaN when S == 1),
+ * every word skips the pixels where one of its own operands is NaN: */
+enum epa_region_word {
+  EPA_REGION_N_VALID = 0,        /* pixels whose Sv is not NaN */
+  EPA_REGION_N_RANGE = 1,        /* pixels whose r is not NaN */
+  EPA_REGION_SV_MAX = 2,         /* key of max Sv */
+  EPA_REGION_RANGE_MIN = 3,      /* key of max(-r): the minimum of r, negated */
+  EPA_REGION_RANGE_MAX = 4,      /* key of max r */
+  EPA_REGION_SUM_SV = 5,         /* sum sv */
+  EPA_REGION_SUM_RANGE = 6,      /* sum r */
+  EPA_REGION_SUM_SV_RANGE = 7,   /* sum sv r, over the pixels with both */
+  EPA_REGION_SUM_SV_AT_RANGE = 8,/* sum sv over the same pixels */
+  EPA_REGION_SUM_DZ = 9,         /* sum dz */
+  EPA_REGION_SUM_SV_DZ = 10      /* sum sv dz, over the pixels with both */
+};
+#define EPA_REGION_WORDS 11
+/* The per-id table: EPA_REGION_ID_WORDS u64 words per entry. */
+#define EPA_REGION_ID_SAMPLES 0 /* pixels of the component */
+#define EPA_REGION_ID_FIRST 1   /* P*S - (its smallest linear pixel index ping * S + sample); 0: the id was never met */
+#define EPA_REGION_ID_WORDS 2
+
+/* One sweep over the code plane and the C planes of sv and range (dtype F32 / F64, converted to f64 exactly; every
+ * sum is f64): stats u64 [C*n*EPA_REGION_WORDS] and ids u64 [n*EPA_REGION_ID_WORDS], both zeroed by the caller, are
+ * added to.  sv is [C*P*S]; the sample (c, p, s) of the range is range[c * range_stride_c + p * range_stride_p + s]
+ * (element strides >= 0; 0 shares a row between channels / pings: nothing has to be expanded).  C == 0: ids alone
+ * (sv, range and stats may be NULL).  A code that names no id in [0, n) adds 1 to state[EPA_SHOAL_STATE_ERROR] and
+ * writes nothing.  Updates are combined over runs of equal code inside a wave and along the pings a wave walks: the
+ * tables take one update per run, not one per pixel.  Sums can differ in their last bits between two calls (the
+ * order of the updates); counts and extrema cannot. */
+int epa_region_stats(const long long* code, long long P, long long S, const void* sv, const void* range, int dtype,
+                     long long C, long long range_stride_c, long long range_stride_p, long long n,
+                     unsigned long long* stats, unsigned long long* ids, unsigned long long* state,
+                     epa_stream_t stream);
+
+/* labels i32 [P*S] = rank[id] on the pixels of component id (rank i32 [n]: the number the caller gives each id),
+ * 0 on background and on codes that name no id in [0, n). */
+int epa_region_labels(const long long* code, long long P, long long S, const int* rank, long long n, int* labels,
+                      epa_stream_t stream);
 
 /* ---- transient-noise detectors: clean.detect_transient (clean/transient_noise/) -------------------------------------
  * sv is [C*P*S] of dtype F32 / F64, mask_out u8 [C*P*S]: 1 = VALID, 0 = transient noise; written completely by the
