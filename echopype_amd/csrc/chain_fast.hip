@@ -426,10 +426,14 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
         const int e = eA + (j < 2 ? 0 : 128) + (j & 1);
         const ColBase<T> cb{SRA_LDS ? col_sra[e] : col[j].sra, col_nL[e], col_lgs[e], (T)0};
         const T svj = calibrate<T>(cb, in[j], r, r0v, g_, a2, A0, nspread, x, mt.log_tab);
-        if (RMAX) {  // as stored (T); x + 0 * raw is the range or NaN, and v_max_f64 / v_min_f64 skip the NaN
-          const double xq = fma((double)in[j], 0.0, (double)(T)x);
-          xmax = vmax_num(xmax, xq);
-          xmin = vmin_num(xmin, xq);
+        if (RMAX) {  // as stored (T).  The echo_range is NaN where the raw sample is NaN and nowhere else (an infinite
+          // sample keeps its range): only the lanes whose sample is a number take it, no masked copy of the range is
+          // made.  (As compiled for gfx950: one v_cmp_o_f32 and the exec-mask bookkeeping around v_max / v_min, where
+          // x + 0 * raw took a conversion and an fma.)
+          if (in[j] == in[j]) {
+            xmax = vmax_num(xmax, (double)(T)x);
+            xmin = vmin_num(xmin, (double)(T)x);
+          }
           nnan += (unsigned)__builtin_popcountll(__ballot(in[j] != in[j]));  // (per wavefront, in a scalar register)
         }
         // the block mean uses the UNMASKED range (the generic kernel does too: a masked sample has a NaN Sv)
@@ -1113,7 +1117,9 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
         const T sj = (T)((j < 2 ? sA : sB) + (j & 1));
         // a NaN sample needs no masking: it makes the exponential, hence lin, NaN by itself
         const T e = epa::lin_from_db_lean(q.g * (T)in[j], mt.exp2_tab);
-        const T lin = ecol[j] * fma(-q.cnk2, sj * sj, (e * c2[j]) * q.csv);
+        // (e times the PRODUCT of the constants: 10^(g raw / 10) * (s - d)^2 alone overflows T 30 .. 40 dB before
+        //  10^(Sv/10) does -- C_sv is tiny -- while e * (c2 * C_sv) = lin(Sv) / E_p(s) <= lin(Sv))
+        const T lin = ecol[j] * fma(-q.cnk2, sj * sj, e * (c2[j] * q.csv));
         sn[j] = xok ? fma(q.a2k, sj, q.snp + sn20[j]) : epa::M<T>::nan();  // echo_range is NaN where the input is
         const T corr = lin > (T)0 ? (T)10 * epa::fast_log10_lean(lin, mt.log_tab, lk) : epa::M<T>::nan();
         const bool keep = corr - sn[j] > snr;
@@ -1181,7 +1187,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
             const T e = epa::lin_from_db_lean(q.g * (T)inv, mt.exp2_tab);
             const T E = epa::lin_from_db_lean(q.a2k * (T)sj, mt.exp2_tab);
             const T mx = fmax((T)x, (T)1);
-            const T lin = E * fma(-qr.cn, mx * mx, (e * cc) * q.csv);
+            const T lin = E * fma(-qr.cn, mx * mx, e * (cc * q.csv));  // (the product of the constants first: see above)
             const T tl = x >= 1.0 ? (q.snp - qr.nb) + sn20j : (T)0;  // 20 log10(R >= 1 ? R : 1)
             const T snv = xok ? (qr.nb + tl) + q.a2k * (T)sj : epa::M<T>::nan();
             const T corr = lin > (T)0 ? (T)10 * epa::fast_log10_lean(lin, mt.log_tab, lk) : epa::M<T>::nan();

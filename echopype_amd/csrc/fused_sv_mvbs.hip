@@ -141,11 +141,12 @@ __device__ __forceinline__ T process_sample(Column<T>& c, float raw, const epa::
   const T NaN = epa::M<T>::nan();
   const double x = fma(c.sra, r.rb, r0v);  // echo_range = (s*ra)*rb [+0]
   if (STATS) {
-    // {min, max, NaN count} of the echo_range, NaN exactly where the raw sample is: x + 0 * raw is the range or NaN,
-    // and v_max_f64 / v_min_f64 return the operand that is a number
-    const double xq = fma((double)raw, 0.0, x);
-    xmax = vmax_num(xmax, xq);
-    xmin = vmin_num(xmin, xq);
+    // {min, max, NaN count} of the echo_range, which is NaN exactly where the raw sample is NaN (an infinite sample
+    // keeps its range): only the lanes whose sample is a number take the range, no masked copy of it is made
+    if (raw == raw) {
+      xmax = vmax_num(xmax, x);
+      xmin = vmin_num(xmin, x);
+    }
     nnan += (unsigned)__builtin_popcountll(__ballot(raw != raw));  // (per wavefront, in a scalar register)
   }
   const double rtd = x - r.shift;
@@ -205,16 +206,24 @@ __device__ __forceinline__ void process_pair(Column<T>& c0, Column<T>& c1, float
       s11 = fma(g, (T)in.y, nspread * (log10_slow<T>(rt1) - log10_slow<T>((T)(r.ra * r.rb))));
     s10 = pos0 ? s10 : NaN;
     s11 = pos1 ? s11 : NaN;
-    if (STATS) {  // x + 0 * raw is the range or NaN; v_max_f64 / v_min_f64 return the operand that is a number
-      const double xq0 = fma((double)in.x, 0.0, x0), xq1 = fma((double)in.y, 0.0, x1);
-      xmax = vmax_num(vmax_num(xmax, xq0), xq1);
-      xmin = vmin_num(vmin_num(xmin, xq0), xq1);
+    if (STATS) {  // the coordinate is NaN where the raw sample is NaN -- not where it is +-inf: such a sample keeps its
+      // range.  Only the lanes whose sample is a number take it (no masked copy of the coordinate is made);
+      // v_max_f64 / v_min_f64 return the operand that is a number (a NaN coefficient / depth row)
+      if (in.x == in.x) {
+        xmax = vmax_num(xmax, x0);
+        xmin = vmin_num(xmin, x0);
+      }
+      if (in.y == in.y) {
+        xmax = vmax_num(xmax, x1);
+        xmin = vmin_num(xmin, x1);
+      }
       // (a NaN coordinate: the raw sample's NaN, or a NaN coefficient / depth row)
-      nnan += (unsigned)__builtin_popcountll(__ballot(xq0 != xq0)) + (unsigned)__builtin_popcountll(__ballot(xq1 != xq1));
+      nnan += (unsigned)__builtin_popcountll(__ballot((in.x != in.x) | (x0 != x0))) +
+              (unsigned)__builtin_popcountll(__ballot((in.y != in.y) | (x1 != x1)));
     }
-    if (DEPTH == 2) {  // the depth array is NaN where the echo_range is: where the raw sample is
-      d0 = fma((T)in.x, (T)0, d0);
-      d1 = fma((T)in.y, (T)0, d1);
+    if (DEPTH == 2) {  // the depth array is NaN where the echo_range is: where the raw sample is NaN
+      d0 = epa::nan_where_nan(d0, in.x);
+      d1 = epa::nan_where_nan(d1, in.y);
     }
   }
   if (DEPTH == 2) epa::store_nt2(depth_dst, d0, d1);

@@ -21,6 +21,18 @@ struct RowK {
   __device__ __forceinline__ double range(int s) const { return ((double)s * ra) * rb + r0; }
 };
 
+// The mask of the echo_range (range.py:145-147): NaN where the raw sample is NULL and nowhere else -- a raw sample of
+// +-inf keeps its range (x + 0 * raw made it NaN as well: inf * 0).  Here x + 0 * 2^-|raw|: 2^-|raw| lies in [0, 1] for
+// every number, +-inf included, and is NaN for a NaN.  A select on raw == raw is the plainer form, but the NaN it selects
+// has to sit in a register (VOP2 takes no literal next to vcc): by the compiler's resource report that is one VGPR more
+// on every float instance of the fused kernel that uses it (DEPTH 2: 118 -> 119) and, selecting the sample's own NaN
+// instead, 16 bytes of scratch per lane on the double one, which sits at its 128-VGPR cap.  (A depth of -0.0 comes out
+// as +0.0: equal under every comparison the library makes.)
+template <typename T>
+__device__ __forceinline__ T nan_where_nan(T x, float raw) {
+  return fma((T)__builtin_amdgcn_exp2f(-__builtin_fabsf(raw)), (T)0, x);
+}
+
 template <typename T>
 __device__ __noinline__ T log10_noinline(T x) {
   return M<T>::log10(x);

@@ -10,14 +10,15 @@ reads it; ``materialize_echo_range=True`` runs the two calls instead).  The fuse
 calls as well -- same results either way.
 """
 import numpy as np
+import torch
 
 from . import _lib, ops
 from .calibrate.api import CALIBRATOR, _compute_cal, _finalize_cal_ds
 from .clean.api import remove_background_noise
 from .clean.utils import add_remove_background_noise_attrs, extract_dB
 from .commongrid.api import _assemble_mvbs, compute_MVBS
-from .commongrid.deferred import (CPS, deferred_mvbs, launch_or_decline, n_range_bins, range_cap, range_edges,
-                                  sorted_time_grid, time_bin_start)
+from .commongrid.deferred import (CPS, deferred_mvbs, launch_or_decline, n_range_bins, nan_coordinate_warning, range_cap,
+                                  range_edges, sorted_time_grid, time_bin_start)
 from .commongrid.utils import _parse_x_bin, resample_edges
 from .utils.prov import echopype_prov_attrs, insert_processing_level
 from .xr_lite import DataArray, Dataset, DeviceArray, defer_mvbs_enabled, xarray_io
@@ -80,7 +81,7 @@ def compute_Sv_MVBS(echodata, *, range_bin="20m", ping_time_bin="20s", skipna=Tr
     def launch():  # (a degenerate grid -- one sample per ping, no valid range -- declines like the kernel would)
         return None if n_cap < 1 else ops.sv_mvbs_fused(
             raw, coef, bin_start, n_t, range_bin_m, n_cap, cal_flags=flags, skipna=True, closed="left",
-            fill_value=fill_value, dtype=cal.dtype, want_range_max=True, want_partials=_shard is not None)
+            fill_value=fill_value, dtype=cal.dtype, want_range_stats=True, want_partials=_shard is not None)
 
     # declined: the two calls deal with it (on a shard: every rank, the collectives that follow differ)
     got = launch_or_decline(launch, shard=_shard, vote=(first_bin, last_bin, fill_value, (C, n_t, n_cap), raw.device))
@@ -94,13 +95,20 @@ def compute_Sv_MVBS(echodata, *, range_bin="20m", ping_time_bin="20s", skipna=Tr
     if _shard is not None and range_var_max is None:
         rmax_t = _shard.range_max_device(rmax_t)
     rmax_f = ops.fetch_async(rmax_t)  # (on its way to the host behind this kernel / all-reduce, on a side stream)
+    # ... and the number of NaN echo_range values, for the reference's NaN-coordinate warning (utils.py:595-608): the
+    # fused kernel counts them; the generic kernel leaves no count, there they are the NaN raw samples
+    if res["range_stats_filled"]:
+        nan_f = ops.fetch_async(res["range_stats"][2:3])
+    else:
+        nan_f = ops.fetch_async(torch.isnan(raw).sum().reshape(1)) if flags & _lib.FLAG_MASK_RANGE else None
 
     # (echo_range is not written: coefficient rows + the raw samples' NaN pattern; epa_range_power on first read)
     ds_Sv = _sv_dataset(cal, echodata, res["Sv"], None, raw, coef, flags, tau_eff, waveform_mode, encode_mode,
                         range_last=True)
     # off a shard a trim that cannot be done bins again from the Sv array, exactly: the public call on the snapshot
     return ds_Sv, deferred_mvbs(ds_Sv, mv_full, n_cap,
-                                lambda: (float(rmax_f.item()) if range_var_max is None else r_cap, 0), range_var_max,
+                                lambda: (float(rmax_f.item()) if range_var_max is None else r_cap,
+                                         int(nan_f.item()) if nan_f is not None else 0), range_var_max,
                                 r_cap, (ping_time, e0 + lo * dt, dt), "echo_range", range_bin_m, ping_time_bin,
                                 fallback=(lambda ds: compute_MVBS(ds, **mv_kw)) if _shard is None else None,
                                 defer=defer_mvbs_enabled())
@@ -187,12 +195,16 @@ def compute_Sv_clean_MVBS(echodata, ping_num, range_sample_num, *, background_no
         return separate_calls()
     alpha2 = coef[..., _lib.CF_ALPHA2].contiguous()  # 2 * sound_absorption per (channel, ping)
 
-    sv_t, _, noise, rmax = ops.sv_noise_fused(
+    sv_t, _, noise, rmax, rstats = ops.sv_noise_fused(
         raw, coef, alpha2, ping_num, range_sample_num, flags=flags, dtype=cal.dtype,
-        noise_max=float("nan") if nmax is None else float(nmax), want_range_max=True)
+        noise_max=float("nan") if nmax is None else float(nmax), want_range_max=True, want_range_stats=True)
+    n_nan_range = int(rstats[2].item())  # (rmax: waited for, by design -- the grid is built from it)
+    if n_nan_range < 0:  # the generic kernel leaves the maximum only: the NaN echo_range values are the NaN raw samples
+        rstats = None
+        n_nan_range = int(torch.isnan(raw).sum().item()) if flags & _lib.FLAG_MASK_RANGE else 0
     e0, dt, n_t = resample_edges(ping_time, ping_time_bin)
     bin_start = ops.time_bin_offsets(ops.to_device(ns), e0, dt, n_t, closed=closed)
-    r_edges = range_edges(range_cap(range_var_max, rmax), range_bin_m)  # (rmax: waited for, by design)
+    r_edges = range_edges(range_cap(range_var_max, rmax), range_bin_m)
     n_r = len(r_edges) - 1
     if n_r < 1:  # no valid range, or a degenerate grid: the separate calls raise / return the empty MVBS the reference would
         return separate_calls()
@@ -217,6 +229,10 @@ def compute_Sv_clean_MVBS(echodata, ping_num, range_sample_num, *, background_no
     prov["processing_function"] = "clean.remove_background_noise"
     ds_Sv.attrs.update(prov)
     ds_Sv = insert_processing_level(ds_Sv, "L*B", input_ds=ds_Sv)
+    if rstats is not None and not materialize_echo_range:  # (the lazy echo_range carries what pass 1 found)
+        ds_Sv["echo_range"].data.set_stats(rstats)
+    if n_nan_range > 0:
+        nan_coordinate_warning("echo_range")
     ds_MVBS = _assemble_mvbs(ds_Sv, res["MVBS"], "channel", ping_time, e0, dt, n_t, r_edges, "echo_range",
                              range_bin_m, ping_time_bin, closed)
     return ds_Sv, ds_MVBS

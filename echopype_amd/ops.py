@@ -1643,7 +1643,8 @@ def sv_noise_fused(raw, coef, alpha2, ping_num, range_sample_num, *, cal_type="S
                    want_range_stats=False, ping_phase=0, want_edges=False):
     """K1+K6 -> (Sv|None, echo_range|None, noise (C, ceil((P + ping_phase)/ping_num)) f64[, nanmax(echo_range)]).
     ``want_range_stats``: the last element is instead the f64 device tensor {nanmin, nanmax, NaN count} of the echo_range
-    (NaN count -1: the kernel that served the configuration leaves none).  ``ping_phase`` / ``want_edges``: a ping shard
+    (NaN count -1: the kernel that served the configuration leaves none; with ``want_range_max`` as well the maximum
+    comes first, then the tensor).  ``ping_phase`` / ``want_edges``: a ping shard
     of a longer file, as ``noise_estimate`` -- with ``want_edges`` two more elements follow: edge_sum f64 (2, C, Sb),
     edge_cnt int32 (2, C, Sb), the raw (sum, count) rows of the shard's first / last ping block."""
     C, P, S = raw.shape
@@ -1664,6 +1665,8 @@ def sv_noise_fused(raw, coef, alpha2, ping_num, range_sample_num, *, cal_type="S
          _lib.CAL_SV if cal_type == "Sv" else _lib.CAL_TS, flags, int(ping_num), int(range_sample_num), int(ping_phase),
          float(noise_max), _p(sv), _p(rng), _p(noise), _p(es), _p(ec), _p(rmax), _p(rstats), _DT[dtype], _stream())
     edges = (es, ec) if want_edges else ()
+    if want_range_stats and want_range_max:  # both: the maximum (every kernel leaves it), then the statistics
+        return (sv, rng, noise, float(rmax.item()), rstats) + edges
     if want_range_stats:
         return (sv, rng, noise, rstats) + edges
     return ((sv, rng, noise, float(rmax.item())) if want_range_max else (sv, rng, noise)) + edges
