@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "fast_math.h"
+#include "ordered_key.h"
 #include "sample_math.h"
 
 namespace epa_chain {
@@ -44,37 +45,17 @@ struct Args {
   unsigned long long* rstat;  // optional, with rmax_key: {min valid echo_range as a key, number of NaN echo_range values}
   int xcd_map;  // ping blocks / time-bin groups dealt to the XCDs in contiguous eighths (epa::xcd_contiguous)
   unsigned long long* mm_keys;  // pass 2, optional [4]: min/max of Sv_noise, min/max of Sv_corrected
-  int flagged_only;  // pass 2, general kernel after the uniform-group kernel: only the groups that one left (kLeftToGeneral)
+  int flagged_only;  // pass 2, general kernel after the uniform-group kernel: only the groups that one left (LeftToGeneral)
   int uni_bins;      // pass 2, uniform-group kernel: time bins per workgroup
 };
 
-// v_max that returns the operand that is a number (IEEE maxNum), without the canonicalising copy fmax() adds
-__device__ __forceinline__ double vmax_num(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float vmax_num(float a, float b) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ double vmin_num(double a, double b) {
-  double r;
-  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-__device__ __forceinline__ float vmin_num(float a, float b) {
-  float r;
-  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-__device__ __forceinline__ unsigned long long ordered_key(double v) {
-  const unsigned long long b = __double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+using epa::kKeyNoMax;
+using epa::kKeyNoMin;
+using epa::key_value;
+using epa::lds_add;
+using epa::ordered_key;
+using epa::vmax_num;
+using epa::vmin_num;
 
 // log10 on the rare paths (column refresh, rounding residue).  Call-free by default: an out-of-line call inside
 // the ping loop makes the compiler spill the ~90 live SGPRs around it (v_readlane / v_writelane per ping).
@@ -112,11 +93,6 @@ __device__ __forceinline__ float log10_pos(float x, const double2*) { return ::l
 template <typename T>
 __device__ __noinline__ T log10_exact(T x) {
   return epa::M<T>::log10(x);
-}
-
-template <typename T>
-__device__ __forceinline__ void lds_add(T* p, T v) {
-  unsafeAtomicAdd(p, v);
 }
 
 // what both passes keep per range column across the pings of a group
@@ -263,40 +239,22 @@ template <typename U>
 __device__ __forceinline__ void wg_minmax_keys(const U (&mm_)[4], unsigned long long* keys, int lane) {
   const double mm[4] = {(double)mm_[0], (double)mm_[1], (double)mm_[2], (double)mm_[3]};
 #if !EPA_WG_KEYS  // (development knob: the round-5 form, one atomic per wavefront and key)
-  if (lane == 0) {
-    if (mm[0] <= mm[1]) {
-      atomicMin(keys + 0, ordered_key(mm[0]));
-      atomicMax(keys + 1, ordered_key(mm[1]));
-    }
-    if (mm[2] <= mm[3]) {
-      atomicMin(keys + 2, ordered_key(mm[2]));
-      atomicMax(keys + 3, ordered_key(mm[3]));
-    }
-  }
+  if (lane == 0) epa::publish_minmax_keys(mm, keys);
   return;
 #endif
   __shared__ unsigned long long wk[4];
   if (threadIdx.x == 0) {
-    wk[0] = wk[2] = ~0ull;
-    wk[1] = wk[3] = 0ull;
+    wk[0] = wk[2] = kKeyNoMin;
+    wk[1] = wk[3] = kKeyNoMax;
   }
   __syncthreads();
-  if (lane == 0) {
-    if (mm[0] <= mm[1]) {
-      atomicMin(&wk[0], ordered_key(mm[0]));
-      atomicMax(&wk[1], ordered_key(mm[1]));
-    }
-    if (mm[2] <= mm[3]) {
-      atomicMin(&wk[2], ordered_key(mm[2]));
-      atomicMax(&wk[3], ordered_key(mm[3]));
-    }
-  }
+  if (lane == 0) epa::publish_minmax_keys(mm, wk);
   __syncthreads();
   if (threadIdx.x == 0) {
-    if (wk[0] != ~0ull) atomicMin(keys + 0, wk[0]);
-    if (wk[1] != 0ull) atomicMax(keys + 1, wk[1]);
-    if (wk[2] != ~0ull) atomicMin(keys + 2, wk[2]);
-    if (wk[3] != 0ull) atomicMax(keys + 3, wk[3]);
+    if (wk[0] != kKeyNoMin) atomicMin(keys + 0, wk[0]);
+    if (wk[1] != kKeyNoMax) atomicMax(keys + 1, wk[1]);
+    if (wk[2] != kKeyNoMin) atomicMin(keys + 2, wk[2]);
+    if (wk[3] != kKeyNoMax) atomicMax(keys + 3, wk[3]);
   }
 }
 
@@ -464,8 +422,8 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
     __shared__ unsigned long long wr[2];
     __shared__ unsigned wn;
     if (threadIdx.x == 0) {
-      wr[0] = 0ull;
-      wr[1] = ~0ull;
+      wr[0] = kKeyNoMax;
+      wr[1] = kKeyNoMin;
       wn = 0u;
     }
     __syncthreads();
@@ -480,9 +438,9 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      if (wr[0] != 0ull) atomicMax(a.rmax_key, wr[0]);
+      if (wr[0] != kKeyNoMax) atomicMax(a.rmax_key, wr[0]);
       if (a.rstat) {  // the rest of {nanmin, nanmax, NaN count} of the echo_range
-        if (wr[1] != ~0ull) atomicMin(a.rstat, wr[1]);
+        if (wr[1] != kKeyNoMin) atomicMin(a.rstat, wr[1]);
         if (wn > 0u) atomicAdd(a.rstat + 1, (unsigned long long)wn);
       }
     }
@@ -534,18 +492,7 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
 // ------------------------------------------------------------------------------------------------
 // written by the uniform-group kernel into the first MVBS cell of a group it leaves to the general kernel (a NaN
 // payload no computation produces; the general kernel overwrites it)
-constexpr unsigned long long kLeftToGeneral = 0x7ff8dead0c0ffee1ull;
-constexpr unsigned kLeftToGeneral32 = 0x7fcdead1u;  // (float grids: a cell is four bytes)
-__device__ __forceinline__ bool left_to_general(const double* cell) {
-  return *reinterpret_cast<const unsigned long long*>(cell) == kLeftToGeneral;
-}
-__device__ __forceinline__ bool left_to_general(const float* cell) {
-  return *reinterpret_cast<const unsigned*>(cell) == kLeftToGeneral32;
-}
-__device__ __forceinline__ void mark_left_to_general(double* cell) {
-  *reinterpret_cast<unsigned long long*>(cell) = kLeftToGeneral;
-}
-__device__ __forceinline__ void mark_left_to_general(float* cell) { *reinterpret_cast<unsigned*>(cell) = kLeftToGeneral32; }
+using LeftToGeneral = epa::LeftMark<0x7ff8dead0c0ffee1ull, 0x7fcdead1u>;
 
 template <typename T>
 struct BinCol : ColBase<T> {
@@ -579,7 +526,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
   // blockIdx.x == n_tbins: pings that belong to no time bin still get their Sv_noise / Sv_corrected
   const bool extra = tb == a.n_tbins;
   if (extra && !(WRITE_NOISE || WRITE_CORR)) return;
-  if (a.flagged_only && !extra && !left_to_general(mvbs_out + ((size_t)c * a.n_tbins + tb) * n_rbins))
+  if (a.flagged_only && !extra && !LeftToGeneral::is_marked(mvbs_out + ((size_t)c * a.n_tbins + tb) * n_rbins))
     return;  // (uniform) the group was done by sv_denoise_mvbs_uniform_kernel
   const int nseg = extra ? 2 : 1;
   for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
@@ -809,7 +756,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_uniform_kernel
   }
   __syncthreads();
   if (differs) {
-    if ((int)threadIdx.x < nbn) mark_left_to_general(mvbs_out + cell0 + (size_t)threadIdx.x * n_rbins);
+    if ((int)threadIdx.x < nbn) LeftToGeneral::mark(mvbs_out + cell0 + (size_t)threadIdx.x * n_rbins);
     return;
   }
 
@@ -985,7 +932,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
   const int S = a.S, n_rbins = a.n_rbins;
   const size_t cell0 = ((size_t)c * a.n_tbins + tb0) * n_rbins;
   // (uniform) only the groups the uniform kernel marked; a group of two bins is marked in both or in neither
-  if (!left_to_general(mvbs_out + cell0)) return;
+  if (!LeftToGeneral::is_marked(mvbs_out + cell0)) return;
   const int pb = bin_start[tb0], pe = bin_start[tb0 + nbn], np = pe - pb;
   for (int i = threadIdx.x; i < nbn * n_rbins; i += epa::kBlock) {
     lsum[i] = (T)0;
@@ -993,8 +940,8 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
   }
   if (threadIdx.x == 0) {
     differs = np > kDriftPings ? 1 : 0;
-    rb_lo_key = ~0ull;
-    rb_hi_key = 0ull;
+    rb_lo_key = kKeyNoMin;
+    rb_hi_key = kKeyNoMax;
   }
   __syncthreads();  // (also publishes the math tables)
   const epa::CoefRow* __restrict__ rowp0 = coef + (size_t)c * a.P;
@@ -1023,10 +970,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
   }
   __syncthreads();
   if (differs) return;  // stays marked: the general kernel takes it
-  auto unkey = [](unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-  };
-  const double rb_lo = unkey(rb_lo_key), rb_hi = unkey(rb_hi_key);
+  const double rb_lo = key_value(rb_lo_key), rb_hi = key_value(rb_hi_key);
 
   const T nspread = (T)a.nspread, snr = (T)a.snr;
   const double bin = a.range_bin, inv_bin = a.inv_range_bin;

@@ -45,6 +45,7 @@
 
 #include "fast_math.h"
 #include "lds_fft.h"
+#include "ordered_key.h"
 
 namespace {
 
@@ -301,17 +302,8 @@ __device__ __forceinline__ C2<F> sum_plain(const RawSample<InT, NB>& raw) {
   }
   return C2<F>{fr, fi};
 }
-// v_min_f64 / v_max_f64 as the hardware has them (clang's fmin / fmax first canonicalise both operands)
-__device__ __forceinline__ double vmax_num(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ double vmin_num(double a, double b) {
-  double r;
-  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
+using epa::vmax_num;  // v_min_f64 / v_max_f64 as the hardware has them
+using epa::vmin_num;
 
 __device__ __forceinline__ double sub_rn(double a, double b) {
   asm volatile("" : "+v"(a));

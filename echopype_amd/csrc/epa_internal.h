@@ -90,6 +90,9 @@ inline int check_launch(const char* what) {
 constexpr int kBlock = 256;  // 4 wavefronts of 64
 constexpr int kMinmaxMaxGrid = 1024;  // the most workgroups (= partials in its workspace) of an epa_nanminmax launch
 
+// may the 16-byte accesses of a vectorised kernel be used on this buffer?  (an optional buffer that is not given: yes)
+inline bool al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 // ---- device math, templated on the compute type ------------------------------------------------
 template <typename T>
 struct M;
@@ -221,3 +224,35 @@ int epa_rows_piece_launch(const float* mask_raw, const void* x, const double* co
                           double* stats_out, hipStream_t st);
 // reduce_util.hip: {min, max, NaN count} partials (3 doubles per workgroup) -> out[3]
 int epa_minmax_final(const double* part, int nparts, double* out, hipStream_t st);
+// block_reduce.hip: the {min, max, min, max} keys (ordered_key.h) of Sv_noise / Sv_corrected, four words: set to "nothing
+// seen" before the pass that lowers and raises them (init_minmax_kernel), and turned into doubles in place after it, NaN
+// where a key was never touched (decode_minmax_kernel)
+int epa_minmax_keys_init(unsigned long long* keys, hipStream_t st);
+int epa_minmax_keys_decode(double* keys, hipStream_t st);
+
+// The fast paths that block_reduce.hip's planner hands the hot configurations to.
+// fused_sv_mvbs.hip: raw power (float, or int16 with the recorded lengths) -> Sv + MVBS in one pass
+int epa_fused_fast_path(const void* raw, int raw_is_i16, const int32_t* n_valid, const double* coef,
+                        int C, int P, int S, double nspread,
+                        unsigned cal_flags, const int32_t* bin_start, int n_tbins, double range_bin,
+                        int n_rbins, unsigned bin_flags, double fill_value, void* sv_out,
+                        void* mvbs_out, void* sum_out, uint32_t* cnt_out, int dtype,
+                        size_t lds_bytes, unsigned cnt_off, unsigned long long* rmax_key,
+                        unsigned long long* rstat, const double* dscale, const double* doffset, void* depth_out,
+                        hipStream_t st);
+// fused_sv_mvbs.hip: Sv with the echo_range from the coefficient rows -> MVBS
+int epa_mvbs_rows_fast_path(const void* sv, const double* coef, int C, int P, int S, const int32_t* bin_start,
+                            int n_tbins, double range_bin, int n_rbins, int as_stored, double fill_value,
+                            void* mvbs_out, void* sum_out, uint32_t* cnt_out, int dtype, size_t lds_bytes,
+                            unsigned cnt_off, hipStream_t st);
+// chain_fast.hip: raw power -> Sv + the noise estimate
+int epa_chain_fast_pass1(const float* raw, const double* coef, const double* alpha2, int C, int P, int S,
+                         double nspread, int ping_num, int rsn, int ping_phase, double noise_max, void* sv_out,
+                         double* noise_out, double* edge_sum_out, uint32_t* edge_cnt_out,
+                         unsigned long long* rmax_key, unsigned long long* rstat, int dtype, hipStream_t st);
+// chain_fast.hip: raw power + noise -> Sv_noise / Sv_corrected + MVBS of Sv_corrected
+int epa_chain_fast_pass2(const float* raw, const double* coef, const double* alpha2, const double* noise, int C,
+                         int P, int S, double nspread, int ping_num, int ping_phase, double snr,
+                         const int32_t* bin_start, int n_tbins, double range_bin, int n_rbins, double fill_value,
+                         void* noise_out, void* corr_out, void* mvbs_out, void* sum_out, uint32_t* cnt_out, int dtype,
+                         size_t lds_acc_bytes, unsigned cnt_off, unsigned long long* mm_keys, hipStream_t st);

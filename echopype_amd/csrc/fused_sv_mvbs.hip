@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "fast_math.h"
+#include "ordered_key.h"
 #include "sample_math.h"
 
 namespace epa_fused {
@@ -31,7 +32,7 @@ struct Args {
   unsigned long long* rmax_key;  // optional: max valid echo_range as an order-preserving u64 key
   unsigned long long* rstat;     // optional, with rmax_key: {min valid echo_range as a key, number of NaN echo_range values}
   int xcd_map;  // time bins dealt to the XCDs in contiguous eighths (epa::xcd_contiguous)
-  int flagged_only;  // mvbs_of_sv_rows_kernel after the fixed-bin kernel: only the time bins that one left (kLeftToRows)
+  int flagged_only;  // mvbs_of_sv_rows_kernel after the fixed-bin kernel: only the time bins that one left (LeftToRows)
   // binned on ``depth`` instead of the echo_range (consolidate/api.py:221 between compute_Sv and compute_MVBS):
   // depth[c,p,s] = doffset[c,p] + dscale[c,p] * echo_range[c,p,s], [C*P] doubles each; NULL: binned on the echo_range
   const double* dscale;
@@ -39,20 +40,17 @@ struct Args {
   void* depth_out;  // optional [C*P*S] of T: the depth array written by the same pass (NaN where the raw sample is)
 };
 
-// order-preserving map double -> u64 (so that atomicMax on the key is a max on the double)
-__device__ __forceinline__ unsigned long long ordered_key(double v) {
-  const unsigned long long b = __double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+using epa::kKeyNoMax;
+using epa::kKeyNoMin;
+using epa::key_value;
+using epa::lds_add;
+using epa::ordered_key;
+using epa::vmax_num;
+using epa::vmin_num;
 
 template <typename T>
 __device__ __noinline__ T log10_slow(T x) {
   return epa::M<T>::log10(x);
-}
-
-template <typename T>
-__device__ __forceinline__ void lds_add(T* p, T v) {
-  unsafeAtomicAdd(p, v);
 }
 
 // Lane-private state of one range column (kept across the pings of a time bin).
@@ -109,23 +107,6 @@ __device__ __forceinline__ double lin_bins(double u, const double* __restrict__ 
   return ldexp(p * tab[mi & 255], mi >> 8);
 }
 __device__ __forceinline__ float lin_bins(float u, const double*) { return ::exp10f(u * 0.1f); }
-
-// v_max that returns the operand that is a number (IEEE maxNum), without the canonicalising copy fmax() adds
-__device__ __forceinline__ double vmax_num(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float vmax_num(float a, float b) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ double vmin_num(double a, double b) {
-  double r;
-  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
 
 // One sample: echo_range, R', Sv, linear value, bin membership, private accumulation.
 // Compile-time flags of the hot instantiation = the EK default (R' <= 0 guard, range masked by NaN
@@ -362,8 +343,8 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
   __shared__ unsigned long long wg_keys[2];  // RMAX: the workgroup's {max key, min key} and NaN count (see the end)
   __shared__ unsigned wg_nnan;
   if (RMAX && threadIdx.x == 0) {
-    wg_keys[0] = 0ull;
-    wg_keys[1] = ~0ull;
+    wg_keys[0] = kKeyNoMax;
+    wg_keys[1] = kKeyNoMin;
     wg_nnan = 0u;
   }
 
@@ -531,9 +512,9 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
     __syncthreads();
     if (threadIdx.x == 0) {
       const unsigned long long kmax = wg_keys[0], kmin = wg_keys[1];
-      if (kmax != 0ull) atomicMax(a.rmax_key, kmax);  // (key 0 = nothing seen)
+      if (kmax != kKeyNoMax) atomicMax(a.rmax_key, kmax);
       if (a.rstat) {  // the rest of {nanmin, nanmax, NaN count}: what compute_MVBS asks of its range variable
-        if (kmin != ~0ull) atomicMin(a.rstat, kmin);  // (key ~0 = nothing seen)
+        if (kmin != kKeyNoMin) atomicMin(a.rstat, kmin);
         if (wg_nnan > 0u) atomicAdd(a.rstat + 1, (unsigned long long)wg_nnan);
       }
     }
@@ -677,26 +658,7 @@ __device__ __forceinline__ void bin_sv_sample(SvColumn<T>& c, T sv, const epa::C
 // lanes spread over the pings.  A time bin whose pings differ in ra or r0, or longer than kFixedPings, is marked in its
 // first MVBS cell (a NaN payload no computation produces) and left to mvbs_of_sv_rows_kernel, launched right after.
 constexpr int kFixedPings = 512;
-template <typename T>
-struct LeftMark;
-template <>
-struct LeftMark<double> {
-  static constexpr unsigned long long kBits = 0x7ff8dead0c0ffee2ull;
-};
-template <>
-struct LeftMark<float> {
-  static constexpr unsigned kBits = 0x7fcdead2u;
-};
-__device__ __forceinline__ bool left_to_rows(const double* cell) {
-  return *reinterpret_cast<const unsigned long long*>(cell) == LeftMark<double>::kBits;
-}
-__device__ __forceinline__ bool left_to_rows(const float* cell) {
-  return *reinterpret_cast<const unsigned*>(cell) == LeftMark<float>::kBits;
-}
-__device__ __forceinline__ void mark_left(double* cell) {
-  *reinterpret_cast<unsigned long long*>(cell) = LeftMark<double>::kBits;
-}
-__device__ __forceinline__ void mark_left(float* cell) { *reinterpret_cast<unsigned*>(cell) = LeftMark<float>::kBits; }
+using LeftToRows = epa::LeftMark<0x7ff8dead0c0ffee2ull, 0x7fcdead2u>;
 
 // (wavefronts per SIMD: measured at 4 x 500 000 x 2000 -- fp64 6.30 ms at 8 (64 VGPRs, six dwords of scratch), 5.80 at 6,
 //  the per-sample form 6.01; fp32 3.08 at 8, 3.17 at 6, the per-sample form 3.39)
@@ -722,8 +684,8 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 6 : 8) void mvbs_of_s
   }
   if (threadIdx.x == 0) {
     differs = np > kFixedPings ? 1 : 0;
-    rb_lo_key = ~0ull;
-    rb_hi_key = 0ull;
+    rb_lo_key = kKeyNoMin;
+    rb_hi_key = kKeyNoMax;
   }
   __syncthreads();
   const epa::CoefRow* __restrict__ rowp0 = coef + (size_t)c * a.P;
@@ -736,13 +698,10 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 6 : 8) void mvbs_of_s
   }
   __syncthreads();
   if (differs) {
-    if (threadIdx.x == 0) mark_left(mvbs_out + cell0);
+    if (threadIdx.x == 0) LeftToRows::mark(mvbs_out + cell0);
     return;
   }
-  auto unkey = [](unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-  };
-  const double rb_lo = unkey(rb_lo_key), rb_hi = unkey(rb_hi_key);
+  const double rb_lo = key_value(rb_lo_key), rb_hi = key_value(rb_hi_key);
   const double bin = a.range_bin, inv_bin = a.inv_range_bin;
   const T* __restrict__ sv_c = sv + (size_t)c * a.P * S;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -857,7 +816,7 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES) void mvbs_of_sv_r
   const double* tab = mt.exp2_tab;
   const int c = blockIdx.y, tb = a.xcd_map ? epa::xcd_contiguous(blockIdx.x, a.n_tbins) : (int)blockIdx.x;
   const int S = a.S, n_rbins = a.n_rbins;
-  if (a.flagged_only && !left_to_rows(mvbs_out + ((size_t)c * a.n_tbins + tb) * n_rbins)) return;  // (uniform)
+  if (a.flagged_only && !LeftToRows::is_marked(mvbs_out + ((size_t)c * a.n_tbins + tb) * n_rbins)) return;  // (uniform)
   for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
     lsum[i] = (T)0;
     lcnt[i] = 0u;

@@ -8,6 +8,7 @@
 //   Sv_corr   = NaN unless Sv_corr - Sv_noise > SNR_threshold
 // HBM-bound: reads Sv (+ echo_range unless affine), writes Sv_noise and Sv_corrected.
 #include "fast_math.h"
+#include "ordered_key.h"
 #include "sample_math.h"
 
 namespace {
@@ -76,41 +77,8 @@ __global__ __launch_bounds__(epa::kBlock) void noise_apply_kernel(
       if (sv_corr) epa::store_vec<T, LEN>(sv_corr + off, oc);
     }
   }
-  if (mm_keys) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mm[0] = fmin(mm[0], __shfl_down(mm[0], o, 64));
-      mm[1] = fmax(mm[1], __shfl_down(mm[1], o, 64));
-      mm[2] = fmin(mm[2], __shfl_down(mm[2], o, 64));
-      mm[3] = fmax(mm[3], __shfl_down(mm[3], o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-      auto key = [](double v) {
-        const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-        return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-      };
-      if (mm[0] <= mm[1]) {
-        atomicMin(mm_keys + 0, key(mm[0]));
-        atomicMax(mm_keys + 1, key(mm[1]));
-      }
-      if (mm[2] <= mm[3]) {
-        atomicMin(mm_keys + 2, key(mm[2]));
-        atomicMax(mm_keys + 3, key(mm[3]));
-      }
-    }
-  }
+  epa::wave_publish_minmax_keys(mm, mm_keys);
 }
-
-__global__ void init_minmax_kernel(unsigned long long* p) { p[threadIdx.x] = (threadIdx.x & 1) ? 0ull : ~0ull; }
-__global__ void decode_minmax_kernel(double* p) {
-  const int i = threadIdx.x;
-  const unsigned long long k = reinterpret_cast<unsigned long long*>(p)[i];
-  const bool none = (i & 1) ? k == 0ull : k == ~0ull;
-  const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  p[i] = none ? __builtin_nan("") : __longlong_as_double(b);
-}
-
-inline bool al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <typename T>
 int launch(const void* sv, const void* range, const double* coef, const float* mask_raw, const double* alpha2,
@@ -118,7 +86,8 @@ int launch(const void* sv, const void* range, const double* coef, const float* m
            void* sv_corr, double* minmax_out, hipStream_t st) {
   const long long rows = (long long)C * P;
   const int need = sizeof(T) == 8 ? 2 : 4;
-  const bool vec = S % need == 0 && al16(sv) && al16(range) && al16(sv_noise) && al16(sv_corr) && al16(mask_raw);
+  const bool vec = S % need == 0 && epa::al16(sv) && epa::al16(range) && epa::al16(sv_noise) && epa::al16(sv_corr) &&
+                   epa::al16(mask_raw);
   const int chunk = vec ? 1024 : epa::kBlock;
   const int chunks_per_row = (S + chunk - 1) / chunk;
   long long gx = 8192 / chunks_per_row;
@@ -128,7 +97,9 @@ int launch(const void* sv, const void* range, const double* coef, const float* m
   const int n_pblocks = (P + ping_phase + ping_num - 1) / ping_num;
   const epa::CoefRow* cf = reinterpret_cast<const epa::CoefRow*>(coef);
   unsigned long long* mm = reinterpret_cast<unsigned long long*>(minmax_out);
-  if (mm) hipLaunchKernelGGL(init_minmax_kernel, dim3(1), dim3(4), 0, st, mm);
+  if (mm) {
+    if (int rc = epa_minmax_keys_init(mm, st)) return rc;
+  }
   if (vec)
     hipLaunchKernelGGL((noise_apply_kernel<T, true>), grid, dim3(epa::kBlock), 0, st, (const T*)sv,
                        (const T*)range, cf, mask_raw, alpha2, noise, P, S, rows, ping_num, ping_phase, n_pblocks, (T)snr,
@@ -138,11 +109,7 @@ int launch(const void* sv, const void* range, const double* coef, const float* m
                        (const T*)range, cf, mask_raw, alpha2, noise, P, S, rows, ping_num, ping_phase, n_pblocks, (T)snr,
                        (T*)sv_noise, (T*)sv_corr, mm);
   if (int rc = epa::check_launch("noise_apply_kernel")) return rc;
-  if (mm) {
-    hipLaunchKernelGGL(decode_minmax_kernel, dim3(1), dim3(4), 0, st, minmax_out);
-    return epa::check_launch("decode_minmax_kernel");
-  }
-  return EPA_OK;
+  return mm ? epa_minmax_keys_decode(minmax_out, st) : EPA_OK;
 }
 
 }  // namespace

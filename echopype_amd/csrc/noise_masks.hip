@@ -17,7 +17,7 @@
 namespace {
 
 using epa::kBlock;
-using namespace epa::sel;  // reflect_index, block_sum / block_min, sort_key, Window, SelectScratch, window_median_lin
+using namespace epa::sel;  // reflect_index, block_sum / block_min, ordered_key / key_value, Window, SelectScratch, window_median_lin
 
 // lexicographic (value, index) minimum -- np.argmin's "first occurrence of the minimum"
 __device__ __forceinline__ int block_argmin(double v, int idx, double* shv, int* shi) {
@@ -796,7 +796,7 @@ __global__ __launch_bounds__(kBlock) void attenuated_prepare_kernel(const T* __r
             if (j < nj && (code[j] == c1 || code[j] == c2)) {
               const unsigned at = atomicAdd(&ncand[wv], 1u);
               if (at < 64u) {
-                cand[wv][at] = sort_key((double)layer[lane + 64 * j]);
+                cand[wv][at] = ordered_key((double)layer[lane + 64 * j]);
                 ctag[wv][at] = code[j];
               }
             }
@@ -2555,7 +2555,7 @@ __global__ __launch_bounds__(kBlock) void pool_median_slide_kernel(MedSlideArgs<
       if (state == 1u && pooled_at(pp)) {
         const int M = __builtin_amdgcn_readfirstlane((int)ncand[z]);  // <= kMedSel
         unsigned long long ki = ~0ull;
-        if (lane < M) ki = sort_key((double)element((int)cidx[z * kMedSel + lane], pp, rs));
+        if (lane < M) ki = ordered_key((double)element((int)cidx[z * kMedSel + lane], pp, rs));
         unsigned rank = 0u;
         for (int j = 0; j < M; ++j) {
           const unsigned long long kj = wave_bcast64(ki, j);
@@ -2899,7 +2899,7 @@ __global__ __launch_bounds__(kBlock, 2) void attenuated_walk_kernel(const T* __r
     bool flag = false;
     if (M && ping_db == ping_db) {
       unsigned long long ki = ~0ull;
-      if (lane < M) ki = sort_key((double)element((int)cidx[z * kMedSel + lane], f_lo, f_rs));
+      if (lane < M) ki = ordered_key((double)element((int)cidx[z * kMedSel + lane], f_lo, f_rs));
       unsigned rank = 0u;
       for (int j = 0; j < M; ++j) {
         const unsigned long long kj = wave_bcast64(ki, j);

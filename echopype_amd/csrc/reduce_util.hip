@@ -340,7 +340,7 @@ int epa_rows_piece_launch(const float* mask_raw, const void* x, const double* co
                           const double* offset, long long rows, int S, void* out, int dtype, double* workspace,
                           double* stats_out, hipStream_t st) {
   const int need = dtype == EPA_F64 ? 2 : 4;
-  auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
+  using epa::al16;
   static const bool off = [] { const char* e = getenv("EPA_ROW_PIECES"); return e && e[0] == '0'; }();  // development knob
   const int chunks = (S + 1023) / 1024;
   const long long pieces = rows * chunks;

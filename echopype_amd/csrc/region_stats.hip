@@ -19,6 +19,7 @@
 // cannot.  No workgroup waits for another.
 #include "epa_internal.h"
 #include "fast_math.h"
+#include "ordered_key.h"
 #include "union_find.h"
 
 namespace {
@@ -29,11 +30,9 @@ constexpr int kWaves = epa::kBlock / 64;
 constexpr int kPings = 32;       // pings walked by one wave
 constexpr int kMaxBlocks = 4096;  // workgroups of the sweep (each builds the 10^x table once, then strides over the tiles)
 
-// order-preserving map double -> u64 (atomicMax on the key is a max on the double; no number has the key 0)
-__device__ __forceinline__ unsigned long long ordered_key(double v) {
-  const unsigned long long b = __double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+// the extrema are maxima of ordered keys in tables the caller zeroed: no number has the key 0 (epa::kKeyNoMax)
+using epa::ordered_key;
+static_assert(epa::kKeyNoMax == 0ull, "a zeroed table holds 'nothing seen'");
 
 // what a lane has gathered for the code it sits on
 struct Acc {

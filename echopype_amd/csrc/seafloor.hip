@@ -29,6 +29,7 @@
 // another: nothing relies on all of them being resident.  Each retry loop has a bound (the pixel count: a correct run cannot reach it); a loop that
 // reaches it counts into an error word the host turns into an exception.
 #include "epa_internal.h"
+#include "ordered_key.h"
 #include "union_find.h"
 
 namespace {
@@ -199,28 +200,15 @@ template <>
 struct Key<float> {
   using U = unsigned int;
   static constexpr int kBits = 32;
-  static __device__ __forceinline__ U of(float x) {
-    const U u = __float_as_uint(x);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-  }
-  static __device__ __forceinline__ double value(unsigned long long k) {
-    const U key = (U)k;
-    const U u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-    return (double)__uint_as_float(u);
-  }
+  static __device__ __forceinline__ U of(float x) { return epa::ordered_key(x); }
+  static __device__ __forceinline__ double value(unsigned long long k) { return (double)epa::key_value((U)k); }
 };
 template <>
 struct Key<double> {
   using U = unsigned long long;
   static constexpr int kBits = 64;
-  static __device__ __forceinline__ U of(double x) {
-    const U u = (U)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-  }
-  static __device__ __forceinline__ double value(unsigned long long key) {
-    const U u = (key & 0x8000000000000000ull) ? (key & 0x7fffffffffffffffull) : ~key;
-    return __longlong_as_double((long long)u);
-  }
+  static __device__ __forceinline__ U of(double x) { return epa::ordered_key(x); }
+  static __device__ __forceinline__ double value(unsigned long long key) { return epa::key_value(key); }
 };
 
 template <typename T>

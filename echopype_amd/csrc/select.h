@@ -11,6 +11,7 @@
 // All functions here are called by every thread of a 256-thread workgroup.
 #pragma once
 #include "fast_math.h"
+#include "ordered_key.h"
 
 namespace epa {
 namespace sel {
@@ -50,14 +51,9 @@ __device__ __forceinline__ unsigned long long block_min(unsigned long long v, un
   return r;
 }
 
-// order-preserving map of the doubles onto the unsigned 64-bit integers, and back
-__device__ __forceinline__ unsigned long long sort_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-}
+// the selection runs on the order-preserving keys of the values (ordered_key.h)
+using epa::key_value;
+using epa::ordered_key;
 
 template <typename T>
 struct Window {
@@ -189,7 +185,7 @@ __device__ bool window_select(const W& w, SC* sc, Rank rank, unsigned& n_valid, 
   constexpr int kCandCap = SC::kCap;  // (shadows the default capacity)
   auto each_global = [&](auto f) {
     w.for_each([&](double v) {
-      if (v == v) f(sort_key(v));
+      if (v == v) f(ordered_key(v));
     });
   };
   unsigned long long prefix = 0ull;

@@ -11,6 +11,7 @@
 // echo_range); MFMA is irrelevant here (no contraction).
 #include "fast_math.h"
 #include "log_tab_data.h"
+#include "ordered_key.h"
 #include "sample_math.h"
 
 namespace {
@@ -99,13 +100,12 @@ __global__ __launch_bounds__(epa::kBlock) void sv_power_kernel(const float* __re
 // Same arithmetic otherwise (cal_power_sample); the logarithm is fast_log10_lean's (4e-16) instead of ocml's: Sv moves by
 // less than 1e-14 dB against the kernel above.  {min, max, NaN count} of the echo_range go to three ordered keys with
 // atomics a wavefront issues only when its value would change the key (almost never after the first workgroups).
-__device__ __forceinline__ unsigned long long ordered_key(double v) {
-  const unsigned long long b = __double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+using epa::kKeyNoMax;
+using epa::kKeyNoMin;
+using epa::key_value;
+using epa::ordered_key;
 
 constexpr int kStatSlots = 4096;  // {max key, min key, NaN count} per slot; a wavefront uses slot (row mod kStatSlots)
-constexpr unsigned long long kDKeyNone = ~0ull;
 
 // n log10(s - d) of a sample: from the channel's table when every row of the channel has the same d (EK files: d is the
 // TVG correction in samples, a constant of the channel), else evaluated here.
@@ -117,7 +117,8 @@ __device__ __forceinline__ T piece_nlog(double sd, T nspread) {
 }
 
 // {min, max} of the rows' d per channel as ordered keys (a NaN d, or rows that differ in ra -- the table would not depend
-// on it, but a channel whose sample interval changes is not the plain case -- poison the channel: keys {0, ~0})
+// on it, but a channel whose sample interval changes is not the plain case -- poison the channel: the minimum's key
+// below and the maximum's above the key of every number, so that the two can no longer meet)
 __global__ __launch_bounds__(epa::kBlock) void d_span_kernel(const epa::CoefRow* __restrict__ coef, int P,
                                                              unsigned long long* __restrict__ dkeys) {
   const int c = blockIdx.y;
@@ -137,8 +138,8 @@ __global__ __launch_bounds__(epa::kBlock) void d_span_kernel(const epa::CoefRow*
   const bool any_bad = __ballot(bad) != 0ull;
   if ((threadIdx.x & 63) == 0) {
     if (any_bad) {
-      atomicMin(dkeys + 2 * c, 0ull);
-      atomicMax(dkeys + 2 * c + 1, kDKeyNone);
+      atomicMin(dkeys + 2 * c, kKeyNoMax);
+      atomicMax(dkeys + 2 * c + 1, kKeyNoMin);
     } else if (lo <= hi) {
       atomicMin(dkeys + 2 * c, ordered_key(lo));
       atomicMax(dkeys + 2 * c + 1, ordered_key(hi));
@@ -147,8 +148,8 @@ __global__ __launch_bounds__(epa::kBlock) void d_span_kernel(const epa::CoefRow*
 }
 __global__ void d_keys_init_kernel(unsigned long long* dkeys, int C) {
   for (int i = threadIdx.x; i < C; i += blockDim.x) {
-    dkeys[2 * i] = kDKeyNone;
-    dkeys[2 * i + 1] = 0ull;
+    dkeys[2 * i] = kKeyNoMin;
+    dkeys[2 * i + 1] = kKeyNoMax;
   }
 }
 // table[c][s] = nspread * log10(s - d_c), the value ColumnLog::update caches (same out-of-line ocml log10: the same bits)
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(epa::kBlock) void nl_table_kernel(const unsigned lo
   const int c = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long klo = dkeys[2 * c], khi = dkeys[2 * c + 1];
   if (klo != khi || s >= S) return;  // (not one d for the channel: the table is not used)
-  const double d = __longlong_as_double((long long)((klo >> 63) ? (klo & 0x7fffffffffffffffull) : ~klo));
+  const double d = key_value(klo);
   table[(size_t)c * S + s] = nspread * epa::log10_noinline<T>((T)((double)s - d));
 }
 
@@ -279,14 +280,14 @@ __global__ __launch_bounds__(epa::kBlock) void sv_power_piece_kernel(const float
 
 __global__ __launch_bounds__(epa::kBlock) void piece_keys_init_kernel(unsigned long long* keys) {
   for (int i = threadIdx.x; i < kStatSlots; i += blockDim.x) {
-    keys[3 * i + 0] = 0ull;   // max key: nothing seen
-    keys[3 * i + 1] = ~0ull;  // min key: nothing seen
-    keys[3 * i + 2] = 0ull;   // NaN count
+    keys[3 * i + 0] = kKeyNoMax;
+    keys[3 * i + 1] = kKeyNoMin;
+    keys[3 * i + 2] = 0ull;  // NaN count
   }
 }
 __global__ __launch_bounds__(epa::kBlock) void piece_keys_decode_kernel(const unsigned long long* keys, double* stats) {
   __shared__ unsigned long long smax[4], smin[4], scnt[4];
-  unsigned long long mx = 0ull, mn = ~0ull, cnt = 0ull;
+  unsigned long long mx = kKeyNoMax, mn = kKeyNoMin, cnt = 0ull;
   for (int i = threadIdx.x; i < kStatSlots; i += blockDim.x) {
     mx = keys[3 * i] > mx ? keys[3 * i] : mx;
     mn = keys[3 * i + 1] < mn ? keys[3 * i + 1] : mn;
@@ -304,11 +305,8 @@ __global__ __launch_bounds__(epa::kBlock) void piece_keys_decode_kernel(const un
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w) { mx = smax[w] > mx ? smax[w] : mx; mn = smin[w] < mn ? smin[w] : mn; }
     cnt = scnt[0] + scnt[1] + scnt[2] + scnt[3];
-    auto unkey = [](unsigned long long k) {
-      return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-    };
-    stats[0] = mn == ~0ull ? __builtin_nan("") : unkey(mn);
-    stats[1] = mx == 0ull ? __builtin_nan("") : unkey(mx);
+    stats[0] = mn == kKeyNoMin ? __builtin_nan("") : key_value(mn);
+    stats[1] = mx == kKeyNoMax ? __builtin_nan("") : key_value(mx);
     stats[2] = (double)cnt;
   }
 }
@@ -335,7 +333,7 @@ __global__ __launch_bounds__(epa::kBlock) void sv_power_scalar_kernel(
 }
 
 // ---- the host-side plan of K1, shared by the launch, the size of its workspace and epa_sv_power_vectorized ------------
-inline bool al16(const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+using epa::al16;
 // the 16-byte path: S a whole number of 16-byte output accesses, every buffer given 16-byte aligned
 inline bool k1_vectorized(int S, size_t out_esz, const void* raw, const void* out, const void* range_out) {
   const int need = out_esz == 8 ? 2 : 4;  // samples per 16-B output access

@@ -1004,7 +1004,8 @@ def region_stats(code, n, state, sv=None, range=None):
 
 
 def _unkey(k):
-    """The float64 values of order-preserving u64 keys (``epa_region_word``); key 0 (nothing seen) -> NaN."""
+    """The float64 values of order-preserving u64 keys (``epa_region_word``); key 0 (nothing seen) -> NaN.  The host
+    mirror of ``epa::key_value`` and ``epa::kKeyNoMax``: csrc/ordered_key.h is the definition and states the contract."""
     k = np.ascontiguousarray(k).view(np.uint64)
     top = np.uint64(1) << np.uint64(63)
     bits = np.where(k & top, k & ~top, ~k)

@@ -840,6 +840,69 @@ def _chain_equivalence(env, dtype, closed, P, pn, bin_s, ss_every, S=1000, gap_a
         _assert_close(res["MVBS"].cpu().numpy(), exp_m, 1e-9, "oracle MVBS")
 
 
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("snr", [3.0, 1e6])
+@pytest.mark.parametrize("S", [6, 8])
+def test_min_max_keys_of_the_denoising_passes_on_every_route(env, S, snr, dtype):
+    """The [min, max of Sv_noise, min, max of Sv_corrected] by-product (ordered keys, csrc/ordered_key.h) of pass 2 from
+    the raw samples -- S = 6: the generic block_reduce_kernel, S = 8: the specialised kernels of chain_fast.hip -- and of
+    epa_noise_apply / epa_noise_apply_rows, each set up by init_minmax_kernel and decoded by decode_minmax_kernel.  A
+    minimum or maximum is one of the values the kernel stored (fmin / fmax / v_min / v_max pick an operand, float ->
+    double is exact), so it EQUALS NumPy's nanmin / nanmax of the arrays the same call wrote; one channel is all NaN, and
+    with an SNR threshold nothing passes Sv_corrected is all NaN: its two keys stay untouched and decode to NaN.  The
+    arrays themselves are held to the separate kernels at the tolerances of the chain tests above."""
+    from echopype_amd import _lib
+    torch, ops, synth = env
+    C, P, pn = 2, 14, 4
+    d = synth.ek60_numpy(C, P, S, ss_every=1)  # a new sound speed with every ping: coefficient rows differ inside a bin
+    d["backscatter_r"][1] = np.nan
+    dt = getattr(torch, dtype)
+    g = lambda k: _dev(torch, d[k], torch.float64)  # noqa: E731
+    coef = ops.power_coef_ek(g("sample_interval"), g("transmit_duration_nominal"), g("transmit_power"),
+                             g("sound_speed_indicative"), g("absorption_indicative"), g("gain_correction"),
+                             g("sa_correction"), g("equivalent_beam_angle"), g("frequency_nominal"),
+                             _dev(torch, d["transmit_duration_nominal"][:, 0].copy(), torch.float64),
+                             pulse_length=g("pulse_length"), gain_is_table=True, sa_is_table=True)
+    raw = _dev(torch, d["backscatter_r"])
+    a2 = _dev(torch, np.broadcast_to(2 * d["absorption_indicative"], (C, P)).copy(), torch.float64)
+    noise = _dev(torch, np.full((C, (P + pn - 1) // pn), -140.0))
+    ns = d["ping_time"].astype("datetime64[ns]").astype(np.int64)
+    dt_ns = 7 * 1_000_000_000  # bins of at most 8 pings stay whole (make_plan): what the single-stage kernels serve
+    n_t = int((ns[-1] - ns[0]) // dt_ns) + 1
+    bs = ops.time_bin_offsets(_dev(torch, ns), int(ns[0]), dt_ns, n_t)
+    sv0, rg0 = ops.sv_power(raw, coef, dtype=dt)
+    n_r = int(np.nanmax(rg0.cpu().numpy())) + 1
+
+    def own_extrema(sn, sc):
+        out = []
+        for a in (sn.cpu().numpy().astype(np.float64), sc.cpu().numpy().astype(np.float64)):
+            out += [np.nanmin(a), np.nanmax(a)] if not np.isnan(a).all() else [np.nan, np.nan]
+        return out
+
+    def check(what, tr, kernel, sn, sc, mm):
+        assert kernel(tr.kernels) and "init_minmax_kernel" in tr.kernels and "decode_minmax_kernel" in tr.kernels, \
+            (what, tr.kernels)
+        np.testing.assert_array_equal(np.asarray(mm), np.asarray(own_extrema(sn, sc)), err_msg=what)
+        assert np.isfinite(mm[:2]).all() and np.isfinite(mm[2:]).all() == (snr == 3.0), (what, mm)
+
+    with _lib.launch_trace() as tr:
+        sn0, sc0, mm0 = ops.noise_apply(sv0, a2, noise, pn, snr, range=rg0, want_minmax=True)
+    check("noise_apply on the echo_range array", tr, lambda ks: "noise_apply_kernel" in ks, sn0, sc0, mm0)
+    with _lib.launch_trace() as tr:
+        sn1, sc1, mm1 = ops.noise_apply(sv0, a2, noise, pn, snr, coef=coef, mask_raw=raw, want_minmax=True)
+    check("noise_apply on the coefficient rows", tr, lambda ks: "noise_apply_kernel" in ks, sn1, sc1, mm1)
+    with _lib.launch_trace() as tr:
+        res = ops.sv_denoise_mvbs(raw, coef, a2, noise, pn, snr, bs, n_t, 1.0, n_r, dtype=dt, want_noise=True,
+                                  want_minmax=True)
+    served = (lambda ks: "block_reduce_kernel" in ks) if S == 6 else \
+        (lambda ks: "block_reduce_kernel" not in ks and any(k.startswith("sv_denoise_mvbs_") for k in ks))
+    check(f"pass 2 from the raw samples, S = {S}", tr, served, res["Sv_noise"], res["Sv_corrected"], res["minmax"])
+    _assert_close(res["Sv_noise"].cpu().numpy(), sn0.cpu().numpy(), 1e-11 if dtype == "float64" else 2e-4, "Sv_noise")
+    _assert_close(res["Sv_corrected"].cpu().numpy(), sc0.cpu().numpy(), RTOL[dtype], "Sv_corrected")
+    m0 = ops.mvbs(sc0, bs, n_t, 1.0, n_r, coef=coef)["MVBS"]
+    _assert_close(res["MVBS"].cpu().numpy(), m0.cpu().numpy(), RTOL[dtype], "MVBS of Sv_corrected")
+
+
 # ---- EK80 complex kernels against the reference's own _cal_complex_samples outputs ---------------------
 @pytest.mark.parametrize("tag,wf,planes", [("ek80bb", "BB", "float64"), ("ek80cw", "CW", "float64"),
                                            ("ek80bbseam", "BB", "float32"), ("ek80bbseam", "BB", "float64")])
