@@ -11,7 +11,7 @@ loudly if it has not been built (``python echopype_amd/build.py``).
 # initialises; streams that share a queue run one after the other.  The package leaves that number to the runtime and the
 # user: ``pipeline`` keeps only side streams it has seen running side by side (``pipeline._runs_beside``).
 from . import _lib  # noqa: F401,E402  (loads the HIP library; raises if missing)
-from . import calibrate, clean, commongrid, consolidate, convert, mask, metrics, ops, pipeline, qc, synth, utils  # noqa: F401,E402
+from . import calibrate, clean, commongrid, consolidate, convert, mask, metrics, ops, pipeline, qc, synth, targets, utils  # noqa: F401,E402
 from .combine import combine_echodata  # noqa: F401,E402
 from .convert import open_raw  # noqa: F401,E402
 from .echodata import EchoData  # noqa: F401,E402
@@ -21,4 +21,4 @@ from .xr_lite import DataArray, Dataset, DeviceArray  # noqa: F401,E402
 __version__ = "0.1.0"
 __all__ = ["calibrate", "clean", "commongrid", "consolidate", "convert", "open_raw", "mask", "metrics", "qc", "utils", "ops", "synth", "pipeline", "compute_Sv_MVBS", "compute_Sv_clean_MVBS", "combine_echodata",
            "EchoData", "Dataset", "DataArray",
-           "DeviceArray"]
+           "DeviceArray", "targets"]

@@ -57,6 +57,13 @@ REGION_FIELDS = ("n_valid", "n_range", "sv_max", "range_min", "range_max", "sum_
                  "sum_sv_at_range", "sum_dz", "sum_sv_dz")  # enum epa_region_word, in its order
 REGION_WORDS = 11  # EPA_REGION_WORDS
 REGION_ID_SAMPLES, REGION_ID_FIRST, REGION_ID_WORDS = 0, 1, 2  # EPA_REGION_ID_*
+SINGLE_TARGET_TILE = 1024  # EPA_SINGLE_TARGET_TILE
+SINGLE_TARGET_ICOL_NAMES = ("channel_index", "ping_index", "range_sample", "sample_first", "sample_last")  # the rows of icols
+SINGLE_TARGET_FCOL_NAMES = ("TS_uncomp", "TS_comp", "beam_compensation", "target_range", "angle_alongship", "angle_athwartship",
+                            "std_angle_alongship", "std_angle_athwartship", "normalized_pulse_length")  # the rows of fcols
+SINGLE_TARGET_ICOLS, SINGLE_TARGET_FCOLS, SINGLE_TARGET_PARAMS = 5, 9, 5  # EPA_SINGLE_TARGET_ICOLS, _FCOLS, _PARAMS
+SINGLE_TARGET_LIMITS = ("TS_threshold", "pldl", "min_norm_pulse_length", "max_norm_pulse_length", "max_beam_compensation",
+                        "max_std_alongship", "max_std_athwartship")  # the order of `limits`
 
 
 class EpaError(RuntimeError):
@@ -192,6 +199,8 @@ SIGNATURES = {
     "epa_nmea_positions": [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _vp],
     "epa_region_stats": [_vp, _ll, _ll, _vp, _vp, _i, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp],
     "epa_region_labels": [_vp, _ll, _ll, _vp, _ll, _vp, _vp],
+    "epa_single_target_count": [_vp, _vp, _vp, _vp, _i, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
+    "epa_single_target_emit": [_vp, _vp, _vp, _vp, _i, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

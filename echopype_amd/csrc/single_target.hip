@@ -1,0 +1,430 @@
+// Single-target detection, split beam (targets.detect_single_targets): the echoes of individual fish along every
+// (channel, ping) row of a TS cube, compensated for their position in the beam.  The rules are this project's own
+// restatement of the Echoview method (echopype_amd/targets/api.py states them word for word; tests/single_target_ref.py
+// is the NumPy judge).  Two entries, one body (sweep<T, EMIT>):
+//   epa_single_target_count   TS once -> n_targets per row, candidates and rejections per channel  -> single_target_count_kernel
+//   epa_single_target_emit    TS once more, of the rows that hold targets -> the table, at the offsets an exclusive
+//                             scan of n_targets gives                                                -> single_target_emit_kernel
+//
+// A row belongs to one workgroup, which walks it in tiles of EPA_SINGLE_TARGET_TILE samples.  A tile and a halo of
+// kHalo samples on either side are loaded once into LDS, coalesced, four adjacent samples per lane; the candidate test
+// and the envelope walk read LDS.  The halo covers the neighbours of the tile's edges and envelopes of up to kHalo
+// samples beyond them; a walk that leaves the halo goes on in global memory, in lines the neighbouring tile's load
+// fetches anyway.  A walk ends as soon as its length alone exceeds max_norm_pulse_length * spp (rule 1 rejects whatever
+// follows), so the work per candidate is bounded by that length.  The angles and the range are read at the envelopes
+// of the candidates that pass rules 1 and 2, nowhere else.
+//
+// Inside a tile lane t tests the samples t, t + 256, t + 512, t + 768, so that step by step and lane by lane is the order
+// of the samples; ballots and prefix population counts turn the candidates into a list in LDS, in sample order.  The
+// list is then judged a candidate per lane, kBlock at a time: the envelope walks and the loads of the angles of all
+// candidates of a tile run side by side (judged where they are found, each of the four steps waits for the loads of its
+// own few candidates: the emit pass of scripts/bench_single_target.py then took 7.2 / 5.7 ms, f32 / f64, instead of
+// 3.8 / 4.9 ms).  The emit pass places a target at  row offset + targets of earlier rounds +
+// targets of lower waves + popcount(ballot below the lane)  -- no serial lane, no atomic.  The count pass reduces its
+// six counters per wave, then per workgroup; n_targets is a plain store per row, and the per-channel counters take
+// one atomic per counter when a workgroup leaves a channel.
+// Both passes judge a candidate with the same function: what the count pass counted is what the emit pass writes.
+#include "epa_internal.h"
+
+namespace {
+
+using epa::kBlock;
+
+constexpr int kWave = 64;
+constexpr int kWaves = kBlock / kWave;
+constexpr int kTile = EPA_SINGLE_TARGET_TILE;
+constexpr int kSteps = kTile / kBlock;  // samples of a tile a lane judges
+constexpr int kHalo = 64;
+constexpr int kMaxGrid = 65536;  // workgroups of a launch; each takes further rows in a loop
+static_assert(kTile == kBlock * 4, "a lane loads four adjacent samples of a tile");
+static_assert(2 * kHalo <= kBlock, "one lane per halo sample");
+// two neighbours cannot both be candidates (the left one would need TS[s+1] <= TS[s], the right one TS[s] < TS[s+1])
+constexpr int kList = kTile / 2;
+
+struct Limits {
+  double ts_thr, pldl, npl_min, npl_max, max_comp, max_sd_al, max_sd_at;
+};
+
+struct Args {
+  const void* ts;
+  const void* along;
+  const void* athw;
+  const void* range;
+  long long rs_c, rs_p;  // element strides of the range along channel and ping (0: shared); samples adjacent
+  long long C, P;
+  int S;
+  const double* prm;  // [EPA_SINGLE_TARGET_PARAMS][C*P]
+  Limits lim;
+  // count
+  int* n_targets;               // [C*P]
+  unsigned long long* n_cand;   // [C]
+  unsigned long long* n_rej;    // [C*4]
+  // emit
+  const long long* offsets;  // [C*P]: exclusive scan of n_targets
+  long long N;
+  int* icols;     // [EPA_SINGLE_TARGET_ICOLS][N]
+  double* fcols;  // [EPA_SINGLE_TARGET_FCOLS][N]
+};
+
+// one row of TS: the window [lo, hi) of it in LDS, the rest in global memory
+template <typename T>
+struct Row {
+  const T* g;
+  const T* w;
+  int lo, hi, S;
+  __device__ __forceinline__ double at(int k) const { return (double)((k >= lo && k < hi) ? w[k - lo] : g[k]); }
+};
+
+struct RowPrm {
+  double spp, bw_al, bw_at, off_al, off_at;
+};
+
+struct Target {
+  int first, last;
+  double ts, ts_comp, comp, range, al, at, sd_al, sd_at, npl;
+};
+
+// The means and population standard deviations of both angles over [l, r], summed in sample order.  The first kKeep
+// samples of the envelope are fetched by loads that do not wait for one another and are kept for the second pass
+// (an admissible envelope is rarely longer); the rest is read in a loop, twice.
+constexpr int kKeep = 8;
+template <typename T>
+__device__ __forceinline__ void angle_moments(const T* al, const T* at, int l, int r, double& a, double& sa, double& b,
+                                              double& sb) {
+  const int n = r - l + 1;
+  T va[kKeep], vb[kKeep];
+#pragma unroll
+  for (int j = 0; j < kKeep; ++j) {
+    const int k = j < n ? l + j : l;
+    va[j] = al[k], vb[j] = at[k];
+  }
+  double s_a = 0.0, s_b = 0.0;
+#pragma unroll
+  for (int j = 0; j < kKeep; ++j)
+    if (j < n) s_a += (double)va[j], s_b += (double)vb[j];
+  for (int k = l + kKeep; k <= r; ++k) s_a += (double)al[k], s_b += (double)at[k];
+  a = s_a / (double)n, b = s_b / (double)n;
+  double q_a = 0.0, q_b = 0.0;
+#pragma unroll
+  for (int j = 0; j < kKeep; ++j)
+    if (j < n) {
+      const double da = (double)va[j] - a, db = (double)vb[j] - b;
+      q_a += da * da, q_b += db * db;
+    }
+  for (int k = l + kKeep; k <= r; ++k) {
+    const double da = (double)al[k] - a, db = (double)at[k] - b;
+    q_a += da * da, q_b += db * db;
+  }
+  sa = ::sqrt(q_a / (double)n), sb = ::sqrt(q_b / (double)n);
+}
+
+// candidate s with TS v: 0 -> a target (tg filled; its range only when EMIT), 1 .. 4 -> the rule that rejects it
+template <typename T, bool EMIT>
+__device__ int judge(const Row<T>& row, int s, double v, const RowPrm& q, const Limits& lim, const T* along,
+                     const T* athw, const T* rng, Target& tg) {
+  if (!(q.spp > 0.0)) return 1;
+  const double L = v - lim.pldl;
+  int l = s, r = s;
+  double top = v;
+  while (l > 0) {
+    const double x = row.at(l - 1);
+    if (!(x >= L)) break;
+    --l;
+    top = x > top ? x : top;
+    if ((double)(r - l + 1) / q.spp > lim.npl_max) return 1;
+  }
+  while (r < row.S - 1) {
+    const double x = row.at(r + 1);
+    if (!(x >= L)) break;
+    ++r;
+    top = x > top ? x : top;
+    if ((double)(r - l + 1) / q.spp > lim.npl_max) return 1;
+  }
+  const double npl = (double)(r - l + 1) / q.spp;
+  if (!(npl >= lim.npl_min && npl <= lim.npl_max)) return 1;
+  if (top > v) return 2;
+  double a, b, sa, sb;
+  angle_moments(along, athw, l, r, a, sa, b, sb);
+  const double x = 2.0 * (a - q.off_al) / q.bw_al, y = 2.0 * (b - q.off_at) / q.bw_at;
+  const double x2 = x * x, y2 = y * y;
+  const double comp = 6.0206 * (x2 + y2 - 0.18 * x2 * y2);
+  if (!(comp <= lim.max_comp)) return 3;
+  if (!(sa <= lim.max_sd_al && sb <= lim.max_sd_at)) return 4;
+  if (EMIT) {
+    double sw = 0.0, swr = 0.0;
+    int seen = 0;
+    const auto add = [&](double rr, int k) {
+      if (rr == rr) {
+        const double w = ::exp10(row.at(k) / 10.0);
+        sw += w;
+        swr += w * rr;
+        ++seen;
+      }
+    };
+    T vr[kKeep];  // (fetched together, like the angles)
+#pragma unroll
+    for (int j = 0; j < kKeep; ++j) vr[j] = rng[l + j <= r ? l + j : l];
+#pragma unroll
+    for (int j = 0; j < kKeep; ++j)
+      if (l + j <= r) add((double)vr[j], l + j);
+    for (int k = l + kKeep; k <= r; ++k) add((double)rng[k], k);
+    tg.first = l, tg.last = r;
+    tg.ts = v, tg.ts_comp = v + comp, tg.comp = comp;
+    tg.range = seen ? swr / sw : __builtin_nan("");
+    tg.al = a, tg.at = b, tg.sd_al = sa, tg.sd_at = sb, tg.npl = npl;
+  }
+  return 0;
+}
+
+// The tile at t0 of the row ts and its halo into the window that starts at sample lo of the row: a lane brings four
+// adjacent samples (one 16-byte load of float32, two of float64, issued with the alignment of an element: global
+// memory is accessed in unaligned mode), and the first 2 * kHalo lanes one halo sample each.
+template <typename T>
+__device__ __forceinline__ void load_tile(T* win, const T* ts, int S, int t0, int lo, int tid) {
+  const int j0 = t0 + 4 * tid;
+  if (j0 + 4 <= S) {
+    T v[4];
+    __builtin_memcpy(v, __builtin_assume_aligned(ts + j0, sizeof(T)), 4 * sizeof(T));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) win[j0 - lo + e] = v[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (j0 + e < S) win[j0 - lo + e] = ts[j0 + e];
+  }
+  if (tid < kHalo) {
+    if (t0 > 0) win[t0 - kHalo + tid - lo] = ts[t0 - kHalo + tid];  // (t0 is a multiple of kTile >= kHalo)
+  } else if (tid < 2 * kHalo) {
+    const long long k = (long long)t0 + kTile + (tid - kHalo);
+    if (k < S) win[(int)k - lo] = ts[k];
+  }
+}
+
+__device__ __forceinline__ unsigned wave_sum(unsigned x) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, kWave);
+  return x;
+}
+
+template <typename T, bool EMIT>
+__global__ __launch_bounds__(kBlock) void sweep(Args a) {
+  __shared__ T win[kTile + 2 * kHalo];
+  __shared__ unsigned red[6][kWaves];     // count: the six counters of every wave
+  __shared__ unsigned wtot[2][kWaves];    // emit: targets of every wave in this round (two rounds in flight)
+  __shared__ unsigned ccnt[kSteps][kWaves];  // candidates of every wave at every step of the tile
+  __shared__ int list[kList];             // the candidates of the tile, in sample order
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned round = 0;  // rounds of judging so far (uniform): which half of wtot is written
+  const int S = a.S;
+  const long long rows = a.C * a.P;
+  // (count) what this workgroup has gathered for the channel it is in, kept by thread 0
+  long long cur_c = -1;
+  unsigned long long tot_cand = 0, tot_rej[4] = {0, 0, 0, 0};
+  for (long long rowi = blockIdx.x; rowi < rows; rowi += gridDim.x) {
+    if (EMIT && a.n_targets[rowi] == 0) continue;  // (uniform over the workgroup)
+    const long long c = rowi / a.P, p = rowi % a.P;
+    const T* ts = static_cast<const T*>(a.ts) + rowi * S;
+    const T* along = static_cast<const T*>(a.along) + rowi * S;
+    const T* athw = static_cast<const T*>(a.athw) + rowi * S;
+    const T* rng = static_cast<const T*>(a.range) + c * a.rs_c + p * a.rs_p;
+    RowPrm q;
+    q.spp = a.prm[0 * rows + rowi];
+    q.bw_al = a.prm[1 * rows + rowi], q.bw_at = a.prm[2 * rows + rowi];
+    q.off_al = a.prm[3 * rows + rowi], q.off_at = a.prm[4 * rows + rowi];
+    unsigned n_cand = 0, n_tg = 0, n_rej[4] = {0, 0, 0, 0};
+    long long base = EMIT ? a.offsets[rowi] : 0;  // (emit) where the next target of this row goes
+    const long long row_end = EMIT ? base + a.n_targets[rowi] : 0;
+    for (int t0 = 0; t0 < S; t0 += kTile) {
+      __syncthreads();  // every walk of the tile before is over: the window may be overwritten
+      const int lo = t0 >= kHalo ? t0 - kHalo : 0;
+      const int hi = (long long)t0 + kTile + kHalo < S ? t0 + kTile + kHalo : S;
+      load_tile(win, ts, S, t0, lo, tid);
+      __syncthreads();
+      const Row<T> row{ts, win, lo, hi, S};
+      // the candidates of the tile, listed in sample order: lane t looks at the samples t, t + 256, t + 512, t + 768,
+      // so that step by step, wave by wave, lane by lane is the order of the samples
+      unsigned long long votes[kSteps];
+      bool cand[kSteps];
+#pragma unroll
+      for (int e = 0; e < kSteps; ++e) {
+        const long long sl = (long long)t0 + e * kBlock + tid;
+        cand[e] = false;
+        if (sl < S) {
+          const int s = (int)sl;
+          const double v = (double)win[s - lo];
+          cand[e] = v >= a.lim.ts_thr;
+          if (cand[e] && s > 0) cand[e] = !((double)win[s - 1 - lo] >= v);
+          if (cand[e] && s < S - 1) cand[e] = !((double)win[s + 1 - lo] > v);
+        }
+        votes[e] = __ballot(cand[e]);
+        if (lane == 0) ccnt[e][wave] = (unsigned)__popcll(votes[e]);
+      }
+      __syncthreads();
+      unsigned total = 0;
+#pragma unroll
+      for (int e = 0; e < kSteps; ++e) {
+        unsigned mine = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+          mine = w == wave ? total : mine;
+          total += ccnt[e][w];
+        }
+        const unsigned at = mine + (unsigned)__popcll(votes[e] & below);
+        if (cand[e] && at < (unsigned)kList) list[at] = t0 + e * kBlock + tid;
+      }
+      if (total > (unsigned)kList) total = kList;  // (cannot happen, see kList: never read past the list)
+      __syncthreads();
+      // ... and judged side by side, a candidate per lane: the loads of all their envelopes are in flight together
+      for (unsigned i0 = 0; i0 < total; i0 += kBlock, ++round) {  // (total is the same in every lane)
+        bool hit = false;
+        Target tg;
+        int s = 0;
+        if (i0 + tid < total) {
+          s = list[i0 + tid];
+          const int rule = judge<T, EMIT>(row, s, (double)win[s - lo], q, a.lim, along, athw, rng, tg);
+          ++n_cand;
+          if (rule == 0) {
+            hit = true;
+            ++n_tg;
+          } else {
+            ++n_rej[rule - 1];
+          }
+        }
+        if (EMIT) {
+          const unsigned long long hits = __ballot(hit);
+          if (lane == 0) wtot[round & 1][wave] = (unsigned)__popcll(hits);
+          __syncthreads();
+          unsigned before = 0, all = 0;
+#pragma unroll
+          for (int w = 0; w < kWaves; ++w) {
+            const unsigned n = wtot[round & 1][w];
+            before += w < wave ? n : 0u;
+            all += n;
+          }
+          if (hit) {
+            const long long at = base + before + __popcll(hits & below);
+            if (at < row_end && at < a.N) {  // (never false when n_targets and offsets come from the count pass)
+              int* ic = a.icols + at;
+              ic[0 * a.N] = (int)c, ic[1 * a.N] = (int)p, ic[2 * a.N] = s;
+              ic[3 * a.N] = tg.first, ic[4 * a.N] = tg.last;
+              double* fc = a.fcols + at;
+              fc[0 * a.N] = tg.ts, fc[1 * a.N] = tg.ts_comp, fc[2 * a.N] = tg.comp, fc[3 * a.N] = tg.range;
+              fc[4 * a.N] = tg.al, fc[5 * a.N] = tg.at, fc[6 * a.N] = tg.sd_al, fc[7 * a.N] = tg.sd_at;
+              fc[8 * a.N] = tg.npl;
+            }
+          }
+          base += all;
+        }
+      }
+    }
+    if (!EMIT) {
+      const unsigned mine[6] = {n_tg, n_cand, n_rej[0], n_rej[1], n_rej[2], n_rej[3]};
+      __syncthreads();  // thread 0 has read the counters of the row before
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        const unsigned s = wave_sum(mine[k]);
+        if (lane == 0) red[k][wave] = s;
+      }
+      __syncthreads();
+      if (tid == 0) {
+        unsigned sum[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          sum[k] = 0;
+#pragma unroll
+          for (int w = 0; w < kWaves; ++w) sum[k] += red[k][w];
+        }
+        a.n_targets[rowi] = (int)sum[0];
+        if (c != cur_c) {
+          if (cur_c >= 0) {
+            if (tot_cand) atomicAdd(a.n_cand + cur_c, tot_cand);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (tot_rej[k]) atomicAdd(a.n_rej + cur_c * 4 + k, tot_rej[k]);
+          }
+          cur_c = c, tot_cand = 0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) tot_rej[k] = 0;
+        }
+        tot_cand += sum[1];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tot_rej[k] += sum[2 + k];
+      }
+    }
+  }
+  if (!EMIT && tid == 0 && cur_c >= 0) {
+    if (tot_cand) atomicAdd(a.n_cand + cur_c, tot_cand);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (tot_rej[k]) atomicAdd(a.n_rej + cur_c * 4 + k, tot_rej[k]);
+  }
+}
+
+int check_inputs(const char* who, const void* ts, const void* along, const void* athw, const void* range, int dtype,
+                 long long C, long long P, long long S, long long rs_c, long long rs_p, const double* prm) {
+  EPA_CHECK_REAL(who, dtype);
+  EPA_CHECK_ARG(C >= 0 && P >= 0 && S >= 0 && C <= 65535 && P < 0x7fffffffLL && S < 0x7fffffffLL - kTile - kHalo,
+                "%s: bad shape C=%lld P=%lld S=%lld", who, C, P, S);
+  EPA_CHECK_ARG(C * P < 0x7fffffffLL, "%s: C*P=%lld rows", who, C * P);
+  EPA_CHECK_ARG(rs_c >= 0 && rs_p >= 0, "%s: range strides %lld, %lld", who, rs_c, rs_p);
+  EPA_CHECK_ARG(C * P * S == 0 || (ts && along && athw && range && prm), "%s: NULL array argument", who);
+  return EPA_OK;
+}
+
+Args make_args(const void* ts, const void* along, const void* athw, const void* range, long long C, long long P,
+               long long S, long long rs_c, long long rs_p, const double* prm, const double* limits) {
+  Args a = {};
+  a.ts = ts, a.along = along, a.athw = athw, a.range = range, a.rs_c = rs_c, a.rs_p = rs_p;
+  a.C = C, a.P = P, a.S = (int)S, a.prm = prm;
+  a.lim = Limits{limits[0], limits[1], limits[2], limits[3], limits[4], limits[5], limits[6]};
+  return a;
+}
+
+int grid_for(long long rows) { return (int)(rows < kMaxGrid ? rows : kMaxGrid); }
+
+}  // namespace
+
+extern "C" int epa_single_target_count(const void* ts, const void* along, const void* athw, const void* range,
+                                       int dtype, long long C, long long P, long long S, long long range_stride_c,
+                                       long long range_stride_p, const double* prm, const double* limits,
+                                       int* n_targets, unsigned long long* n_candidates,
+                                       unsigned long long* n_rejected, epa_stream_t stream) {
+  const char* who = "epa_single_target_count";
+  if (int rc = check_inputs(who, ts, along, athw, range, dtype, C, P, S, range_stride_c, range_stride_p, prm)) return rc;
+  EPA_CHECK_ARG(limits, "%s: NULL limits", who);
+  EPA_CHECK_ARG(C * P == 0 || (n_targets && n_candidates && n_rejected), "%s: NULL output argument", who);
+  if (C * P == 0) return EPA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (S == 0) {  // rows without samples hold no targets
+    EPA_CHECK_HIP(hipMemsetAsync(n_targets, 0, (size_t)(C * P) * sizeof(int), st));
+    return EPA_OK;
+  }
+  Args a = make_args(ts, along, athw, range, C, P, S, range_stride_c, range_stride_p, prm, limits);
+  a.n_targets = n_targets, a.n_cand = n_candidates, a.n_rej = n_rejected;
+  return epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sweep<T, false><<<grid_for(C * P), kBlock, 0, st>>>(a);
+    return epa::check_launch("single_target_count_kernel");
+  });
+}
+
+extern "C" int epa_single_target_emit(const void* ts, const void* along, const void* athw, const void* range, int dtype,
+                                      long long C, long long P, long long S, long long range_stride_c,
+                                      long long range_stride_p, const double* prm, const double* limits,
+                                      const int* n_targets, const long long* offsets, long long N, int* icols,
+                                      double* fcols, epa_stream_t stream) {
+  const char* who = "epa_single_target_emit";
+  if (int rc = check_inputs(who, ts, along, athw, range, dtype, C, P, S, range_stride_c, range_stride_p, prm)) return rc;
+  EPA_CHECK_ARG(limits, "%s: NULL limits", who);
+  EPA_CHECK_ARG(N >= 0 && N <= C * P * S, "%s: N=%lld targets of %lld samples", who, N, C * P * S);
+  if (N == 0) return EPA_OK;
+  EPA_CHECK_ARG(n_targets && offsets && icols && fcols, "%s: NULL table argument", who);
+  Args a = make_args(ts, along, athw, range, C, P, S, range_stride_c, range_stride_p, prm, limits);
+  a.n_targets = const_cast<int*>(n_targets), a.offsets = offsets, a.N = N, a.icols = icols, a.fcols = fcols;
+  return epa::dispatch_real(who, dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    sweep<T, true><<<grid_for(C * P), kBlock, 0, (hipStream_t)stream>>>(a);
+    return epa::check_launch("single_target_emit_kernel");
+  });
+}

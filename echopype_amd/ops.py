@@ -1041,6 +1041,71 @@ def region_labels(code, rank):
     return labels
 
 
+# ---- single targets, split beam (targets.detect_single_targets) -------------------------------------------------------
+SINGLE_TARGET_TILE = _lib.SINGLE_TARGET_TILE  # samples of a row a workgroup holds at a time (EPA_SINGLE_TARGET_TILE)
+
+
+def _single_target_args(who, ts, along, athw, range, prm, limits):
+    """The arguments the two single-target entries share, checked: -> (tuple of C arguments, keep-alive list)."""
+    if ts.dim() != 3 or ts.dtype not in _DT:
+        raise ValueError(f"{who}: TS must be float32 / float64 of shape (C, P, S), got {ts.dtype} {tuple(ts.shape)}")
+    C, P, S = ts.shape
+    for name, t in (("angle_alongship", along), ("angle_athwartship", athw)):
+        if t.dtype != ts.dtype or tuple(t.shape) != (C, P, S):
+            raise ValueError(f"{who}: {name} must be {ts.dtype} of shape {(C, P, S)}, got {t.dtype} {tuple(t.shape)}")
+    if range.dtype != ts.dtype or not range.is_cuda:
+        raise ValueError(f"{who}: range must be a device tensor of TS's type")
+    try:
+        rv = range.expand(C, P, S)
+    except RuntimeError:
+        raise ValueError(f"{who}: range of shape {tuple(range.shape)} does not broadcast to {(C, P, S)}") from None
+    if S > 1 and rv.stride(2) != 1:  # (samples apart, or no sample axis: the one case copied)
+        rv = rv.contiguous()
+    rs_c, rs_p = (rv.stride(0) if C > 1 else 0), (rv.stride(1) if P > 1 else 0)
+    if prm.dtype != torch.float64 or tuple(prm.shape) != (5, C, P):
+        raise ValueError(f"{who}: prm must be float64 of shape {(5, C, P)}, got {prm.dtype} {tuple(prm.shape)}")
+    lim = np.ascontiguousarray(limits, dtype=np.float64)
+    if lim.shape != (len(_lib.SINGLE_TARGET_LIMITS),):
+        raise ValueError(f"{who}: {len(_lib.SINGLE_TARGET_LIMITS)} limits expected, got an array of shape {lim.shape}")
+    args = (_p(ts), _p(along), _p(athw), ctypes.c_void_p(rv.data_ptr()), _DT[ts.dtype], C, P, S, rs_c, rs_p, _p(prm),
+            lim.ctypes.data_as(ctypes.c_void_p))
+    return args, (rv, lim)
+
+
+def single_target_count(ts, along, athw, range, prm, limits):
+    """The count pass of the single-target detection over a (C, P, S) cube ``ts`` with its angle cubes (same type and
+    shape), its ``range`` ((C, P, S) or broadcasting to it: read through its strides, samples adjacent), ``prm`` f64
+    (5, C, P) = samples per pulse, the two beamwidths, the two angle offsets, and the seven host ``limits`` in the
+    order of ``_lib.SINGLE_TARGET_LIMITS`` -> (``n_targets`` int32 (C, P), ``n_candidates`` int64 (C,),
+    ``n_rejected`` int64 (C, 4))."""
+    args, keep = _single_target_args("single_target_count", ts, along, athw, range, prm, limits)
+    C, P, _ = ts.shape
+    dev = ts.device
+    n_targets = torch.empty((C, P), dtype=torch.int32, device=dev)
+    n_cand = torch.zeros(C, dtype=torch.int64, device=dev)
+    n_rej = torch.zeros((C, 4), dtype=torch.int64, device=dev)
+    call("epa_single_target_count", *args, _p(n_targets), _p(n_cand), _p(n_rej), _stream())
+    del keep
+    return n_targets, n_cand, n_rej
+
+
+def single_target_emit(ts, along, athw, range, prm, limits, n_targets, offsets, n):
+    """The emit pass: the inputs of ``single_target_count``, the ``n_targets`` it left, ``offsets`` int64 (C, P) their
+    exclusive scan and ``n`` their sum -> (int32 (5, n), float64 (9, n)): the columns ``_lib.SINGLE_TARGET_ICOL_NAMES`` and
+    ``_lib.SINGLE_TARGET_FCOL_NAMES``, ordered by (channel, ping, sample)."""
+    args, keep = _single_target_args("single_target_emit", ts, along, athw, range, prm, limits)
+    C, P, _ = ts.shape
+    n = int(n)
+    if n_targets.dtype != torch.int32 or tuple(n_targets.shape) != (C, P) or offsets.dtype != torch.int64 or \
+            tuple(offsets.shape) != (C, P) or n <= 0:
+        raise ValueError(f"single_target_emit: n_targets int32 and offsets int64 of shape {(C, P)} and n > 0 expected")
+    icols = torch.empty((_lib.SINGLE_TARGET_ICOLS, n), dtype=torch.int32, device=ts.device)
+    fcols = torch.empty((_lib.SINGLE_TARGET_FCOLS, n), dtype=torch.float64, device=ts.device)
+    call("epa_single_target_emit", *args, _p(n_targets), _p(offsets), n, _p(icols), _p(fcols), _stream())
+    del keep
+    return icols, fcols
+
+
 # ---- transient-noise detectors (clean.detect_transient) --------------------------------------------------------------
 def transient_fielding(sv, chan, n, thr0, thr1, maxts):
     """Fielding's transient-noise mask of a (C, P, S) cube -> bool (C, P, S), True = valid.  ``chan``: host int (C, 4)

@@ -449,3 +449,116 @@ def transient_scene(P=200, S=300, seed=20261019, dtype=np.float64, dz=2.5, eleva
     sv[rng.random((P, S)) < nan_frac] = np.nan
     return {"Sv": sv.astype(dtype), "depth": depth.astype(dtype), "bottom": bottom, "pings": pings, "tops": tops,
             "gains": gains}
+
+
+def single_target_scene(P=37, S=257, seed=20261020, dtype=np.float64, seam=1024, density=0.6, floor=-75.0, dr=0.2,
+                        scale=1):
+    """One channel's (ping_time, range_sample) planes for the single-target detector, as a dict of NumPy arrays:
+    ``TS``, ``angle_alongship``, ``angle_athwartship`` (P, S) of ``dtype`` and ``echo_range`` (S,) = ``dr * arange(S)``.
+    - a noise floor around ``floor`` dB (spread 3 dB: well below a -50 dB threshold) with angles scattered over +-5
+      degrees; a row of fewer than 16 samples is instead one echo throughout: samples within 5 dB of each other
+      below a level between -52 and -35 dB, one beam position, twice the angle jitter below, 5 % of the samples NaN;
+    - the row is cut into slots of 16 samples, and a slot carries an echo with probability ``density``: mostly echoes
+      parabolic in dB, of a half-width (at 6 dB) between 0.6 and 4.5 samples about a centre between two samples, peak
+      between -55 and -30 dB, at a random position in the beam (out to 4.5 degrees off axis) and with an angle jitter
+      of 0.05, 0.3 or 0.9 degrees from sample to sample; and, planted because random echoes almost never make them:
+      overlapping pairs (a weaker peak inside the envelope of a stronger one), plateaus of two equal samples, and
+      echoes with a NaN inside the envelope (in TS, or in one of the angles);
+    - every fourth ping starts with an echo whose peak is sample 0, the next with one whose envelope starts there; the
+      two after that end the row likewise;
+    - every third ping carries an echo across each multiple of ``seam`` (the tile length of the kernel), its peak
+      alternately on the sample before the seam and on it.
+    ``scale`` = k > 1 stretches everything along the row by k (longer pulses: a detector then wants ``spp`` near 4 k):
+    slots of 16 k samples, half-widths k times as large, the planted shapes interpolated to k times their length.  The
+    pair becomes a wide parabola with a spike 3 dB above its peak k samples beside it; the echo across a seam reaches
+    about 2.4 k samples over it, alternately from the sample before the seam and back from the sample on it."""
+    rng = np.random.default_rng(seed)
+    k = max(int(scale), 1)
+
+    def stretch(shape):
+        shape = np.asarray(shape, dtype=np.float64)
+        m = len(shape)
+        return shape if k == 1 else np.interp(np.arange((m - 1) * k + 1) / k, np.arange(m), shape)
+
+    ts = floor + 3.0 * rng.standard_normal((P, S))
+    al = rng.uniform(-5.0, 5.0, (P, S))
+    at = rng.uniform(-5.0, 5.0, (P, S))
+
+    def position():
+        u = rng.random()
+        rad = rng.uniform(0.0, 2.0) if u < 0.6 else (rng.uniform(2.0, 3.2) if u < 0.85 else rng.uniform(3.2, 4.5))
+        phi = rng.uniform(0.0, 2.0 * np.pi)
+        return rad * np.cos(phi), rad * np.sin(phi), (0.05, 0.3, 0.9)[int(rng.choice(3, p=(0.65, 0.2, 0.15)))]
+
+    def put(p, s0, shape, nan_angle=None):
+        """The dB values ``shape`` (NaN allowed) from sample ``s0`` on, clipped to the row, with one beam position."""
+        a0, b0, jit = position()
+        for j, v in enumerate(shape):
+            s = s0 + j
+            if 0 <= s < S:
+                ts[p, s] = v
+                al[p, s] = a0 + jit * rng.standard_normal()
+                at[p, s] = b0 + jit * rng.standard_normal()
+                if nan_angle is not None and j == len(shape) // 2:
+                    (al if nan_angle == 0 else at)[p, s] = np.nan
+
+    def parabola(v, h, frac, half=6):
+        k = np.arange(-half, half + 1)
+        shape = v - 6.0 * ((k - frac) / h) ** 2
+        return shape[shape > v - 25.0]
+
+    if S < 16:
+        for p in range(P):
+            a0, b0, jit = position()
+            ts[p] = rng.uniform(-52.0, -35.0) - rng.uniform(0.0, 5.0, S)
+            al[p] = a0 + 2.0 * jit * rng.standard_normal(S)
+            at[p] = b0 + 2.0 * jit * rng.standard_normal(S)
+        ts[rng.random((P, S)) < 0.05] = np.nan
+    else:
+        for p in range(P):
+            for slot in range(S // (16 * k)):
+                if rng.random() >= density:
+                    continue
+                s0 = slot * 16 * k + 3 * k
+                v = rng.uniform(-55.0, -30.0)
+                kind = rng.random()
+                if kind < 0.55:
+                    sh = parabola(v, k * float(rng.choice((0.6, 1.2, 1.8, 2.4, 3.2, 4.5))), rng.uniform(-0.5, 0.5), 6 * k)
+                    put(p, s0 + 5 * k - len(sh) // 2, sh)
+                elif kind < 0.7:  # the weaker peak v lies in the envelope of v + 3
+                    if k == 1:
+                        put(p, s0, [v - 9, v - 3, v, v - 2.5, v - 2, v + 3, v - 1, v - 9])
+                    else:
+                        sh = parabola(v, 1.6 * k, rng.uniform(-0.4, 0.4), 6 * k)
+                        sh[len(sh) // 2 + k] = v + 3
+                        put(p, s0 + 5 * k - len(sh) // 2, sh)
+                elif kind < 0.8:
+                    put(p, s0, stretch([v - 8, v - 2, v, v, v - 2, v - 8]))
+                elif kind < 0.88:
+                    sh = stretch([v - 8, v - 2, v, v - 1, v - 2, v - 8]).copy()
+                    sh[3 * k] = np.nan
+                    put(p, s0, sh)
+                else:
+                    put(p, s0, stretch([v - 8, v - 2, v - 1, v, v - 1.5, v - 8]), nan_angle=int(rng.integers(2)))
+            v = rng.uniform(-45.0, -32.0)
+            end = p % 4
+            if end == 0:
+                put(p, 0, stretch([v, v - 2, v - 4, v - 9, v - 30]))
+            elif end == 1:
+                put(p, 0, stretch([v - 2, v, v - 1, v - 3, v - 9, v - 30]))
+            elif end == 2:
+                put(p, S - 4 * k - 1, stretch([v - 30, v - 9, v - 4, v - 2, v]))
+            else:
+                put(p, S - 5 * k - 1, stretch([v - 30, v - 9, v - 3, v - 1, v, v - 2]))
+            if p % 3 == 0:
+                for m in range(seam, S - 4 * k, seam):
+                    v = rng.uniform(-45.0, -32.0)
+                    sh = stretch([v - 30, v - 9, v - 3, v, v - 2, v - 4, v - 9, v - 30])
+                    if k == 1:
+                        put(p, m - 4 + (p // 3) % 2, sh)
+                    elif (p // 3) % 2 == 0:
+                        put(p, m - 1 - 3 * k, sh)      # the peak on the sample before the seam, the long side after it
+                    else:
+                        put(p, m - 4 * k, sh[::-1])    # the peak on the seam, the long side before it
+    return {"TS": ts.astype(dtype), "angle_alongship": al.astype(dtype), "angle_athwartship": at.astype(dtype),
+            "echo_range": (dr * np.arange(S)).astype(dtype)}

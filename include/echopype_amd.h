@@ -1085,6 +1085,37 @@ enum epa_nmea_type { EPA_NMEA_GGA = 0, EPA_NMEA_GLL = 1, EPA_NMEA_RMC = 2 };
 int epa_nmea_positions(const uint8_t* bytes, long long n_bytes, long long n_alloc, const int64_t* table_host,
                        const int64_t* table, long long n, double* lat, double* lon, uint8_t* code, epa_stream_t stream);
 
+/* ---- single targets, split beam: targets.detect_single_targets (targets/api.py) -------------------------------------
+ * The echoes of individual fish along every (channel, ping) row, by this project's restatement of the Echoview
+ * single-target detection (split beam); targets/api.py states the six rules, and the two entries apply them alike.
+ * ts, along, athw: [C*P*S] of dtype F32 / F64 (converted to f64 exactly; all arithmetic is f64); the sample (c, p, s) of
+ * the range, of the same dtype, is range[c * range_stride_c + p * range_stride_p + s] (element strides >= 0; 0 shares a
+ * row).  prm f64 [EPA_SINGLE_TARGET_PARAMS][C*P]: samples per pulse, beamwidth alongship / athwartship, angle offset
+ * alongship / athwartship of every row.  limits: HOST f64 [7] = TS_threshold, pldl, min_norm_pulse_length,
+ * max_norm_pulse_length, max_beam_compensation, max_std_alongship, max_std_athwartship.
+ * A row belongs to one workgroup, which walks it in tiles of EPA_SINGLE_TARGET_TILE samples.
+ *
+ * count: n_targets i32 [C*P] is written completely; n_candidates u64 [C] and n_rejected u64 [C*4] (rules 1 .. 4), zeroed
+ * by the caller, are added to.  C*P == 0 launches nothing; S == 0 zeroes n_targets. */
+#define EPA_SINGLE_TARGET_TILE 1024
+#define EPA_SINGLE_TARGET_PARAMS 5
+#define EPA_SINGLE_TARGET_ICOLS 5 /* channel_index, ping_index, range_sample (the peak), sample_first, sample_last */
+#define EPA_SINGLE_TARGET_FCOLS 9 /* TS_uncomp, TS_comp, beam_compensation, target_range, angle_alongship,
+                                   * angle_athwartship, std_angle_alongship, std_angle_athwartship,
+                                   * normalized_pulse_length */
+int epa_single_target_count(const void* ts, const void* along, const void* athw, const void* range, int dtype,
+                            long long C, long long P, long long S, long long range_stride_c, long long range_stride_p,
+                            const double* prm, const double* limits, int* n_targets, unsigned long long* n_candidates,
+                            unsigned long long* n_rejected, epa_stream_t stream);
+/* emit: the same inputs, n_targets as count left it, offsets i64 [C*P] its exclusive scan over (channel, ping) and N its
+ * sum.  icols i32 [EPA_SINGLE_TARGET_ICOLS][N] and fcols f64 [EPA_SINGLE_TARGET_FCOLS][N] take one column entry per
+ * target, ordered by (channel, ping, sample); a row writes inside [offsets, offsets + n_targets) and below N only.
+ * Rows whose n_targets is 0 are not read.  N == 0 launches nothing. */
+int epa_single_target_emit(const void* ts, const void* along, const void* athw, const void* range, int dtype,
+                           long long C, long long P, long long S, long long range_stride_c, long long range_stride_p,
+                           const double* prm, const double* limits, const int* n_targets, const long long* offsets,
+                           long long N, int* icols, double* fcols, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
