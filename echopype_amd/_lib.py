@@ -64,6 +64,15 @@ SINGLE_TARGET_FCOL_NAMES = ("TS_uncomp", "TS_comp", "beam_compensation", "target
 SINGLE_TARGET_ICOLS, SINGLE_TARGET_FCOLS, SINGLE_TARGET_PARAMS = 5, 9, 5  # EPA_SINGLE_TARGET_ICOLS, _FCOLS, _PARAMS
 SINGLE_TARGET_LIMITS = ("TS_threshold", "pldl", "min_norm_pulse_length", "max_norm_pulse_length", "max_beam_compensation",
                         "max_std_alongship", "max_std_athwartship")  # the order of `limits`
+TRACK_TILE = 128  # EPA_TRACK_TILE
+TRACK_PARAMS, TRACK_ICOLS, TRACK_FCOLS = 11, 6, 13  # EPA_TRACK_PARAMS, _ICOLS, _FCOLS
+TRACK_PARAM_NAMES = ("gate_alongship", "gate_athwartship", "gate_range", "max_ping_gap", "missed_ping_expansion",
+                "weight_alongship", "weight_athwartship", "weight_range", "weight_TS", "weight_ping_gap",
+                "max_TS_difference")  # the order of `params` (EPA_TRACK_PARAMS of them; max_TS_difference 0: no TS gate)
+TRACK_ICOL_NAMES = ("channel_index", "n_targets", "ping_first", "ping_last", "target_first",
+                    "target_last")  # the rows of a track's icols
+TRACK_FCOL_NAMES = ("TS_mean", "TS_max", "range_mean", "x_first", "y_first", "z_first", "x_last", "y_last", "z_last",
+                    "path_length", "displacement", "tortuosity", "delta_range")  # the rows of a track's fcols
 
 
 class EpaError(RuntimeError):
@@ -201,6 +210,12 @@ SIGNATURES = {
     "epa_region_labels": [_vp, _ll, _ll, _vp, _ll, _vp, _vp],
     "epa_single_target_count": [_vp, _vp, _vp, _vp, _i, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
     "epa_single_target_emit": [_vp, _vp, _vp, _vp, _i, _ll, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp],
+    "epa_track_prepare": [_vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
+    "epa_track_propose": [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
+    "epa_track_accept": [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
+    "epa_track_roots": [_vp, _ll, _i, _vp, _vp, _vp, _vp, _vp],
+    "epa_track_chains": [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp],
+    "epa_track_table": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -1,0 +1,430 @@
+// Target tracking (targets.track_targets): the single targets of one fish over consecutive pings grouped into a track,
+// by gated nearest-neighbour linking settled in a fixed number of propose / accept rounds.  The rules are this project's
+// own (echopype_amd/targets/track.py states them word for word; tests/track_ref.py is the NumPy judge).  The table is
+// ordered by (channel, ping), so the rows of one (channel, ping) are a segment and the rows a target may link to are ONE
+// contiguous run of segments.  Six entries:
+//   epa_track_prepare   positions, the segment starts (a lower bound per (channel, ping)), the verdict on
+//                       the table's order and indices, empty links                              -> track_prepare_kernel
+//   epa_track_propose   every target without a successor picks the gated free target of least (cost, row)
+//                       in the run ahead of it                                                  -> track_propose_kernel
+//   epa_track_accept    every target without a predecessor picks, among those that proposed to it, the one of
+//                       least (cost, row), recomputing the cost with the same function            -> track_accept_kernel
+//   epa_track_roots     pointer doubling over pred: the root of every chain and the position in it -> track_roots_kernel
+//   epa_track_chains    at every chain's last target: is it a track, and how long               -> track_chains_kernel
+//   epa_track_table     track numbers, the members of every track laid out in chain order
+//                       (track_order_kernel), and one wave per track over them                  -> track_table_kernel
+//
+// Propose and accept give a workgroup of one wave one (channel, ping) segment; the run is staged through LDS in tiles of
+// EPA_TRACK_TILE rows, and every lane walks the tile for its own target (all lanes read the same LDS word: a
+// broadcast).  The cost is evaluated without contraction into fused multiply-adds, so that it has the same bits in
+// both kernels (and in IEEE arithmetic anywhere else): accept needs no 64-bit atomics, and nothing depends on arrival
+// order.  Every kernel is memory-safe on ANY table content: the segment starts are lower bounds inside [0, n] whatever
+// the order of the rows, a pair is linked only if the two rows' own indices say so (same channel, later ping), so
+// the links cannot form a cycle, and every stored row number is one this library wrote.
+#include "epa_internal.h"
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kLinkBlock = kWave;  // propose / accept: one wave per (channel, ping) segment
+constexpr int kTile = EPA_TRACK_TILE;
+constexpr int kMaxGrid = 1 << 20;  // workgroups of a link launch; each takes further segments in a loop
+static_assert(kTile % kLinkBlock == 0, "a lane stages kTile / kLinkBlock rows of a tile");
+
+struct Gates {
+  double g_al, g_at, g_r, expansion, w_al, w_at, w_r, w_ts, w_gap, max_ts;  // max_ts == 0: no TS gate
+  int max_gap;
+};
+
+Gates make_gates(const double* p) {
+  Gates g;
+  g.g_al = p[0], g.g_at = p[1], g.g_r = p[2];
+  g.max_gap = (int)p[3];
+  g.expansion = p[4];
+  g.w_al = p[5], g.w_at = p[6], g.w_r = p[7], g.w_ts = p[8], g.w_gap = p[9];
+  g.max_ts = p[10];
+  return g;
+}
+
+bool gates_ok(const double* p) {
+  if (!p) return false;
+  for (int k = 0; k < EPA_TRACK_PARAMS; ++k)
+    if (!(p[k] >= 0.0) || !(p[k] < 1e300)) return false;
+  return p[0] > 0.0 && p[1] > 0.0 && p[2] > 0.0 && p[3] <= 1073741824.0 && p[3] == (double)(long long)p[3];
+}
+
+struct Point {
+  double x, y, z, ts;
+  int ping, chan;
+};
+
+__device__ __forceinline__ bool linkable(const Point& a) { return a.x == a.x && a.y == a.y && a.z == a.z && a.ts == a.ts; }
+
+// rules 2 and 3 for the pair (i earlier, j later): false if not gated, else the cost.  No contraction: every operation
+// is rounded on its own, in the order written, wherever this is inlined.
+__device__ __forceinline__ bool pair_cost(const Gates& q, const Point& i, const Point& j, double& cost) {
+#pragma clang fp contract(off)
+  if (i.chan != j.chan) return false;
+  const long long k = (long long)j.ping - (long long)i.ping - 1;
+  if (k < 0 || k > (long long)q.max_gap) return false;
+  const double f = 1.0 + (double)k * q.expansion / 100.0;
+  const double dx = ::fabs(j.x - i.x) / (f * q.g_al);
+  const double dy = ::fabs(j.y - i.y) / (f * q.g_at);
+  const double dz = ::fabs(j.z - i.z) / (f * q.g_r);
+  if (!(dx <= 1.0 && dy <= 1.0 && dz <= 1.0)) return false;
+  double dT = 0.0;
+  if (q.max_ts > 0.0) {
+    dT = ::fabs(j.ts - i.ts) / q.max_ts;
+    if (!(dT <= 1.0)) return false;
+  }
+  double c = q.w_al * (dx * dx);
+  c = c + q.w_at * (dy * dy);
+  c = c + q.w_r * (dz * dz);
+  if (q.w_ts > 0.0) c = c + q.w_ts * (dT * dT);
+  c = c + q.w_gap * (double)k / (double)(q.max_gap > 1 ? q.max_gap : 1);
+  cost = c;
+  return true;
+}
+
+// ---- prepare ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long row_key(const int* chan, const int* ping, long long P, long long i) {
+  return (long long)chan[i] * P + (long long)ping[i];
+}
+
+__global__ __launch_bounds__(epa::kBlock) void prepare_kernel(const int* chan, const int* ping, const double* range,
+                                                              const double* along, const double* athw, long long n,
+                                                              long long C, long long P, int* seg, double* xyz,
+                                                              int* succ, int* pred, int* bad) {
+  const long long t = (long long)blockIdx.x * epa::kBlock + threadIdx.x;
+  if (t < n) {
+    const int c = chan[t], p = ping[t];
+    bool wrong = c < 0 || c >= C || p < 0 || p >= P;
+    if (t > 0 && row_key(chan, ping, P, t - 1) > row_key(chan, ping, P, t)) wrong = true;
+    if (wrong) bad[0] = 1;  // (every writer stores the same word)
+    const double kRad = 3.14159265358979323846 / 180.0;
+    const double u = ::tan(along[t] * kRad), v = ::tan(athw[t] * kRad);
+    const double z = range[t] / ::sqrt(1.0 + u * u + v * v);
+    xyz[t] = z * u, xyz[n + t] = z * v, xyz[2 * n + t] = z;
+    succ[t] = -1, pred[t] = -1;
+  }
+  if (t <= C * P) {  // the first row whose key is not below t: inside [0, n] whatever the rows hold
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+      const long long mid = lo + (hi - lo) / 2;
+      if (row_key(chan, ping, P, mid) < t) lo = mid + 1;
+      else hi = mid;
+    }
+    seg[t] = (int)lo;
+  }
+}
+
+// ---- propose / accept --------------------------------------------------------------------------------------------------
+struct LinkArgs {
+  const int* chan;
+  const int* ping;
+  const double* xyz;  // [3][n]
+  const double* ts;
+  long long n, C, P;
+  const int* seg;  // [C*P + 1]
+  Gates q;
+  int* succ;
+  int* pred;
+  int* prop;
+};
+
+__device__ __forceinline__ Point load_point(const LinkArgs& a, long long i) {
+  Point r;
+  r.x = a.xyz[i], r.y = a.xyz[a.n + i], r.z = a.xyz[2 * a.n + i], r.ts = a.ts[i];
+  r.ping = a.ping[i], r.chan = a.chan[i];
+  return r;
+}
+
+template <bool ACCEPT>
+__global__ __launch_bounds__(kLinkBlock) void link_kernel(LinkArgs a) {
+  __shared__ double sx[kTile], sy[kTile], sz[kTile], st[kTile];
+  __shared__ int sping[kTile], schan[kTile], sstate[kTile];  // state: pred of the row (propose), prop of the row (accept)
+  const int tid = threadIdx.x;
+  const long long keys = a.C * a.P;
+  for (long long key = blockIdx.x; key < keys; key += gridDim.x) {
+    const long long lo = a.seg[key], hi = a.seg[key + 1];
+    if (lo >= hi) continue;  // (uniform over the workgroup) an empty ping, or rows out of order
+    const long long c = key / a.P, p = key % a.P;
+    long long rlo, rhi;  // the run of rows a target of this segment may link to / be linked from
+    if (!ACCEPT) {
+      const long long last = p + 2 + a.q.max_gap < a.P ? p + 2 + a.q.max_gap : a.P;  // clipped at the channel's end
+      rlo = hi, rhi = a.seg[c * a.P + last];
+    } else {
+      const long long first = p - 1 - a.q.max_gap > 0 ? p - 1 - a.q.max_gap : 0;
+      rlo = a.seg[c * a.P + first], rhi = lo;
+    }
+    for (long long i0 = lo; i0 < hi; i0 += kLinkBlock) {
+      const long long i = i0 + tid;
+      const bool active = i < hi;
+      Point me = {};
+      bool live = false;
+      if (active) {
+        me = load_point(a, i);
+        live = linkable(me) && (ACCEPT ? a.pred[i] : a.succ[i]) < 0;
+      }
+      double best_c = 0.0;
+      int best = -1;
+      for (long long t0 = rlo; t0 < rhi; t0 += kTile) {
+        const int m = (int)(rhi - t0 < kTile ? rhi - t0 : kTile);
+        __syncthreads();  // every lane is done with the tile before
+        for (int k = tid; k < m; k += kLinkBlock) {
+          const Point o = load_point(a, t0 + k);
+          sx[k] = o.x, sy[k] = o.y, sz[k] = o.z, st[k] = o.ts, sping[k] = o.ping, schan[k] = o.chan;
+          sstate[k] = ACCEPT ? a.prop[t0 + k] : a.pred[t0 + k];
+        }
+        __syncthreads();
+        if (live) {
+          for (int k = 0; k < m; ++k) {  // rows ascending: of equal costs the lower row stays
+            if (ACCEPT ? sstate[k] != (int)i : sstate[k] >= 0) continue;
+            const Point o = {sx[k], sy[k], sz[k], st[k], sping[k], schan[k]};
+            double cst;
+            if (!linkable(o) || !(ACCEPT ? pair_cost(a.q, o, me, cst) : pair_cost(a.q, me, o, cst))) continue;
+            if (best < 0 || cst < best_c) best_c = cst, best = (int)(t0 + k);
+          }
+        }
+      }
+      if (!ACCEPT) {
+        if (active) a.prop[i] = best;
+      } else if (best >= 0) {
+        a.pred[i] = best;   // (best proposed to this row alone: no other lane writes its succ)
+        a.succ[best] = (int)i;
+      }
+    }
+  }
+}
+
+// ---- roots -------------------------------------------------------------------------------------------------------------
+// one doubling pass: ptr <- ptr[ptr], rank <- rank + rank[ptr].  The first pass reads pred itself (ptr = pred or the row,
+// rank = 1 or 0).
+template <bool FIRST>
+__global__ __launch_bounds__(epa::kBlock) void roots_kernel(const int* pred, const int* ptr_in, const int* rank_in,
+                                                            int* ptr_out, int* rank_out, long long n) {
+  const long long i = (long long)blockIdx.x * epa::kBlock + threadIdx.x;
+  if (i >= n) return;
+  int q, r, q2, r2;
+  if (FIRST) {
+    const int pr = pred[i];
+    q = pr >= 0 ? pr : (int)i, r = pr >= 0;
+    const int pq = pred[q];
+    q2 = pq >= 0 ? pq : q, r2 = pq >= 0;
+  } else {
+    q = ptr_in[i], r = rank_in[i];
+    q2 = ptr_in[q], r2 = rank_in[q];
+  }
+  ptr_out[i] = q2, rank_out[i] = r + r2;
+}
+
+// ---- chains ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(epa::kBlock) void chains_kernel(const int* ping, const double* xyz, const double* ts,
+                                                             const int* succ, const int* root, const int* rank,
+                                                             long long n, int min_targets, int min_pings,
+                                                             int* flag_len) {  // [2][n], zeroed: is a track, its length
+  const long long i = (long long)blockIdx.x * epa::kBlock + threadIdx.x;
+  if (i >= n || succ[i] >= 0) return;
+  const Point me = {xyz[i], xyz[n + i], xyz[2 * n + i], ts[i], 0, 0};
+  const int r = root[i];
+  const long long len = (long long)rank[i] + 1, span = (long long)ping[i] - (long long)ping[r] + 1;
+  if (linkable(me) && len >= min_targets && span >= min_pings) flag_len[r] = 1, flag_len[n + r] = (int)len;
+}
+
+// ---- the track table ---------------------------------------------------------------------------------------------------
+struct TableArgs {
+  const int* chan;
+  const int* ping;
+  const double* range;
+  const double* ts;
+  const double* xyz;
+  const int* root;
+  const int* rank;
+  const int* flag_len;        // [2][n]
+  const long long* scans;     // [2][n]: inclusive scans of flag_len's rows
+  long long n, T, M;          // rows, tracks, rows in tracks
+  int* track_id;              // [n]
+  int* order;                 // [M]: the rows of track 1 in chain order, then of track 2, ...
+  int* start;                 // [T]: where a track's rows begin in order
+  int* icols;                 // [EPA_TRACK_ICOLS][T]
+  double* fcols;              // [EPA_TRACK_FCOLS][T]
+};
+
+__global__ __launch_bounds__(epa::kBlock) void order_kernel(TableArgs a) {
+  const long long i = (long long)blockIdx.x * epa::kBlock + threadIdx.x;
+  if (i >= a.n) return;
+  const int r = a.root[i];
+  int id = 0;
+  if (a.flag_len[r]) {
+    const long long t = a.scans[r], len = a.flag_len[a.n + r], at = a.scans[a.n + r] - len + a.rank[i];
+    if (t >= 1 && t <= a.T && at >= 0 && at < a.M) {  // (never false: the scans are of this flag_len)
+      id = (int)t;
+      a.order[at] = (int)i;
+      if (i == r) a.start[t - 1] = (int)(at), a.icols[1 * a.T + t - 1] = (int)len;
+    }
+  }
+  a.track_id[i] = id;
+}
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, kWave);
+  return x;
+}
+__device__ __forceinline__ double wave_max(double x) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    const double y = __shfl_xor(x, o, kWave);
+    x = y > x ? y : x;
+  }
+  return x;
+}
+
+// One wave per track.  Lane l adds the members l, l + 64, ... in chain order, then the 64 partial sums are added in
+// the fixed tree of wave_sum: an order set by the track's length alone.
+__global__ __launch_bounds__(epa::kBlock) void table_kernel(TableArgs a) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const long long t = (long long)blockIdx.x * (epa::kBlock / kWave) + threadIdx.x / kWave;
+  if (t >= a.T) return;  // (uniform over the wave)
+  const long long s0 = a.start[t];
+  long long len = a.icols[1 * a.T + t];
+  if (s0 < 0 || len < 1 || s0 + len > a.M) return;  // (never: written by order_kernel)
+  const int* mem = a.order + s0;
+  const long long n = a.n;
+  double lin = 0.0, top = -__builtin_inf(), rsum = 0.0, path = 0.0;
+  for (long long k = lane; k < len; k += kWave) {
+    const int m = mem[k];
+    lin += ::exp10(a.ts[m] / 10.0);
+    top = a.ts[m] > top ? a.ts[m] : top;
+    rsum += a.range[m];
+    if (k + 1 < len) {
+      const int m1 = mem[k + 1];
+      const double dx = a.xyz[m1] - a.xyz[m], dy = a.xyz[n + m1] - a.xyz[n + m], dz = a.xyz[2 * n + m1] - a.xyz[2 * n + m];
+      path += ::sqrt(dx * dx + dy * dy + dz * dz);
+    }
+  }
+  lin = wave_sum(lin), rsum = wave_sum(rsum), path = wave_sum(path), top = wave_max(top);
+  if (lane != 0) return;
+  const int f = mem[0], l = mem[len - 1];
+  int* ic = a.icols + t;
+  ic[0 * a.T] = a.chan[f], ic[2 * a.T] = a.ping[f], ic[3 * a.T] = a.ping[l], ic[4 * a.T] = f, ic[5 * a.T] = l;
+  const double xf = a.xyz[f], yf = a.xyz[n + f], zf = a.xyz[2 * n + f];
+  const double xl = a.xyz[l], yl = a.xyz[n + l], zl = a.xyz[2 * n + l];
+  const double dx = xl - xf, dy = yl - yf, dz = zl - zf, disp = ::sqrt(dx * dx + dy * dy + dz * dz);
+  double* fc = a.fcols + t;
+  fc[0 * a.T] = 10.0 * ::log10(lin / (double)len), fc[1 * a.T] = top, fc[2 * a.T] = rsum / (double)len;
+  fc[3 * a.T] = xf, fc[4 * a.T] = yf, fc[5 * a.T] = zf, fc[6 * a.T] = xl, fc[7 * a.T] = yl, fc[8 * a.T] = zl;
+  fc[9 * a.T] = path, fc[10 * a.T] = disp, fc[11 * a.T] = path / disp, fc[12 * a.T] = zl - zf;
+}
+
+int check_shape(const char* who, long long n, long long C, long long P) {
+  EPA_CHECK_ARG(n >= 0 && C >= 0 && P >= 0 && n < 0x7fffffffLL - epa::kBlock && C <= 65535 && P < 0x7fffffffLL,
+                "%s: bad shape n=%lld C=%lld P=%lld", who, n, C, P);
+  EPA_CHECK_ARG(C * P < 0x7fffffffLL - epa::kBlock, "%s: C*P=%lld segments", who, C * P);
+  return EPA_OK;
+}
+
+int blocks_for(long long items) { return (int)((items + epa::kBlock - 1) / epa::kBlock); }
+
+template <bool ACCEPT>
+int link(const char* who, const int* chan, const int* ping, const double* xyz, const double* ts,
+         long long n, long long C, long long P, const int* seg, const double* params, int* succ, int* pred, int* prop,
+         epa_stream_t stream) {
+  if (int rc = check_shape(who, n, C, P)) return rc;
+  EPA_CHECK_ARG(gates_ok(params), "%s: bad params", who);
+  if (n == 0 || C * P == 0) return EPA_OK;
+  EPA_CHECK_ARG(chan && ping && xyz && ts && seg && succ && pred && prop, "%s: NULL array argument", who);
+  LinkArgs a = {chan, ping, xyz, ts, n, C, P, seg, make_gates(params), succ, pred, prop};
+  const long long keys = C * P;
+  link_kernel<ACCEPT><<<(int)(keys < kMaxGrid ? keys : kMaxGrid), kLinkBlock, 0, (hipStream_t)stream>>>(a);
+  return EPA_OK;
+}
+
+}  // namespace
+
+extern "C" int epa_track_prepare(const int* channel_index, const int* ping_index, const double* range,
+                                 const double* along, const double* athw, long long n, long long C, long long P,
+                                 int* seg, double* xyz, int* succ, int* pred, int* bad, epa_stream_t stream) {
+  const char* who = "epa_track_prepare";
+  if (int rc = check_shape(who, n, C, P)) return rc;
+  EPA_CHECK_ARG(seg && bad, "%s: NULL output argument", who);
+  EPA_CHECK_ARG(n == 0 || (channel_index && ping_index && range && along && athw && xyz && succ && pred),
+                "%s: NULL array argument", who);
+  const long long items = n > C * P + 1 ? n : C * P + 1;
+  prepare_kernel<<<blocks_for(items), epa::kBlock, 0, (hipStream_t)stream>>>(channel_index, ping_index, range, along,
+                                                                            athw, n, C, P, seg, xyz, succ, pred, bad);
+  return epa::check_launch("track_prepare_kernel");
+}
+
+extern "C" int epa_track_propose(const int* channel_index, const int* ping_index, const double* xyz, const double* ts,
+                                 long long n, long long C, long long P, const int* seg, const double* params,
+                                 const int* succ, const int* pred, int* prop, epa_stream_t stream) {
+  if (int rc = link<false>("epa_track_propose", channel_index, ping_index, xyz, ts, n, C, P, seg, params,
+                           const_cast<int*>(succ), const_cast<int*>(pred), prop, stream))
+    return rc;
+  return (n == 0 || C * P == 0) ? EPA_OK : epa::check_launch("track_propose_kernel");
+}
+
+extern "C" int epa_track_accept(const int* channel_index, const int* ping_index, const double* xyz, const double* ts,
+                                long long n, long long C, long long P, const int* seg, const double* params,
+                                const int* prop, int* succ, int* pred, epa_stream_t stream) {
+  if (int rc = link<true>("epa_track_accept", channel_index, ping_index, xyz, ts, n, C, P, seg, params, succ, pred,
+                          const_cast<int*>(prop), stream))
+    return rc;
+  return (n == 0 || C * P == 0) ? EPA_OK : epa::check_launch("track_accept_kernel");
+}
+
+extern "C" int epa_track_roots(const int* pred, long long n, int passes, int* ptr_a, int* rank_a, int* ptr_b,
+                               int* rank_b, epa_stream_t stream) {
+  const char* who = "epa_track_roots";
+  EPA_CHECK_ARG(n >= 0 && n < 0x7fffffffLL - epa::kBlock && passes >= 1 && passes <= 32, "%s: n=%lld passes=%d", who, n,
+                passes);
+  if (n == 0) return EPA_OK;
+  EPA_CHECK_ARG(pred && ptr_a && rank_a && ptr_b && rank_b, "%s: NULL array argument", who);
+  hipStream_t st = (hipStream_t)stream;
+  // pass k writes the pair (k odd: b, k even: a) and reads the other
+  for (int k = 0; k < passes; ++k) {
+    int* po = (k & 1) ? ptr_b : ptr_a;
+    int* ro = (k & 1) ? rank_b : rank_a;
+    const int* pi = (k & 1) ? ptr_a : ptr_b;
+    const int* ri = (k & 1) ? rank_a : rank_b;
+    if (k == 0) roots_kernel<true><<<blocks_for(n), epa::kBlock, 0, st>>>(pred, nullptr, nullptr, po, ro, n);
+    else roots_kernel<false><<<blocks_for(n), epa::kBlock, 0, st>>>(pred, pi, ri, po, ro, n);
+    if (int rc = epa::check_launch("track_roots_kernel")) return rc;
+  }
+  return EPA_OK;
+}
+
+extern "C" int epa_track_chains(const int* ping_index, const double* xyz, const double* ts, const int* succ,
+                                const int* root, const int* rank, long long n, int min_targets, int min_pings,
+                                int* flag_len, epa_stream_t stream) {
+  const char* who = "epa_track_chains";
+  EPA_CHECK_ARG(n >= 0 && n < 0x7fffffffLL - epa::kBlock && min_targets >= 1 && min_pings >= 1,
+                "%s: n=%lld min_targets=%d min_pings=%d", who, n, min_targets, min_pings);
+  if (n == 0) return EPA_OK;
+  EPA_CHECK_ARG(ping_index && xyz && ts && succ && root && rank && flag_len, "%s: NULL array argument", who);
+  chains_kernel<<<blocks_for(n), epa::kBlock, 0, (hipStream_t)stream>>>(ping_index, xyz, ts, succ, root, rank, n,
+                                                                       min_targets, min_pings, flag_len);
+  return epa::check_launch("track_chains_kernel");
+}
+
+extern "C" int epa_track_table(const int* channel_index, const int* ping_index, const double* range, const double* ts,
+                               const double* xyz, const int* root, const int* rank, const int* flag_len,
+                               const long long* scans, long long n, long long T, long long M, int* track_id, int* order,
+                               int* start, int* icols, double* fcols, epa_stream_t stream) {
+  const char* who = "epa_track_table";
+  EPA_CHECK_ARG(n >= 1 && n < 0x7fffffffLL - epa::kBlock && T >= 1 && T <= M && M <= n, "%s: n=%lld T=%lld M=%lld", who,
+                n, T, M);
+  EPA_CHECK_ARG(channel_index && ping_index && range && ts && xyz && root && rank && flag_len && scans && track_id &&
+                    order && start && icols && fcols,
+                "%s: NULL array argument", who);
+  hipStream_t st = (hipStream_t)stream;
+  TableArgs a = {channel_index, ping_index, range, ts, xyz, root, rank, flag_len, scans, n, T, M, track_id, order, start,
+                 icols, fcols};
+  EPA_CHECK_HIP(hipMemsetAsync(start, 0xff, (size_t)T * sizeof(int), st));  // -1: a track the order pass never met
+  order_kernel<<<blocks_for(n), epa::kBlock, 0, st>>>(a);
+  if (int rc = epa::check_launch("track_order_kernel")) return rc;
+  const int per = epa::kBlock / kWave;
+  table_kernel<<<(int)((T + per - 1) / per), epa::kBlock, 0, st>>>(a);
+  return epa::check_launch("track_table_kernel");
+}

@@ -1106,6 +1106,102 @@ def single_target_emit(ts, along, athw, range, prm, limits, n_targets, offsets, 
     return icols, fcols
 
 
+# ---- target tracking (targets.track_targets) --------------------------------------------------------------------------
+TRACK_TILE = _lib.TRACK_TILE  # rows of a run a workgroup of propose / accept stages in LDS at a time (EPA_TRACK_TILE)
+
+
+def _track_params(params):
+    prm = np.ascontiguousarray(params, dtype=np.float64)
+    if prm.shape != (len(_lib.TRACK_PARAM_NAMES),):
+        raise ValueError(f"track: {len(_lib.TRACK_PARAM_NAMES)} params expected, got an array of shape {prm.shape}")
+    return prm
+
+
+def _track_columns(who, n, **cols):
+    for name, (t, dtype) in cols.items():
+        if t.dtype != dtype or t.shape[-1] != n or not t.is_cuda:
+            raise ValueError(f"{who}: {name} must be a device tensor of {dtype} with {n} rows, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+
+
+def track_prepare(channel_index, ping_index, range, along, athw, C, P):
+    """The first pass of the tracking over a table of n rows (int32 index columns, float64 ``range`` and angles) ->
+    (``seg`` int32 (C * P + 1,): the first row of every (channel, ping) segment, ``xyz`` float64 (3, n), ``succ`` and
+    ``pred`` int32 (n,) = -1, ``bad`` int32 (1,): 1 if the rows are not ordered by (channel, ping) or an index is outside
+    [0, C) x [0, P))."""
+    n = channel_index.numel()
+    _track_columns("track_prepare", n, channel_index=(channel_index, torch.int32), ping_index=(ping_index, torch.int32),
+                   range=(range, torch.float64), along=(along, torch.float64), athw=(athw, torch.float64))
+    dev = channel_index.device
+    seg = torch.empty(C * P + 1, dtype=torch.int32, device=dev)
+    xyz = torch.empty((3, n), dtype=torch.float64, device=dev)
+    succ = torch.empty(n, dtype=torch.int32, device=dev)
+    pred = torch.empty(n, dtype=torch.int32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    call("epa_track_prepare", _p(channel_index), _p(ping_index), _p(range), _p(along), _p(athw), n, C, P, _p(seg),
+         _p(xyz), _p(succ), _p(pred), _p(bad), _stream())
+    return seg, xyz, succ, pred, bad
+
+
+def track_link_round(channel_index, ping_index, xyz, ts, C, P, seg, params, succ, pred, prop):
+    """One propose / accept round, in place on ``succ`` and ``pred`` (``prop`` int32 (n,): the proposals of the round).
+    ``params``: the host numbers in the order of ``_lib.TRACK_PARAM_NAMES``."""
+    n = channel_index.numel()
+    _track_columns("track_link_round", n, channel_index=(channel_index, torch.int32),
+                   ping_index=(ping_index, torch.int32), xyz=(xyz, torch.float64), ts=(ts, torch.float64),
+                   succ=(succ, torch.int32), pred=(pred, torch.int32), prop=(prop, torch.int32))
+    if seg.dtype != torch.int32 or seg.numel() != C * P + 1:
+        raise ValueError(f"track_link_round: seg must be int32 of {C * P + 1} entries")
+    prm = _track_params(params)
+    head = (_p(channel_index), _p(ping_index), _p(xyz), _p(ts), n, C, P, _p(seg), prm.ctypes.data_as(ctypes.c_void_p))
+    call("epa_track_propose", *head, _p(succ), _p(pred), _p(prop), _stream())
+    call("epa_track_accept", *head, _p(prop), _p(succ), _p(pred), _stream())
+
+
+def track_roots(pred, passes):
+    """``passes`` passes of pointer doubling over ``pred`` -> (``root``, ``rank``) int32 (n,): the first row of every
+    row's chain and the row's position in it (chains of up to ``2 ** passes`` rows)."""
+    n = pred.numel()
+    _track_columns("track_roots", n, pred=(pred, torch.int32))
+    bufs = torch.empty((4, n), dtype=torch.int32, device=pred.device)
+    call("epa_track_roots", _p(pred), n, int(passes), _p(bufs[0]), _p(bufs[1]), _p(bufs[2]), _p(bufs[3]), _stream())
+    return (bufs[0], bufs[1]) if passes % 2 == 1 else (bufs[2], bufs[3])
+
+
+def track_chains(ping_index, xyz, ts, succ, root, rank, min_targets, min_pings):
+    """-> ``flag_len`` int32 (2, n): at the first row of every chain that is a track, 1 and the number of its rows."""
+    n = ping_index.numel()
+    _track_columns("track_chains", n, ping_index=(ping_index, torch.int32), xyz=(xyz, torch.float64),
+                   ts=(ts, torch.float64), succ=(succ, torch.int32), root=(root, torch.int32), rank=(rank, torch.int32))
+    flag_len = torch.zeros((2, n), dtype=torch.int32, device=ping_index.device)
+    call("epa_track_chains", _p(ping_index), _p(xyz), _p(ts), _p(succ), _p(root), _p(rank), n, int(min_targets),
+         int(min_pings), _p(flag_len), _stream())
+    return flag_len
+
+
+def track_table(channel_index, ping_index, range, ts, xyz, root, rank, flag_len, scans, T, M):
+    """The track table: ``scans`` int64 (2, n) the inclusive scans of ``flag_len``'s rows, ``T >= 1`` and ``M`` their
+    totals -> (``track_id`` int32 (n,), int32 (6, T), float64 (13, T)): the columns ``_lib.TRACK_ICOL_NAMES`` and
+    ``_lib.TRACK_FCOL_NAMES``."""
+    n = channel_index.numel()
+    _track_columns("track_table", n, channel_index=(channel_index, torch.int32), ping_index=(ping_index, torch.int32),
+                   range=(range, torch.float64), ts=(ts, torch.float64), xyz=(xyz, torch.float64),
+                   root=(root, torch.int32), rank=(rank, torch.int32), flag_len=(flag_len, torch.int32),
+                   scans=(scans, torch.int64))
+    T, M = int(T), int(M)
+    if not 1 <= T <= M <= n:
+        raise ValueError(f"track_table: 1 <= T <= M <= n expected, got T={T} M={M} n={n}")
+    dev = channel_index.device
+    track_id = torch.empty(n, dtype=torch.int32, device=dev)
+    order = torch.zeros(M, dtype=torch.int32, device=dev)  # (every entry is written; never a stray row number)
+    start = torch.empty(T, dtype=torch.int32, device=dev)
+    icols = torch.empty((len(_lib.TRACK_ICOL_NAMES), T), dtype=torch.int32, device=dev)
+    fcols = torch.empty((len(_lib.TRACK_FCOL_NAMES), T), dtype=torch.float64, device=dev)
+    call("epa_track_table", _p(channel_index), _p(ping_index), _p(range), _p(ts), _p(xyz), _p(root), _p(rank),
+         _p(flag_len), _p(scans), n, T, M, _p(track_id), _p(order), _p(start), _p(icols), _p(fcols), _stream())
+    return track_id, icols, fcols
+
+
 # ---- transient-noise detectors (clean.detect_transient) --------------------------------------------------------------
 def transient_fielding(sv, chan, n, thr0, thr1, maxts):
     """Fielding's transient-noise mask of a (C, P, S) cube -> bool (C, P, S), True = valid.  ``chan``: host int (C, 4)

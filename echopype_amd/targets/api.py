@@ -294,7 +294,8 @@ def detect_single_targets(ds, method, params, echodata=None, *, device=None):
     counts ``n_targets`` (channel, ping_time) int32, ``n_candidates`` (channel) and ``n_rejected`` (channel, rule)
     over the four rules.  ``channel_index`` counts along the result's ``channel`` coordinate (the selected channels).
     No pings, no samples, or nothing detected gives the same variables with ``target`` of length 0.  The order is
-    fully defined and no sum depends on scheduling: two calls give identical tables.
+    fully defined and no sum depends on scheduling: two calls give identical tables.  ``track_targets`` groups the rows
+    of this table into fish tracks.
 
     Device work and the one host synchronisation: see the module."""
     ds = from_xarray(ds)

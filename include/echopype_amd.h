@@ -1116,6 +1116,54 @@ int epa_single_target_emit(const void* ts, const void* along, const void* athw, 
                            const double* prm, const double* limits, const int* n_targets, const long long* offsets,
                            long long N, int* icols, double* fcols, epa_stream_t stream);
 
+/* ---- target tracking: targets.track_targets (targets/track.py) -------------------------------------------------------
+ * The single targets of one fish over consecutive pings grouped into tracks by gated nearest-neighbour linking in a fixed
+ * number of propose / accept rounds; targets/track.py states the five rules.  The table has n rows ordered by
+ * (channel_index, ping_index), i32 columns; range, along, athw, ts f64 [n].  All arithmetic is f64.  Every entry is
+ * memory-safe on any content of the index columns; what it computes for a table that prepare finds bad is unspecified.
+ * params: HOST f64 [EPA_TRACK_PARAMS] = gate_alongship, gate_athwartship, gate_range, max_ping_gap,
+ * missed_ping_expansion, weight_alongship, weight_athwartship, weight_range, weight_TS, weight_ping_gap,
+ * max_TS_difference (0: no TS gate).  n == 0 launches nothing, except in prepare.
+ *
+ * prepare: seg i32 [C*P + 1]: the first row whose (channel, ping) is not below the segment's; xyz f64 [3][n] (rule 1);
+ * succ, pred i32 [n] set to -1; bad i32 [1], zeroed by the caller, set to 1 if a row's indices are outside [0, C) x [0, P)
+ * or the rows are not ordered. */
+#define EPA_TRACK_TILE 128   /* rows of a run a workgroup of propose / accept stages in LDS at a time */
+#define EPA_TRACK_PARAMS 11
+#define EPA_TRACK_ICOLS 6    /* channel_index, n_targets, ping_first, ping_last, target_first, target_last */
+#define EPA_TRACK_FCOLS 13   /* TS_mean, TS_max, range_mean, x_first, y_first, z_first, x_last, y_last, z_last,
+                              * path_length, displacement, tortuosity, delta_range */
+int epa_track_prepare(const int* channel_index, const int* ping_index, const double* range, const double* along,
+                      const double* athw, long long n, long long C, long long P, int* seg, double* xyz, int* succ,
+                      int* pred, int* bad, epa_stream_t stream);
+/* propose: prop i32 [n] of every row: the gated row without a predecessor that minimises (cost, row) among the rows of
+ * the next 1 + max_ping_gap pings of its channel, -1 if there is none, the row has a successor or holds a NaN. */
+int epa_track_propose(const int* channel_index, const int* ping_index, const double* xyz, const double* ts, long long n,
+                      long long C, long long P, const int* seg, const double* params, const int* succ, const int* pred,
+                      int* prop, epa_stream_t stream);
+/* accept: every row without a predecessor takes, among the rows whose prop names it, the one minimising (cost, row):
+ * pred of the row and succ of the taken row are set. */
+int epa_track_accept(const int* channel_index, const int* ping_index, const double* xyz, const double* ts, long long n,
+                     long long C, long long P, const int* seg, const double* params, const int* prop, int* succ,
+                     int* pred, epa_stream_t stream);
+/* roots: `passes` (1 .. 32) passes of pointer doubling over pred, one launch each; a chain of up to 2**passes rows is
+ * resolved.  The pairs (ptr_a, rank_a) and (ptr_b, rank_b), i32 [n] each, are written in turn, a first: the last pass
+ * leaves the first row of every row's chain and the row's position in it in a if passes is odd, in b if it is even. */
+int epa_track_roots(const int* pred, long long n, int passes, int* ptr_a, int* rank_a, int* ptr_b, int* rank_b,
+                    epa_stream_t stream);
+/* chains: flag_len i32 [2][n], zeroed by the caller: [0][r] = 1 and [1][r] = the number of rows, at the first row r of
+ * every chain that is a track (rule 5; a row holding a NaN is none). */
+int epa_track_chains(const int* ping_index, const double* xyz, const double* ts, const int* succ, const int* root,
+                     const int* rank, long long n, int min_targets, int min_pings, int* flag_len, epa_stream_t stream);
+/* table: scans i64 [2][n] the inclusive scans of flag_len's two rows, T >= 1 and M their totals.  track_id i32 [n];
+ * order i32 [M]: the rows of track 1 in chain order, then those of track 2, ...; start i32 [T]: where a track begins in
+ * order; icols i32 [EPA_TRACK_ICOLS][T], fcols f64 [EPA_TRACK_FCOLS][T].  One wave per track: lane l adds the rows
+ * l, l + 64, ... of the track in chain order, and the 64 partial sums are added in a fixed tree. */
+int epa_track_table(const int* channel_index, const int* ping_index, const double* range, const double* ts,
+                    const double* xyz, const int* root, const int* rank, const int* flag_len, const long long* scans,
+                    long long n, long long T, long long M, int* track_id, int* order, int* start, int* icols,
+                    double* fcols, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
