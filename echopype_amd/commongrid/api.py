@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
-from ..device_view import as_tensor, broadcast_to_dims
+from ..device_view import as_tensor, broadcast_to_dims, resolve_device, strided_view
 from ..utils.prov import echopype_prov_attrs, insert_processing_level
 from ..xr_lite import DataArray, Dataset, DeviceArray, LazyDeviceArray, defer_mvbs_enabled, from_xarray, xarray_io
 from .deferred import (CPS, deferred_mvbs, launch_or_decline, n_range_bins, nan_coordinate_warning, range_cap, range_edges,
@@ -406,6 +406,136 @@ def _assemble_mvbs(ds_Sv, mvbs_t, dim_0, ping_time, e0, dt, n_t, r_edges, range_
     if "channel" in ds_Sv and dim_0 != "channel":
         ds_MVBS["channel"] = ds_Sv["channel"]
     return insert_processing_level(ds_MVBS, "L3*", input_ds=ds_Sv)
+
+
+_REGRID_DIMS = ("channel", "ping_time", "range_sample")
+_REGRID_CELLS = ("a sample stands for the interval between the midpoints of its range and its neighbours' (the outer two "
+                 "mirrored); a cell holds 10 log10 of the overlap-weighted mean of 10^(Sv/10) over the samples that reach "
+                 "into it, NaN samples left out; coverage is the share of the cell those overlaps fill")
+
+
+def _largest_range(rng, range_var):
+    """The largest value of the range variable, NaN skipped: the by-product of the kernel that wrote the array, else one
+    reduction on the device -- one host wait either way, as in compute_MVBS; host data are reduced on the host."""
+    d = rng.data
+    if isinstance(d, DeviceArray):
+        t = d.tensor
+        if t.dtype in (torch.float32, torch.float64) and t.is_contiguous():
+            hi = _range_stats(rng, None)[1]
+        else:
+            hi = ops.nanminmax(t.double().contiguous())[1]
+    else:
+        a = np.asarray(d, dtype=np.float64)
+        hi = float(np.nanmax(a)) if a.size and not np.isnan(a).all() else float("nan")
+    if hi == float("inf"):
+        raise ValueError(f"the largest value of {range_var} is not finite: give range_var_max")
+    if not np.isfinite(hi):
+        raise ValueError("range bins are empty: the range variable holds no valid values")
+    return hi
+
+
+@xarray_io()
+def regrid_Sv(ds_Sv, range_var="echo_range", range_bin="0.2m", range_var_max=None, with_coverage=True, *, device=None):
+    """``ds_Sv["Sv"]`` resampled along range onto ONE grid shared by all channels and pings, in the linear domain, with
+    the integrated backscatter kept: what ``mask.frequency_differencing``, ``mask.detect_shoal`` or ``mask.apply_mask``
+    need when channels (or, after ``combine_echodata``, pings) have different sample intervals, so that index ``s`` is
+    another range in each.  Pings are not touched.  (No counterpart in the reference, whose ``commongrid.regrid`` is a
+    stub; the rule is restated in NumPy in ``tests/regrid_ref.py``.)
+
+    The grid is compute_MVBS's: edges ``e = np.arange(0, rmax + range_bin, range_bin)``, ``rmax`` from ``range_var_max``
+    (a string such as ``"250m"``, plus 1e-8 as there) or the largest value of ``ds_Sv[range_var]``; ``J = len(e) - 1`` cells
+    (0: an empty range axis), the output coordinate ``range_var`` holds their left edges.
+
+    One row (channel, ping), ``r`` its range in float64 and ``v`` its Sv: ``n`` is the length of the leading run of
+    finite ``r`` (samples behind it, the NaN tail of a padded row, are ignored).  Sample ``i`` stands for the interval
+    ``[m[i], m[i+1])`` with ``m[i] = (r[i-1] + r[i]) / 2``, ``m[0] = r[0] - (r[1] - r[0]) / 2`` and ``m[n] = r[n-1] +
+    (r[n-1] - r[n-2]) / 2``; repeated ranges give intervals of zero width, which contribute nothing.  With ``o_ij`` the
+    length sample ``i`` shares with cell ``j``, ``W_j = sum o_ij`` and ``N_j = sum o_ij 10^(v_i/10)`` over the samples
+    whose ``v`` is not NaN: ``Sv_j = 10 log10(N_j / W_j)`` where ``W_j > 0``, else NaN, and ``coverage_j = W_j /
+    range_bin``.  ``-inf`` is a sample of linear value 0, ``+inf`` gives ``+inf``.  A row with ``n < 2`` or whose
+    ``r[:n]`` decreases somewhere is all NaN with coverage 0 and is counted in ``n_rows_unordered``.  All arithmetic is
+    float64, rounded once to the type of ``Sv`` (float32 or float64; other types are converted to float64 first).  For
+    every row ``sum_j 10^(Sv_j/10) coverage_j range_bin`` equals the integral of the samples over the grid.
+
+    ``ds_Sv["Sv"]`` has the dimensions ``(channel, ping_time, range_sample)`` (another order: ``NotImplementedError``),
+    on the host or the device; ``ds_Sv[range_var]`` (``echo_range`` or ``depth``) any subset of them that includes
+    ``range_sample``, of any real type.  Sharded datasets are not supported.
+
+    Returns a Dataset with ``Sv`` over ``(channel, ping_time, range_var)`` on the device, ``coverage`` of the same shape
+    and type (``with_coverage=False``: not written), ``n_rows_unordered`` (a 0-d int32 on the device, not read here), the
+    coordinates ``channel``, ``ping_time`` and ``range_var``, and every variable of ``ds_Sv`` without ``range_sample``.
+    It goes straight into ``mask.frequency_differencing`` and ``mask.apply_mask``; ``mask.detect_shoal`` works along a
+    dimension called ``range_sample`` and takes the ``Sv`` array under that name.
+
+    Device work: one launch (``epa_regrid_rows``), a workgroup per row; every output element is written exactly once.
+    A range array is read where it lies, a lower-dimensional one through zero strides.  A deferred ``Sv`` and a lazy
+    ``echo_range`` / ``depth`` are written first, as for any other reader: evaluating the range from its coefficient
+    rows inside the kernel, and a float32 path for the exponential, are not built.  Host synchronisations: none with
+    ``range_var_max``, else one (the largest range)."""
+    ds_Sv = from_xarray(ds_Sv)
+    if not isinstance(range_var, str):
+        raise TypeError("The input range_var must be a string!")
+    if "Sv" not in ds_Sv.variables:
+        raise ValueError("Input Sv dataset must contain all of the following variables: {'Sv'}")
+    ds_Sv, range_bin_m = _setup_and_validate(ds_Sv, range_var, range_bin)
+    if not range_bin_m > 0:
+        raise ValueError(f"range_bin must be positive, got {range_bin!r}")
+    r_cap = range_cap(range_var_max, None)  # (TypeError / ValueError of a bad range_var_max)
+    sv_da, rng = ds_Sv["Sv"], ds_Sv[range_var]
+    order = tuple(sv_da.dims)
+    if order != _REGRID_DIMS:
+        raise NotImplementedError(f"the dimensions of Sv must be {_REGRID_DIMS}, got {order}")
+    sizes = dict(zip(order, sv_da.shape))
+    rdims = tuple(rng.dims)
+    if len(set(rdims)) != len(rdims) or not set(rdims) <= set(order) or "range_sample" not in rdims:
+        raise ValueError(f"The dimensions of {range_var}, {rdims}, must be among those of Sv, {order}, and include "
+                         "'range_sample'.")
+    if any(n != sizes[d] for d, n in zip(rdims, rng.shape)):
+        raise ValueError(f"The shape of {range_var}, {dict(zip(rdims, rng.shape))}, does not match Sv, {sizes}.")
+    for name, da in (("Sv", sv_da), (range_var, rng)):
+        if not isinstance(da.data, DeviceArray) and np.asarray(da.data).dtype.kind not in "fiu":
+            raise TypeError(f"{name} must hold real numbers, got {np.asarray(da.data).dtype}")
+
+    if isinstance(sv_da.data, DeviceArray):
+        sv_t = sv_da.data.tensor  # (a deferred Sv is written here)
+        dev = sv_t.device
+    else:
+        dev = rng.data.tensor.device if isinstance(rng.data, DeviceArray) else resolve_device(device)
+        sv_t = as_tensor(sv_da, device=dev)
+    if sv_t.dtype not in (torch.float32, torch.float64):
+        sv_t = sv_t.double()
+    sv_t = sv_t.contiguous()
+    rmax = r_cap if r_cap is not None else _largest_range(rng, range_var)
+    r_edges = range_edges(rmax, range_bin_m)
+    n_r = len(r_edges) - 1
+    r_t = strided_view(rng, order, dev)
+    if r_t.device != dev:
+        r_t = r_t.to(dev)
+    sv_rg, cov, n_bad = ops.regrid_rows(sv_t, r_t, range_bin_m, n_r, with_coverage=bool(with_coverage))
+
+    out = Dataset(coords={"channel": ds_Sv["channel"], "ping_time": ds_Sv["ping_time"], range_var: r_edges[:-1]})
+    out.coords[range_var].attrs = {"long_name": "Range distance", "units": "m"}
+    dims = ("channel", "ping_time", range_var)
+    out["Sv"] = DataArray(DeviceArray(sv_rg), dims, attrs={
+        "long_name": "Volume backscattering strength (Sv re 1 m-1)", "units": "dB",
+        "cell_methods": f"{range_var}: mean (interval: {range_bin_m} meter comment: {range_var} is the interval start)",
+        "binning_mode": "physical units", "range_meter_interval": str(range_bin_m) + "m"})
+    if cov is not None:
+        out["coverage"] = DataArray(DeviceArray(cov), dims, attrs={
+            "long_name": "Share of the cell that samples with a valid Sv fill", "units": "1"})
+    out["n_rows_unordered"] = DataArray(DeviceArray(n_bad.reshape(())), (), attrs={
+        "long_name": "Rows left NaN: fewer than two leading finite ranges, or ranges that decrease"})
+    for k, c in ds_Sv.coords.items():
+        if k not in out.coords and k != range_var and "range_sample" not in c.dims:
+            out.coords[k] = c
+    for k in ds_Sv.data_vars:
+        v = ds_Sv[k]
+        if k not in ("Sv", range_var) and "range_sample" not in v.dims:
+            out[k] = v
+    prov = echopype_prov_attrs(process_type="processing")
+    prov["processing_function"] = "commongrid.regrid_Sv"
+    out = out.assign_attrs({**prov, "range_var": range_var, "range_bin": range_bin, "regrid_cell_definition": _REGRID_CELLS})
+    return insert_processing_level(out, "L3*", input_ds=ds_Sv)
 
 
 @xarray_io()

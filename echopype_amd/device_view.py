@@ -61,6 +61,27 @@ def device_view(var, order, *, device=None, index=None, dtype=None, floating=Fal
     return ops.to_device(a, dtype=dtype, device=dev)
 
 
+def strided_view(var, order, device=None):
+    """The data of ``var`` as a float32 / float64 device tensor with one axis per dimension of ``order``, for a kernel
+    that reads it through its strides: the array where it lies (a device array is neither moved nor copied, host data
+    are uploaded once; anything but float32 / float64 becomes float64), its dimensions permuted into the sequence of
+    ``order`` (a view), an axis of length 1 for every dimension ``var`` lacks.  Nothing is expanded."""
+    dims = tuple(var.dims)
+    d = var.data
+    if isinstance(d, DeviceArray):
+        t = d.tensor
+    else:
+        a = np.asarray(d)
+        t = ops.to_device(a if a.dtype in _FLOAT_NP else a.astype(np.float64), device=device).reshape(a.shape)
+    if t.dtype not in _FLOAT_T:
+        t = t.double()
+    t = t.permute([dims.index(x) for x in order if x in dims])
+    for i, x in enumerate(order):
+        if x not in dims:
+            t = t.unsqueeze(i)
+    return t
+
+
 def channel_position(labels, channel):
     """Position of ``channel`` among the channel ``labels``, compared by their ``str()``: ``sel(channel=channel)``."""
     chans = [str(c) for c in np.asarray(getattr(labels, "values", labels)).reshape(-1)]

@@ -249,6 +249,9 @@ def frequency_differencing(source_Sv, storage_options={}, freqABEq=None, chanABE
     is converted to that type before the comparison (float32 data is compared in float32; anything but float32 /
     float64 is converted to float64 first).  NaN in either channel, and inf - inf, give False for every operator.
 
+    The two channels are compared element by element along the last dimension: where their sample intervals differ,
+    index ``s`` is another range in each, and ``commongrid.regrid_Sv`` brings them onto one range grid first.
+
     Returns the DataArray ``mask`` over the dimensions of ``Sv`` without ``channel``, with the coordinates of ``Sv``
     that do not carry ``channel`` and the reference's attributes ``mask_type`` and ``history``.  Its data stays on the
     device (a ``torch.bool`` tensor) and goes straight into ``mask.apply_mask``.
@@ -457,7 +460,7 @@ def regrid_mask(mask_da, range_da, range_bin="20m", ping_time_bin="20s", third_d
 # ---- the samples between two lines (no counterpart in the reference: there it is ``ds["depth"] < bottom``) -------------
 from numbers import Real  # noqa: E402
 
-from ..device_view import resolve_device  # noqa: E402
+from ..device_view import resolve_device, strided_view  # noqa: E402
 from ..xr_lite import LazyDeviceArray  # noqa: E402
 
 _LINE_DIMS = ("channel", "ping_time")
@@ -621,19 +624,8 @@ def line_mask(ds, upper=None, lower=None, range_var="depth", var_name="Sv", clos
         out = ops.line_mask((C, P, S), coef=rows, nan_raw=raw, scale=scale, offset=offset,
                             dtype=torch.float64 if rng.data.dtype == np.dtype("float64") else torch.float32, **kw)
     else:
-        if is_device(rng.data):
-            r_t = rng.data.tensor
-        else:
-            a = np.asarray(rng.data)
-            r_t = ops.to_device(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64),
-                                device=dev).reshape(a.shape)
-        if r_t.dtype not in (torch.float32, torch.float64):
-            r_t = r_t.double()
         # the dimensions in the order of the cube (a view), a broadcast axis of length 1 for those the range lacks
-        r_t = r_t.permute([rdims.index(d) for d in order if d in rdims])
-        for i, d in enumerate(order):
-            if d not in rdims:
-                r_t = r_t.unsqueeze(i)
+        r_t = strided_view(rng, order, dev)
         out = ops.line_mask((C, P, S), range=r_t if has_chan else r_t.unsqueeze(0), **kw)
     if not has_chan:
         out = out[0]

@@ -1358,6 +1358,45 @@ def line_mask(shape, *, range=None, coef=None, nan_raw=None, scale=None, offset=
     return out
 
 
+# ---- Sv onto one range grid, the echo integral kept (commongrid.regrid_Sv) ----------------------------------------------
+def regrid_rows(sv, range, range_bin, n_rbins, *, with_coverage=True, out=None, _max_grid=0):
+    """Every row of ``sv`` (C, P, S), float32 / float64, onto the cells ``[j * range_bin, (j + 1) * range_bin)``,
+    ``j < n_rbins`` -> (Sv (C, P, n_rbins) of sv's dtype, coverage of the same shape and type or None, int32 (1,) device
+    tensor: the rows refused because fewer than two leading ranges are finite or they decrease) (``epa_regrid_rows``: one
+    launch, every output element written exactly once; the rule is in the header).  ``range``: a float32 / float64
+    device tensor, of sv's dtype or not, of sv's shape or broadcasting to it (read through its strides: nothing is
+    copied).  ``out``: the (Sv, coverage) tensors to write into instead of new ones, coverage None without
+    ``with_coverage`` (tests: a pre-filled allocation shows that every element is written).  ``_max_grid``: the most
+    workgroups to launch (tests: the row loop at small shapes)."""
+    if sv.dim() != 3 or sv.dtype not in _DT:
+        raise ValueError(f"regrid_rows: sv must be float32 / float64 of shape (C, P, S), got {sv.dtype} {tuple(sv.shape)}")
+    C, P, S = sv.shape
+    dev, n_rbins = sv.device, int(n_rbins)
+    if range.dtype not in _DT or not range.is_cuda or range.device != dev:
+        raise ValueError(f"regrid_rows: range must be a float32 / float64 tensor on {dev}, got {range.dtype} on {range.device}")
+    try:
+        rv = range.expand(C, P, S)
+    except RuntimeError:
+        raise ValueError(f"regrid_rows: range of shape {tuple(range.shape)} does not broadcast to {(C, P, S)}") from None
+    if n_rbins < 0:
+        raise ValueError(f"regrid_rows: n_rbins must not be negative, got {n_rbins}")
+    shape = (C, P, n_rbins)
+    if out is None:
+        sv_out = torch.empty(shape, dtype=sv.dtype, device=dev)
+        cov = torch.empty(shape, dtype=sv.dtype, device=dev) if with_coverage else None
+    else:
+        sv_out, cov = out
+        for t, wanted in ((sv_out, True), (cov, bool(with_coverage))):
+            if (t is not None) != wanted or (t is not None and (t.dtype != sv.dtype or tuple(t.shape) != shape
+                                                                 or t.device != dev or not t.is_contiguous())):
+                raise ValueError(f"regrid_rows: out must hold contiguous {shape} tensors of {sv.dtype} on {dev}, the second "
+                                 "None without with_coverage")
+    n_unordered = torch.empty(1, dtype=torch.int32, device=dev)
+    call("epa_regrid_rows", _p(sv), _DT[sv.dtype], ctypes.c_void_p(rv.data_ptr()), _DT[range.dtype], *rv.stride(), C, P, S,
+         float(range_bin), n_rbins, _p(sv_out), _p(cov), _p(n_unordered), int(_max_grid), _stream())
+    return sv_out, cov, n_unordered
+
+
 # ---- echo summary statistics per row (metrics.*) ------------------------------------------------------------------------
 METRICS =("abundance", "center_of_mass", "dispersion", "evenness", "aggregation")
 

@@ -920,6 +920,35 @@ int epa_line_mask(const void* range, long long range_stride_c, long long range_s
                   const double* lower, long long lower_stride_c, long long lower_stride_p, double lower_offset,
                   unsigned flags, int C, int P, int S, uint8_t* out, epa_stream_t stream);
 
+/* ---- commongrid.regrid_Sv: Sv onto one range grid, the echo integral kept ------------------------------------------------
+ * Every row (c, p) of sv [C*P*S] (dtype F32 / F64, contiguous) is resampled onto the cells [j*range_bin, (j+1)*range_bin),
+ * j = 0 .. n_rbins-1 (the edges of np.arange(0, max + bin, bin): compute_MVBS's grid).  For one row, with r the range
+ * promoted to float64 (F32 promotes exactly) and v its Sv:
+ *   n    = the length of the leading run of finite r (S if all are); samples behind it are ignored
+ *   the row is REFUSED if n < 2 or r[0..n) decreases somewhere: its outputs are NaN / coverage 0, and it is counted
+ *   m[i] = (r[i-1] + r[i]) / 2 for 0 < i < n, m[0] = r[0] - (r[1] - r[0]) / 2, m[n] = r[n-1] + (r[n-1] - r[n-2]) / 2:
+ *          sample i stands for [m[i], m[i+1]); a cell of zero width contributes nothing
+ *   o_ij = max(0, min(m[i+1], e[j+1]) - max(m[i], e[j])),  W_j = sum_i o_ij,  N_j = sum_i o_ij * 10^(v_i / 10), over the
+ *          i < n with v_i not NaN and o_ij > 0, in ascending i (-inf is a sample of linear value 0, +inf gives +inf)
+ *   sv_out[row*n_rbins + j] = 10 log10(N_j / W_j) where W_j > 0, else NaN;  coverage_out[...] = W_j / (e[j+1] - e[j])
+ * All of it in float64, the two outputs rounded once to dtype.  One kernel launch, a workgroup per row, rows longer than
+ * EPA_REGRID_TILE samples in tiles of that length; no scratch.  Every element of sv_out and (if given) coverage_out is
+ * stored exactly once, nothing is pre-filled; n_unordered_out is set to 0 by a 4-byte memset in front of the launch.
+ *   range : of range_dtype (F32 / F64, need not be dtype), element (c, p, s) at [c*range_stride_c + p*range_stride_p +
+ *            s*range_stride_s] in elements, a stride of 0 broadcasts: (S,), (C, S) and (C, P, S) ranges are read where
+ *            they lie
+ *   coverage_out : of dtype [C*P*n_rbins], or NULL: not written
+ *   n_unordered_out : i32 [1] on the device, the number of refused rows (also with n_rbins == 0)
+ *   max_grid : the most workgroups to launch, 0: the library's choice (tests: the row loop at small shapes)
+ * EPA_EINVAL (nothing is launched): a bad dtype; C, P or S negative; S or n_rbins above 2^30; range_bin not positive and
+ * finite; a negative stride or max_grid; n_unordered_out NULL; sv or range NULL with C*P*S > 0; sv_out NULL with
+ * C*P*n_rbins > 0. */
+#define EPA_REGRID_TILE 2048 /* source samples of a row that lie in LDS at a time */
+int epa_regrid_rows(const void* sv, int dtype, const void* range, int range_dtype, long long range_stride_c,
+                    long long range_stride_p, long long range_stride_s, int C, int P, int S, double range_bin,
+                    int n_rbins, void* sv_out, void* coverage_out, int32_t* n_unordered_out, int max_grid,
+                    epa_stream_t stream);
+
 /* ---- echo summary statistics per row: metrics.abundance / center_of_mass / dispersion / evenness / aggregation --------
  * (metrics/summary_statistics.py).  sv [R*S] and range of dtype F32 / F64; range is [R*S] when range_per_row != 0,
  * else [S], shared by all rows.  For j = 1 .. S-1: dz_j = range_j - range_{j-1} rounded in dtype, 0 -> NaN;
