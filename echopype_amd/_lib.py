@@ -34,6 +34,10 @@ CMP_GT, CMP_LT, CMP_LE, CMP_GE, CMP_EQ = range(5)  # enum epa_cmp
 ALIGN_LINEAR, ALIGN_NEAREST = 0, 1  # epa_align_to_ping_time mode
 LINE_CLOSED_RIGHT, LINE_NAN_IGNORE = 1, 2  # EPA_LINE_*: the flags of epa_line_mask
 REGRID_TILE = 2048  # EPA_REGRID_TILE: source samples of a row that epa_regrid_rows keeps in LDS at a time
+WINDOW_MEDIAN, WINDOW_MEAN, WINDOW_MIN, WINDOW_MAX = range(4)  # enum epa_window_method
+WINDOW_METHODS = ("median", "mean", "min", "max")  # ... by name, in its order
+WINDOW_FILTER_MAX = 15  # EPA_WINDOW_FILTER_MAX: the largest window size along either axis
+WINDOW_FILTER_TP, WINDOW_FILTER_TS = 16, 64  # EPA_WINDOW_FILTER_TP, _TS: the pings x samples of a workgroup's tile
 QC_FACTS = 4  # EPA_QC_FACTS
 QC_FIRST, QC_COUNT, QC_NAT, QC_SLOTS = range(4)  # the words of the facts
 QC_MAX_WIN = 1024  # EPA_QC_MAX_WIN
@@ -199,6 +203,7 @@ SIGNATURES = {
     "epa_line_mask": [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _i, _vp, _ll, _ll, _d, _vp, _ll, _ll, _d, _u, _i, _i, _i, _vp,
                       _vp],
     "epa_regrid_rows": [_vp, _i, _vp, _i, _ll, _ll, _ll, _i, _i, _i, _d, _i, _vp, _vp, _vp, _i, _vp],
+    "epa_window_filter": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "epa_echo_metrics": [_vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "epa_align_to_ping_time": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp],
     "epa_time_reversals": [_vp, _ll, _vp, _vp, _vp],

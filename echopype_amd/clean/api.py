@@ -421,6 +421,62 @@ def detect_transient(ds, method, params):
     return METHODS_TRANSIENT[method](ds, **params)
 
 
+# ---- 2-D window operators on Sv (not in the reference: Echoview's median, convolution, erosion and dilation) ------------
+@xarray_io()
+def window_filter(ds_Sv, method="median", ping_num=3, range_sample_num=3, var_name="Sv", min_valid=1, keep_nan=True):
+    """``ds_Sv[var_name]`` with every sample replaced by the ``method`` of the ``ping_num x range_sample_num`` samples
+    around it, on the device: the median in front of ``mask.detect_shoal`` (single-sample spikes neither seed nor bridge
+    regions), the linear-domain mean in front of ``mask.frequency_differencing``, a ``"min"`` followed by a ``"max"`` (an
+    opening) against speckle.  (No counterpart in the reference; the rule is restated in NumPy in
+    ``tests/window_filter_ref.py``.)
+
+    THE RULE.  The variable is float32 or float64 over ``(..., ping_time, range_sample)`` with at most one leading
+    dimension (``channel``).  Both sizes are odd and between 1 and 15; ``hp = ping_num // 2``, ``hs = range_sample_num //
+    2``.  The window of ``(p, s)`` is pings ``p-hp .. p+hp`` and samples ``s-hs .. s+hs`` clipped to the array: it
+    shrinks at the edges (no reflection, no padding value), and a window never crosses channels.  The VALID values of a
+    window are its non-NaN values; ``-inf`` and ``+inf`` are values, ordered as usual, in every method.
+
+    * ``"median"``: the median of the valid values.  An odd count gives one of the inputs, bit for bit.  An even count
+      gives ``10 log10((10^(a/10) + 10^(b/10)) / 2)`` of the two middle values ``a <= b`` -- the linear-domain convention
+      of the noise masks -- and ``a`` itself when ``a == b``.
+    * ``"mean"``: ``10 log10(mean(10^(v/10)))`` over the valid values; ``-inf`` if all are ``-inf``, ``+inf`` if any is.
+    * ``"min"``, ``"max"``: the smallest / largest valid value, an input bit for bit (erosion / dilation of Sv).
+
+    ``min_valid`` (1 .. ``ping_num * range_sample_num``): a window with fewer valid values gives NaN.  ``keep_nan``: a
+    sample that is NaN stays NaN whatever its neighbours hold -- what ``apply_mask``, a seafloor line or the NaN pad of a
+    short ping removed is not filled in again; with ``False`` such a sample gets its window's result.  Arithmetic that is
+    not a selection is float64 for both types, rounded once; the output has the input's dtype and shape.
+
+    Returns a shallow copy of the dataset in which ``var_name`` is the filtered array in HBM, with the same dimensions
+    and coordinates, the attribute ``window_filter = "<method> <ping_num>x<range_sample_num>"`` and without
+    ``actual_range`` (it no longer holds); ``ds_Sv`` itself is untouched.  A bad argument raises ``ValueError`` before any
+    device work.  Device work: one launch (``epa_window_filter``), no host synchronisation; a deferred ``Sv`` is written
+    first, as for any other reader.
+
+    Not built: boolean masks (cast one, filter with min / max, compare), windows in metres or seconds, weighted kernels,
+    windows above 15, a sharded multi-GPU form."""
+    ds_Sv = from_xarray(ds_Sv)
+    ops.window_filter_args(method, ping_num, range_sample_num, min_valid, who="clean.window_filter")
+    if not isinstance(var_name, str) or var_name not in ds_Sv.data_vars:
+        raise ValueError(f"clean.window_filter: the dataset has no variable {var_name!r}")
+    da = ds_Sv[var_name]
+    dims = tuple(da.dims)
+    if len(dims) not in (2, 3) or dims[-2:] != _CPS[1:]:
+        raise ValueError(f"clean.window_filter: {var_name} must lie over (..., 'ping_time', 'range_sample') with at most one "
+                         f"leading dimension, got {dims}")
+    if np.dtype(da.dtype).kind != "f":
+        raise ValueError(f"clean.window_filter: {var_name} must be floating, got {da.dtype}")
+    x = device_view(da, dims, floating=True)
+    y = ops.window_filter(x, method, ping_num, range_sample_num, min_valid=min_valid, keep_nan=keep_nan)
+    attrs = da.attrs.copy()  # (a number still on its way from the GPU stays on its way: nothing is read here)
+    if "actual_range" in attrs:
+        del attrs["actual_range"]
+    attrs["window_filter"] = f"{method} {int(ping_num)}x{int(range_sample_num)}"
+    out = ds_Sv.copy()
+    out.data_vars[var_name] = DataArray(DeviceArray(y), dims, attrs=attrs, name=var_name)
+    return out
+
+
 # names used by older echopype releases (docs/source/whats-new.md:366)
 estimate_noise = estimate_background_noise
 remove_noise = remove_background_noise

@@ -1397,6 +1397,51 @@ def regrid_rows(sv, range, range_bin, n_rbins, *, with_coverage=True, out=None, 
     return sv_out, cov, n_unordered
 
 
+# ---- NaN-aware median, mean, min and max windows (clean.window_filter) ----------------------------------------------------
+def window_filter_args(method, ping_num, range_sample_num, min_valid, who="window_filter"):
+    """The checked (method code, ping_num, range_sample_num, min_valid) of a window filter; ValueError otherwise.  No
+    device is touched."""
+    if not isinstance(method, str) or method not in _lib.WINDOW_METHODS:
+        raise ValueError(f"{who}: method must be one of {_lib.WINDOW_METHODS}, got {method!r}")
+    sizes = []
+    for name, n in (("ping_num", ping_num), ("range_sample_num", range_sample_num)):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n % 2 != 1 or not 1 <= n <= _lib.WINDOW_FILTER_MAX:
+            raise ValueError(f"{who}: {name} must be an odd integer within 1 .. {_lib.WINDOW_FILTER_MAX}, got {n!r}")
+        sizes.append(int(n))
+    if isinstance(min_valid, bool) or not isinstance(min_valid, (int, np.integer)) or not 1 <= min_valid <= sizes[0] * sizes[1]:
+        raise ValueError(f"{who}: min_valid must be an integer within 1 .. {sizes[0] * sizes[1]} (the window), got {min_valid!r}")
+    return _lib.WINDOW_METHODS.index(method), sizes[0], sizes[1], int(min_valid)
+
+
+def window_filter(x, method, ping_num, range_sample_num, *, min_valid=1, keep_nan=True, out=None, _max_grid=0):
+    """``x`` (C, P, S) or (P, S), float32 / float64, contiguous, on the device -> the tensor of the same type and shape
+    in which every sample is the ``method`` ("median", "mean", "min", "max") of the ``ping_num x range_sample_num``
+    samples around it, both sizes odd and at most ``_lib.WINDOW_FILTER_MAX`` (``epa_window_filter``: one launch, every
+    output element written exactly once; THE RULE is in the header and in ``clean.window_filter``).  The window is
+    clipped to the array and never crosses channels; NaN is skipped, +-inf are values; fewer than ``min_valid`` valid
+    values give NaN; with ``keep_nan`` a NaN sample stays NaN.  ``out``: the tensor to write into instead of a new one
+    (it must not overlap ``x``; tests: a pre-filled allocation shows that every element is written).  ``_max_grid``:
+    the most workgroups to launch (tests: the tile loop at small shapes).  No host synchronisation."""
+    code, ping_num, range_sample_num, min_valid = window_filter_args(method, ping_num, range_sample_num, min_valid)
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or x.dtype not in _DT:
+        raise ValueError("window_filter: x must be a float32 / float64 tensor of shape (C, P, S) or (P, S), got "
+                         f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    if not x.is_cuda:
+        raise ValueError(f"window_filter: x must be on the device, got a tensor on {x.device}")
+    if not x.is_contiguous():
+        raise ValueError("window_filter: x must be contiguous")
+    if out is None:
+        out = torch.empty_like(x)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != x.dtype or out.shape != x.shape or out.device != x.device
+          or not out.is_contiguous()):
+        raise ValueError(f"window_filter: out must be a contiguous {tuple(x.shape)} tensor of {x.dtype} on {x.device}")
+    C = x.shape[0] if x.dim() == 3 else 1
+    P, S = x.shape[-2:]
+    call("epa_window_filter", _p(x), _DT[x.dtype], C, P, S, code, ping_num, range_sample_num, min_valid, int(bool(keep_nan)),
+         _p(out), int(_max_grid), _stream())
+    return out
+
+
 # ---- echo summary statistics per row (metrics.*) ------------------------------------------------------------------------
 METRICS =("abundance", "center_of_mass", "dispersion", "evenness", "aggregation")
 

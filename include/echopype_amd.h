@@ -949,6 +949,35 @@ int epa_regrid_rows(const void* sv, int dtype, const void* range, int range_dtyp
                     int n_rbins, void* sv_out, void* coverage_out, int32_t* n_unordered_out, int max_grid,
                     epa_stream_t stream);
 
+/* ---- clean.window_filter: NaN-aware median, mean, min and max windows on Sv ----------------------------------------------
+ * x [C*P*S] (dtype F32 / F64, contiguous) -> out of the same type and shape.  THE RULE.  With hp = ping_num / 2 and hs =
+ * range_sample_num / 2 (both sizes odd, 1 .. EPA_WINDOW_FILTER_MAX), the window of (c, p, s) is the samples (c, p', s')
+ * with |p' - p| <= hp and |s' - s| <= hs that lie inside the array: it shrinks at the edges (no reflection, no padding
+ * value) and never crosses channels.  Its VALID values are those that are not NaN; -inf and +inf are values, ordered as
+ * usual, in every method.  With n the number of valid values:
+ *   EPA_WINDOW_MEDIAN : n odd: the middle valid value, an input bit for bit.  n even: with a <= b the two middle values,
+ *                       a itself when a == b (no round trip through the exponential), else
+ *                       10 log10((10^(a/10) + 10^(b/10)) / 2): the median of the linear values
+ *   EPA_WINDOW_MEAN   : 10 log10(sum of 10^(v/10) over the valid v / n); -inf if all of them are -inf, +inf if any is +inf
+ *   EPA_WINDOW_MIN / EPA_WINDOW_MAX : the smallest / largest valid value, an input bit for bit (erosion / dilation)
+ *   out = NaN where n < min_valid (1 .. ping_num * range_sample_num; a window without a valid value is always NaN), and,
+ *   with keep_nan != 0, where x itself is NaN whatever its neighbours hold; with keep_nan == 0 such a sample gets its
+ *   window's result.
+ * What is not a selection (the mean's exponentials, sum and logarithm; the even median's two exponentials and logarithm)
+ * is float64 for both types and rounded once to dtype.  One kernel launch; a workgroup owns a tile of EPA_WINDOW_FILTER_TP
+ * pings x EPA_WINDOW_FILTER_TS samples and reads it with its halo from LDS, where array positions outside the array are
+ * NaN; every element of out is stored exactly once, nothing is pre-filled; no scratch.
+ *   max_grid : the most workgroups to launch, 0: the library's choice (tests: the tile loop at small shapes)
+ * EPA_EINVAL (nothing is launched): a bad dtype or method; C, P or S negative; an even size or one outside 1 ..
+ * EPA_WINDOW_FILTER_MAX; min_valid outside 1 .. ping_num * range_sample_num; a negative max_grid; x or out NULL with
+ * C*P*S > 0; out overlapping x (a neighbour's halo would read results); more than 2^31 - 1 tiles. */
+enum epa_window_method { EPA_WINDOW_MEDIAN = 0, EPA_WINDOW_MEAN = 1, EPA_WINDOW_MIN = 2, EPA_WINDOW_MAX = 3 };
+#define EPA_WINDOW_FILTER_MAX 15 /* the largest window size along either axis */
+#define EPA_WINDOW_FILTER_TP 16 /* pings of a workgroup's tile */
+#define EPA_WINDOW_FILTER_TS 64 /* samples of a workgroup's tile */
+int epa_window_filter(const void* x, int dtype, int C, int P, int S, int method, int ping_num, int range_sample_num,
+                      int min_valid, int keep_nan, void* out, int max_grid, epa_stream_t stream);
+
 /* ---- echo summary statistics per row: metrics.abundance / center_of_mass / dispersion / evenness / aggregation --------
  * (metrics/summary_statistics.py).  sv [R*S] and range of dtype F32 / F64; range is [R*S] when range_per_row != 0,
  * else [S], shared by all rows.  For j = 1 .. S-1: dz_j = range_j - range_{j-1} rounded in dtype, 0 -> NaN;
