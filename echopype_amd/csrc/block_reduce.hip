@@ -500,8 +500,9 @@ Plan make_plan(int C, int P, int S, int n_tbins, int n_rbins, bool aligned16) {
   pl.use_lds = need <= kAccLdsMax;
   const size_t acc_bytes = pl.use_lds ? (need < 64 ? 64 : need) : 64;
   pl.cnt_off = (unsigned)sum_bytes;
-  pl.tab_off = (unsigned)((acc_bytes + 15) & ~(size_t)15);
-  pl.lds_bytes = pl.tab_off + epa::kMathTabBytes;
+  const epa::BinLds lds = epa::bin_lds_layout(acc_bytes);
+  pl.tab_off = lds.tab_off;
+  pl.lds_bytes = lds.total;
   const long long groups = (long long)C * n_tbins;
   pl.nparts = 1;
   if (groups < kSplitBelowGroups) {
@@ -527,11 +528,7 @@ int launch_reduce(ReduceArgs& a, const Plan& pl, hipStream_t st) {
 #define EPA_RL(V)                                                                                 \
   do {                                                                                            \
     auto kern = block_reduce_kernel<T, SRC, OP, V>;                                               \
-    if (pl.lds_bytes > 64 * 1024) {                                                               \
-      EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                      \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,               \
-                                        (int)pl.lds_bytes));                                      \
-    }                                                                                             \
+    if (int rc = epa::allow_lds(kern, pl.lds_bytes)) return rc;                                   \
     hipLaunchKernelGGL(kern, grid, block, pl.lds_bytes, st, a);                                   \
   } while (0)
   if (pl.vec == 4) EPA_RL(4); else if (pl.vec == 2) EPA_RL(2); else EPA_RL(1);

@@ -20,6 +20,7 @@
 #include "fast_math.h"
 #include "ordered_key.h"
 #include "sample_math.h"
+#include "time_bin.h"
 
 namespace epa_chain {
 
@@ -52,7 +53,6 @@ struct Args {
 using epa::kKeyNoMax;
 using epa::kKeyNoMin;
 using epa::key_value;
-using epa::lds_add;
 using epa::ordered_key;
 using epa::vmax_num;
 using epa::vmin_num;
@@ -181,12 +181,12 @@ struct RowCache {
   __device__ __forceinline__ RowCache() : d(__builtin_nan("")), ra(d), rb(d), dtl(d), log10k((T)0) {}
   // plog / pi: log10(k) of ping pi of the group, computed once per workgroup (fill_ping_logs), pi < kPingLogs
   template <typename C>
-  __device__ __forceinline__ void update(const epa::CoefRow& r, C (&col)[VEC], int sA, int sB, T nspread,
+  __device__ __forceinline__ void update(const epa::CoefRow& r, C (&col)[VEC], const epa::PairLanes& lm, T nspread,
                                          const double2* log_tab, const T* plog, int pi) {
     if (!((r.d == d) & (r.ra == ra))) {
       d = r.d;
       for (int j = 0; j < VEC; ++j) {
-        const double sj = (double)((j < 2 ? sA : sB) + (j & 1));
+        const double sj = (double)lm.sample(j);
         col[j].nL = nspread * log10_exact<T>((T)(sj - r.d));
         col[j].sra = sj * r.ra;
         const T v = (T)(sj - r.d), v2 = v * v;
@@ -205,7 +205,7 @@ struct RowCache {
     if (!(dnew == dtl)) {
       dtl = dnew;
       for (int j = 0; j < VEC; ++j) {
-        const double sj = (double)((j < 2 ? sA : sB) + (j & 1));
+        const double sj = (double)lm.sample(j);
         col[j].lgs = log10_slow((T)(sj - dnew), log_tab);
       }
     }
@@ -263,23 +263,19 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
     const float* __restrict__ raw, const epa::CoefRow* __restrict__ coef,
     const double* __restrict__ alpha2, T* __restrict__ sv_out, double* __restrict__ noise_out, Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* lsum = reinterpret_cast<T*>(smem);
-  uint32_t* lcnt = reinterpret_cast<uint32_t*>(smem + a.cnt_off);
+  const epa::BinAcc<T> acc(smem, a.cnt_off);
   const epa::MathTabs mt = epa::build_math_tabs(smem + a.tab_off);
   __shared__ T red[8];
 
   // One workgroup takes kP1Blocks consecutive ping blocks: the per-column logs it caches (two ocml-grade logs per
   // column and chunk) are then paid once per 40 pings instead of once per 20 (interleaved A/B on one box, 2 G samples:
   // 5.45 -> 5.27 ms with 2 blocks, 5.30 with 4: the larger footprint of a workgroup starts to cost what the fixed work
-  // saves).  lsum / lcnt hold one row of range-block sums per ping block.
+  // saves).  The accumulators hold one row of range-block sums per ping block.
   // (the workgroups of one XCD walk one contiguous eighth of the ping blocks: epa::xcd_contiguous)
   const int c = blockIdx.y, pbk0 = (a.xcd_map ? epa::xcd_contiguous(blockIdx.x, gridDim.x) : (int)blockIdx.x) * kP1Blocks;
   const int nb = min(kP1Blocks, a.n_pblocks - pbk0);
   const int S = a.S, Sb = a.n_rblocks;
-  for (int i = threadIdx.x; i < kP1Blocks * Sb; i += epa::kBlock) {
-    lsum[i] = (T)0;
-    lcnt[i] = 0u;
-  }
+  acc.clear(kP1Blocks * Sb);
   __syncthreads();
   const T nspread = (T)a.nspread;
   const epa::CoefRow* __restrict__ rowp0 = coef + (size_t)c * a.P;
@@ -301,27 +297,25 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
   __syncthreads();
 
   for (int chunk0 = 0; chunk0 < S; chunk0 += kChunk) {
-    const int sA = chunk0 + wave * 256 + 2 * lane, sB = sA + 128;
+    const epa::PairLanes lm(chunk0, wave, lane, S);
+    const int sA = lm.sA, sB = lm.sB;
     if (sA >= S) continue;
-    const bool hasB = sB < S;
+    const bool hasB = lm.hasB;
     const int eA = wave * 256 + 2 * lane;  // the lane's entries of col_nL / col_lgs: eA, eA + 1, eA + 128, eA + 129
     NoiseCol<T> col[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
       col[j].sra = 0.0; col[j].acc_sum = (T)0; col[j].acc_cnt = 0u;
-      col_nL[eA + (j < 2 ? 0 : 128) + (j & 1)] = epa::M<T>::nan();
-      col_lgs[eA + (j < 2 ? 0 : 128) + (j & 1)] = (T)0;
+      col_nL[eA + epa::PairLanes::offset(j)] = epa::M<T>::nan();
+      col_lgs[eA + epa::PairLanes::offset(j)] = (T)0;
     }
     int rbk[VEC];  // range block of each column
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) rbk[j] = ((j < 2 ? sA : sB) + (j & 1)) / a.rsn;
+    for (int j = 0; j < VEC; ++j) rbk[j] = lm.sample(j) / a.rsn;
     auto flush = [&](int g) {  // the columns' sums of ping block g -> its row of range-block sums
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
-        if (col[j].acc_cnt > 0u) {
-          lds_add(lsum + g * Sb + rbk[j], col[j].acc_sum);
-          atomicAdd(lcnt + g * Sb + rbk[j], col[j].acc_cnt);
-        }
+        if (col[j].acc_cnt > 0u) acc.row(g * Sb).add(rbk[j], col[j].acc_sum, col[j].acc_cnt);
         col[j].acc_sum = (T)0;
         col[j].acc_cnt = 0u;
       }
@@ -349,9 +343,9 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
         rc.d = r.d;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-          const double sj = (double)((j < 2 ? sA : sB) + (j & 1));
-          col_nL[eA + (j < 2 ? 0 : 128) + (j & 1)] = nspread * log10_exact<T>((T)(sj - r.d));
-          if (SRA_LDS) col_sra[eA + (j < 2 ? 0 : 128) + (j & 1)] = sj * r.ra;
+          const double sj = (double)lm.sample(j);
+          col_nL[eA + epa::PairLanes::offset(j)] = nspread * log10_exact<T>((T)(sj - r.d));
+          if (SRA_LDS) col_sra[eA + epa::PairLanes::offset(j)] = sj * r.ra;
           else col[j].sra = sj * r.ra;
         }
       }
@@ -369,8 +363,8 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
           rc.dtl = dnew;
 #pragma unroll
           for (int j = 0; j < VEC; ++j) {
-            const double sj = (double)((j < 2 ? sA : sB) + (j & 1));
-            col_lgs[eA + (j < 2 ? 0 : 128) + (j & 1)] = log10_slow((T)(sj - dnew), mt.log_tab);
+            const double sj = (double)lm.sample(j);
+            col_lgs[eA + epa::PairLanes::offset(j)] = log10_slow((T)(sj - dnew), mt.log_tab);
           }
         }
       }
@@ -381,7 +375,7 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
       const float in[VEC] = {inA.x, inA.y, inB.x, inB.y};
       auto one = [&](int j) -> T {
         double x;
-        const int e = eA + (j < 2 ? 0 : 128) + (j & 1);
+        const int e = eA + epa::PairLanes::offset(j);
         const ColBase<T> cb{SRA_LDS ? col_sra[e] : col[j].sra, col_nL[e], col_lgs[e], (T)0};
         const T svj = calibrate<T>(cb, in[j], r, r0v, g_, a2, A0, nspread, x, mt.log_tab);
         if (RMAX) {  // as stored (T).  The echo_range is NaN where the raw sample is NaN and nowhere else (an infinite
@@ -451,16 +445,16 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
     if (a.edge_sum && (pbk0 + g == 0 || pbk0 + g == a.n_pblocks - 1)) {  // (uniform) rows for the cross-shard merge
       const size_t e0 = ((size_t)(pbk0 + g == 0 ? 0 : 1) * gridDim.y + c) * Sb;  // (a single block: its first edge only)
       for (int i = threadIdx.x; i < Sb; i += epa::kBlock) {
-        a.edge_sum[e0 + i] = (double)lsum[g * Sb + i];
-        a.edge_cnt[e0 + i] = lcnt[g * Sb + i];
+        a.edge_sum[e0 + i] = (double)acc.sum[g * Sb + i];
+        a.edge_cnt[e0 + i] = acc.cnt[g * Sb + i];
       }
     }
     T best = (T)__builtin_inf();
     int any = 0;
     for (int i = threadIdx.x; i < Sb; i += epa::kBlock) {
-      const uint32_t n = lcnt[g * Sb + i];
+      const uint32_t n = acc.cnt[g * Sb + i];
       if (n > 0u) {
-        const T db = (T)10 * epa::M<T>::log10(lsum[g * Sb + i] / (T)n);
+        const T db = (T)10 * epa::M<T>::log10(acc.sum[g * Sb + i] / (T)n);
         if (db == db) {
           best = fmin(best, db);
           any = 1;
@@ -494,17 +488,16 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
 // payload no computation produces; the general kernel overwrites it)
 using LeftToGeneral = epa::LeftMark<0x7ff8dead0c0ffee1ull, 0x7fcdead1u>;
 
+// (The cursor is epa::BinCursor's, written out: the fp64 instances of the kernel below sit at their 168-VGPR cap, and
+// through the shared cursor their spills move -- profiles/time_bin_resources.txt.)
 template <typename T>
 struct BinCol : ColBase<T> {
   double blo, bhi;  // edges of the range bin the column currently sits in (empty: blo > bhi)
   T acc_sum;
   int acc_rb;
   uint32_t acc_cnt;
-  __device__ __forceinline__ void flush(T* lsum, uint32_t* lcnt) {
-    if (acc_rb >= 0 && acc_cnt > 0u) {
-      lds_add(lsum + acc_rb, acc_sum);
-      atomicAdd(lcnt + acc_rb, acc_cnt);
-    }
+  __device__ __forceinline__ void flush(const epa::BinAcc<T>& acc) {
+    if (acc_rb >= 0 && acc_cnt > 0u) acc.add(acc_rb, acc_sum, acc_cnt);
   }
 };
 
@@ -517,8 +510,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
     const int32_t* __restrict__ bin_start, T* __restrict__ noise_out, T* __restrict__ corr_out,
     T* __restrict__ mvbs_out, T* __restrict__ sum_out, uint32_t* __restrict__ cnt_out, Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* lsum = reinterpret_cast<T*>(smem);
-  uint32_t* lcnt = reinterpret_cast<uint32_t*>(smem + a.cnt_off);
+  const epa::BinAcc<T> acc(smem, a.cnt_off);
   const epa::MathTabs mt = epa::build_math_tabs(smem + a.tab_off);
 
   const int c = blockIdx.y, tb = blockIdx.x;
@@ -529,10 +521,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
   if (a.flagged_only && !extra && !LeftToGeneral::is_marked(mvbs_out + ((size_t)c * a.n_tbins + tb) * n_rbins))
     return;  // (uniform) the group was done by sv_denoise_mvbs_uniform_kernel
   const int nseg = extra ? 2 : 1;
-  for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
-    lsum[i] = (T)0;
-    lcnt[i] = 0u;
-  }
+  acc.clear(n_rbins);
   __syncthreads();
 
   const T nspread = (T)a.nspread, snr = (T)a.snr;
@@ -557,9 +546,10 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
   if (kProd) fill_ping_consts(pcs, rowp0 + pb, a2p + pb, nzp, pb + a.ping_phase, pe - pb, a.noise_ping_num, mt.exp2_tab);
   __syncthreads();
   for (int chunk0 = 0; chunk0 < S; chunk0 += kChunk) {
-    const int sA = chunk0 + wave * 256 + 2 * lane, sB = sA + 128;
+    const epa::PairLanes lm(chunk0, wave, lane, S);
+    const int sA = lm.sA, sB = lm.sB;
     if (sA >= S) continue;
-    const bool hasB = sB < S;
+    const bool hasB = lm.hasB;
     BinCol<T> col[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
@@ -584,7 +574,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
         nA = *reinterpret_cast<const float2*>(raw_c + row_off + S + sA);
         if (hasB) nB = *reinterpret_cast<const float2*>(raw_c + row_off + S + sB);
       }
-      rc.update(r, col, sA, sB, nspread, mt.log_tab, plog, p - pb);
+      rc.update(r, col, lm, nspread, mt.log_tab, plog, p - pb);
       const T g = (T)r.g, a2 = (T)r.alpha2, A0 = (T)r.A0, na2 = (T)a2p[p];
       const T nb = (T)nzp[(p + a.ping_phase) / a.noise_ping_num];
       const float in[VEC] = {inA.x, inA.y, inB.x, inB.y};
@@ -619,7 +609,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
           const T mx = fmax((T)x, (T)1), xx = mx * mx;
           T lsv = epa::lin_from_db_lean(g * (T)in[j], mt.exp2_tab) * (c2 * (T)pc.csv);
           if (pc.da2k != 0.0)  // (uniform, never through the Dataset API) the calibration used another absorption
-            lsv *= (T)epa::lin_from_db_lean(pc.da2k * (double)((j < 2 ? sA : sB) + (j & 1)), mt.exp2_tab);
+            lsv *= (T)epa::lin_from_db_lean(pc.da2k * (double)lm.sample(j), mt.exp2_tab);
           lin = ecol[j] * (lsv - (T)pc.cn * xx);
         } else {
           const T sv = calibrate<T>(cj, in[j], r, r.r0, g, a2, A0, nspread, x, mt.log_tab);
@@ -642,7 +632,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
         if (!same) {
           const int rb = xok ? epa::range_bin_index(x, bin, inv_bin, n_rbins, false) : -1;
           if (rb != cj.acc_rb) {
-            if (!extra) cj.flush(lsum, lcnt);
+            if (!extra) cj.flush(acc);
             cj.acc_rb = rb;
             cj.acc_sum = (T)0;
             cj.acc_cnt = 0u;
@@ -665,7 +655,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
     }
     if (!extra) {
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) col[j].flush(lsum, lcnt);
+      for (int j = 0; j < VEC; ++j) col[j].flush(acc);
     }
   }
   }
@@ -682,16 +672,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
   if (extra) return;
   __syncthreads();
   const size_t cell0 = ((size_t)c * a.n_tbins + tb) * n_rbins;
-  T* out = mvbs_out + cell0;
-  T* gsum = sum_out ? sum_out + cell0 : nullptr;
-  uint32_t* gcnt = cnt_out ? cnt_out + cell0 : nullptr;
-  for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
-    const uint32_t n = lcnt[i];
-    const T s = lsum[i];
-    out[i] = n > 0u ? (T)10 * epa::M<T>::log10(s / (T)n) : (T)a.fill_value;
-    if (gsum) gsum[i] = s;
-    if (gcnt) gcnt[i] = n;
-  }
+  acc.store(mvbs_out, sum_out, cnt_out, cell0, n_rbins, (T)a.fill_value);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -719,23 +700,19 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_uniform_kernel
     T* __restrict__ corr_out, T* __restrict__ mvbs_out, T* __restrict__ sum_out,
     uint32_t* __restrict__ cnt_out, Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* lsum = reinterpret_cast<T*>(smem);
-  uint32_t* lcnt = reinterpret_cast<uint32_t*>(smem + a.cnt_off);
+  const epa::BinAcc<T> acc(smem, a.cnt_off);
   const epa::MathTabs mt = epa::build_math_tabs(smem + a.tab_off);
   __shared__ PingLin<T> pl[kUniPings];
   __shared__ int differs;
 
   // a workgroup takes a.uni_bins consecutive time bins (their pings are one run): the per-column constants are paid
-  // once for all of them; lsum / lcnt hold one row of range bins per time bin
+  // once for all of them; the accumulators hold one row of range bins per time bin
   const int c = blockIdx.y, tb0 = (a.xcd_map ? epa::xcd_contiguous(blockIdx.x, gridDim.x) : (int)blockIdx.x) * a.uni_bins;
   const int nbn = min(a.uni_bins, a.n_tbins - tb0);
   const int S = a.S, n_rbins = a.n_rbins;
   const int pb = bin_start[tb0], pe = bin_start[tb0 + nbn], np = pe - pb;
   const size_t cell0 = ((size_t)c * a.n_tbins + tb0) * n_rbins;
-  for (int i = threadIdx.x; i < nbn * n_rbins; i += epa::kBlock) {
-    lsum[i] = (T)0;
-    lcnt[i] = 0u;
-  }
+  acc.clear(nbn * n_rbins);
   if (threadIdx.x == 0) differs = np > kUniPings ? 1 : 0;
   __syncthreads();  // (also publishes the math tables)
   const epa::CoefRow* __restrict__ rowp0 = coef + (size_t)c * a.P;
@@ -772,16 +749,17 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_uniform_kernel
   T mm[4] = {(T)__builtin_inf(), -(T)__builtin_inf(), (T)__builtin_inf(), -(T)__builtin_inf()};
 
   for (int chunk0 = 0; chunk0 < S; chunk0 += kChunk) {
-    const int sA = chunk0 + wave * 256 + 2 * lane, sB = sA + 128;
+    const epa::PairLanes lm(chunk0, wave, lane, S);
+    const int sA = lm.sA, sB = lm.sB;
     if (sA >= S) continue;
-    const bool hasB = sB < S;
+    const bool hasB = lm.hasB;
     // ---- the group's per-column constants
     T c2E[VEC], xxE[VEC], sncol[VEC], acc_sum[VEC];
     int rbin[VEC];
     uint32_t acc_cnt[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const double sj = (double)((j < 2 ? sA : sB) + (j & 1));
+      const double sj = (double)lm.sample(j);
       const double x = (sj * r.ra) * r.rb + r.r0;  // echo_range (range.py:138 operation order)
       const double rtd = x - r.shift;              // R' <= 0 -> NaN (calibrate_ek.py:107)
       const T v = (T)(sj - r.d), v2 = v * v;
@@ -804,10 +782,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_uniform_kernel
     auto flush = [&](int g) {  // the columns' sums of time bin g -> its row of range bins
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
-        if (rbin[j] >= 0 && acc_cnt[j] > 0u) {
-          lds_add(lsum + g * n_rbins + rbin[j], acc_sum[j]);
-          atomicAdd(lcnt + g * n_rbins + rbin[j], acc_cnt[j]);
-        }
+        if (rbin[j] >= 0 && acc_cnt[j] > 0u) acc.row(g * n_rbins).add(rbin[j], acc_sum[j], acc_cnt[j]);
         acc_sum[j] = (T)0;
         acc_cnt[j] = 0u;
       }
@@ -876,16 +851,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_uniform_kernel
     wg_minmax_keys(mm, a.mm_keys, lane);
   }
   __syncthreads();
-  T* out = mvbs_out + cell0;
-  T* gsum = sum_out ? sum_out + cell0 : nullptr;
-  uint32_t* gcnt = cnt_out ? cnt_out + cell0 : nullptr;
-  for (int i = threadIdx.x; i < nbn * n_rbins; i += epa::kBlock) {
-    const uint32_t n = lcnt[i];
-    const T s = lsum[i];
-    out[i] = n > 0u ? (T)10 * epa::M<T>::log10(s / (T)n) : (T)a.fill_value;
-    if (gsum) gsum[i] = s;
-    if (gcnt) gcnt[i] = n;
-  }
+  acc.store(mvbs_out, sum_out, cnt_out, cell0, nbn * n_rbins, (T)a.fill_value);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -919,8 +885,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
     T* __restrict__ corr_out, T* __restrict__ mvbs_out, T* __restrict__ sum_out,
     uint32_t* __restrict__ cnt_out, Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* lsum = reinterpret_cast<T*>(smem);
-  uint32_t* lcnt = reinterpret_cast<uint32_t*>(smem + a.cnt_off);
+  const epa::BinAcc<T> acc(smem, a.cnt_off);
   const epa::MathTabs mt = epa::build_math_tabs(smem + a.tab_off);
   __shared__ PingDrift<T> pl[kDriftPings];
   __shared__ PingDriftRare<T> plr[kDriftPings];
@@ -934,10 +899,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
   // (uniform) only the groups the uniform kernel marked; a group of two bins is marked in both or in neither
   if (!LeftToGeneral::is_marked(mvbs_out + cell0)) return;
   const int pb = bin_start[tb0], pe = bin_start[tb0 + nbn], np = pe - pb;
-  for (int i = threadIdx.x; i < nbn * n_rbins; i += epa::kBlock) {
-    lsum[i] = (T)0;
-    lcnt[i] = 0u;
-  }
+  acc.clear(nbn * n_rbins);
   if (threadIdx.x == 0) {
     differs = np > kDriftPings ? 1 : 0;
     rb_lo_key = kKeyNoMin;
@@ -995,9 +957,10 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
   }
 
   for (int chunk0 = 0; chunk0 < S; chunk0 += kChunk) {
-    const int sA = chunk0 + wave * 256 + 2 * lane, sB = sA + 128;
+    const epa::PairLanes lm(chunk0, wave, lane, S);
+    const int sA = lm.sA, sB = lm.sB;
     if (sA >= S) continue;
-    const bool hasB = sB < S;
+    const bool hasB = lm.hasB;
     // ---- the group's per-column constants
     T c2[VEC], sn20[VEC], acc_sum[VEC];
     int rbin[VEC];
@@ -1005,7 +968,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
     unsigned plain = 0;
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const double sj = (double)((j < 2 ? sA : sB) + (j & 1));
+      const double sj = (double)lm.sample(j);
       const double sra = sj * r.ra;
       const double x_lo = sra * rb_lo, x_hi = sra * rb_hi;  // the group's extreme ranges of this column (monotone in rb)
       const T v = (T)(sj - r.d), v2 = v * v;
@@ -1021,10 +984,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
       acc_cnt[j] = 0u;
     }
     auto flush_col = [&](int g, int j) {
-      if (rbin[j] >= 0 && acc_cnt[j] > 0u) {
-        lds_add(lsum + g * n_rbins + rbin[j], acc_sum[j]);
-        atomicAdd(lcnt + g * n_rbins + rbin[j], acc_cnt[j]);
-      }
+      if (rbin[j] >= 0 && acc_cnt[j] > 0u) acc.row(g * n_rbins).add(rbin[j], acc_sum[j], acc_cnt[j]);
       acc_sum[j] = (T)0;
       acc_cnt[j] = 0u;
     };
@@ -1058,7 +1018,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
       for (int j = 0; j < VEC; ++j) {
         if (j >= 2 && !hasB) break;
         const bool xok = in[j] == in[j];
-        const T sj = (T)((j < 2 ? sA : sB) + (j & 1));
+        const T sj = (T)lm.sample(j);
         // a NaN sample needs no masking: it makes the exponential, hence lin, NaN by itself
         const T e = epa::lin_from_db_lean(q.g * (T)in[j], mt.exp2_tab);
         // (e times the PRODUCT of the constants: 10^(g raw / 10) * (s - d)^2 alone overflows T 30 .. 40 dB before
@@ -1095,8 +1055,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
     // ---- the columns off the plain path (a few per wavefront): one column at a time with the wavefront's lanes
     // spread over the PINGS of the group -- the general kernel's per-sample arithmetic, the range bin found per ping,
     // the sums added straight to the group's rows
-    const unsigned have = hasB ? 0xfu : 0x3u;
-    const unsigned off_plain = (~plain) & have;
+    const unsigned off_plain = (~plain) & lm.have();
     if (__ballot(off_plain != 0u) != 0ull) {
       // the lanes still here are 0 .. nact - 1 (sA grows with the lane): in the row's last, partial wavefront only
       // they exist to share the pings, so the stride is their number, not 64
@@ -1107,7 +1066,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
         while (todo != 0ull) {  // (wave-uniform)
           const int src = __ffsll((long long)todo) - 1;
           todo &= todo - 1ull;
-          const int sx = chunk0 + wave * 256 + 2 * src + (j < 2 ? 0 : 128) + (j & 1);
+          const int sx = epa::PairLanes::sample_of(chunk0, wave, src, j);
           const double sj = (double)sx;
           const T v = (T)(sj - r.d), v2 = v * v;
           const T c2j = v > (T)0 ? (nspread == (T)20 ? v2 : v2 * v2) : (T)0;
@@ -1146,10 +1105,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
               mm_max(3, scv);
             }
             const int rb = xok ? epa::range_bin_index(x, bin, inv_bin, n_rbins, false) : -1;
-            if ((rb >= 0) & keep) {
-              lds_add(lsum + g2 * n_rbins + rb, lin);
-              atomicAdd(lcnt + g2 * n_rbins + rb, 1u);
-            }
+            if ((rb >= 0) & keep) acc.row(g2 * n_rbins).add(rb, lin, 1u);
           }
         }
       }
@@ -1169,44 +1125,32 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
     wg_minmax_keys(mm, a.mm_keys, lane);
   }
   __syncthreads();
-  T* out = mvbs_out + cell0;
-  T* gsum = sum_out ? sum_out + cell0 : nullptr;
-  uint32_t* gcnt = cnt_out ? cnt_out + cell0 : nullptr;
-  for (int i = threadIdx.x; i < nbn * n_rbins; i += epa::kBlock) {
-    const uint32_t n = lcnt[i];
-    const T s = lsum[i];
-    out[i] = n > 0u ? (T)10 * epa::M<T>::log10(s / (T)n) : (T)a.fill_value;  // (overwrites the mark of the group)
-    if (gsum) gsum[i] = s;
-    if (gcnt) gcnt[i] = n;
-  }
+  acc.store(mvbs_out, sum_out, cnt_out, cell0, nbn * n_rbins, (T)a.fill_value);  // (overwrites the mark of the group)
 }
 
-template <typename K>
-int set_lds(K kern, size_t lds) {
-  if (lds > 64 * 1024)
-    EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return EPA_OK;
+// the (sum, count) rows of a kernel that holds `cells` accumulators, then the math tables: cnt_off, tab_off -> the bytes
+template <typename T>
+size_t lay_out_lds(Args& a, size_t cells) {
+  const size_t sum_bytes = (cells * sizeof(T) + 15) & ~(size_t)15;
+  const epa::BinLds lds = epa::bin_lds_layout(sum_bytes + cells * 4);
+  a.cnt_off = (unsigned)sum_bytes;
+  a.tab_off = lds.tab_off;
+  return lds.total;
 }
 
 template <typename T>
 int launch_pass1(Args& a, const float* raw, const double* coef, const double* alpha2, void* sv_out,
                  double* noise_out, int C, hipStream_t st) {
-  const size_t sum_bytes = ((size_t)kP1Blocks * a.n_rblocks * sizeof(T) + 15) & ~(size_t)15;
-  a.cnt_off = (unsigned)sum_bytes;
-  a.tab_off = (unsigned)((sum_bytes + (size_t)kP1Blocks * a.n_rblocks * 4 + 15) & ~(size_t)15);
-  const size_t lds = a.tab_off + epa::kMathTabBytes;
+  const size_t lds = lay_out_lds<T>(a, (size_t)kP1Blocks * a.n_rblocks);
   const dim3 grid((unsigned)((a.n_pblocks + kP1Blocks - 1) / kP1Blocks), (unsigned)C);
-#define EPA_P1(W, R)                                                                                    \
-  do {                                                                                                  \
-    auto kern = sv_noise_fast_kernel<T, W, R>;                                                          \
-    if (int rc = set_lds(kern, lds)) return rc;                                                         \
-    hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds, st, raw,                                     \
-                       reinterpret_cast<const epa::CoefRow*>(coef), alpha2, (T*)sv_out, noise_out, a);  \
-  } while (0)
-  if (a.rmax_key) { if (sv_out) EPA_P1(true, true); else EPA_P1(false, true); }
-  else { if (sv_out) EPA_P1(true, false); else EPA_P1(false, false); }
-#undef EPA_P1
+  const int rc = epa::dispatch_flags([&](auto w, auto r) -> int {
+    auto kern = sv_noise_fast_kernel<T, decltype(w)::value, decltype(r)::value>;
+    if (int rc = epa::allow_lds(kern, lds)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds, st, raw, reinterpret_cast<const epa::CoefRow*>(coef), alpha2,
+                       (T*)sv_out, noise_out, a);
+    return EPA_OK;
+  }, sv_out != nullptr, a.rmax_key != nullptr);
+  if (rc) return rc;
   return epa::check_launch("sv_noise_fast_kernel");
 }
 
@@ -1214,10 +1158,24 @@ template <typename T>
 int launch_pass2(Args& a, const float* raw, const double* coef, const double* alpha2, const double* noise,
                  const int32_t* bin_start, void* noise_out, void* corr_out, void* mvbs_out, void* sum_out,
                  uint32_t* cnt_out, int C, size_t lds_acc_bytes, hipStream_t st) {
-  a.tab_off = (unsigned)((lds_acc_bytes + 15) & ~(size_t)15);
-  const size_t lds = a.tab_off + epa::kMathTabBytes;
+  const epa::BinLds lds = epa::bin_lds_layout(lds_acc_bytes);
+  a.tab_off = lds.tab_off;
   const dim3 grid((unsigned)a.n_tbins + 1u, (unsigned)C);
   a.flagged_only = 0;
+  // the three kernels of pass 2 take the same arguments and the same (WRITE_NOISE, WRITE_CORR, MINMAX)
+  enum Which { kUniform, kDrift, kGeneral };
+  auto run = [&](Which which, dim3 g, size_t bytes, const Args& ar) {
+    return epa::dispatch_flags([&](auto n, auto k, auto m) -> int {
+      constexpr bool N = decltype(n)::value, K = decltype(k)::value, M = decltype(m)::value;
+      auto kern = which == kUniform ? sv_denoise_mvbs_uniform_kernel<T, N, K, M>
+                  : which == kDrift ? sv_denoise_mvbs_drift_kernel<T, N, K, M>
+                                    : sv_denoise_mvbs_fast_kernel<T, N, K, M>;
+      if (int rc = epa::allow_lds(kern, bytes)) return rc;
+      hipLaunchKernelGGL(kern, g, dim3(epa::kBlock), bytes, st, raw, reinterpret_cast<const epa::CoefRow*>(coef), alpha2,
+                         noise, bin_start, (T*)noise_out, (T*)corr_out, (T*)mvbs_out, (T*)sum_out, cnt_out, ar);
+      return EPA_OK;
+    }, noise_out != nullptr, corr_out != nullptr, a.mm_keys != nullptr);
+  };
   static const bool uniform_off = [] {  // development knob: EPA_CHAIN_UNIFORM=0 leaves every group to the general kernel
     const char* e = getenv("EPA_CHAIN_UNIFORM");
     return e && e[0] == '0';
@@ -1227,69 +1185,21 @@ int launch_pass2(Args& a, const float* raw, const double* coef, const double* al
     // two time bins per workgroup (the per-column constants paid once for both) when both rows of accumulators fit
     Args au = a;
     au.uni_bins = (size_t)2 * a.n_rbins * (sizeof(T) + 4) + epa::kMathTabBytes <= 48 * 1024 ? 2 : 1;
-    const size_t usum = ((size_t)au.uni_bins * a.n_rbins * sizeof(T) + 15) & ~(size_t)15;
-    au.cnt_off = (unsigned)usum;
-    au.tab_off = (unsigned)((usum + (size_t)au.uni_bins * a.n_rbins * 4 + 15) & ~(size_t)15);
-    const size_t ulds = au.tab_off + epa::kMathTabBytes;
+    const size_t ulds = lay_out_lds<T>(au, (size_t)au.uni_bins * a.n_rbins);
     const dim3 ugrid((unsigned)((a.n_tbins + au.uni_bins - 1) / au.uni_bins), (unsigned)C);
-#define EPA_U2(N, K, M)                                                                                  \
-  do {                                                                                                   \
-    auto kern = sv_denoise_mvbs_uniform_kernel<T, N, K, M>;                                                 \
-    if (int rc = set_lds(kern, ulds)) return rc;                                                         \
-    hipLaunchKernelGGL(kern, ugrid, dim3(epa::kBlock), ulds, st, raw,                                    \
-                       reinterpret_cast<const epa::CoefRow*>(coef), alpha2, noise, bin_start,            \
-                       (T*)noise_out, (T*)corr_out, (T*)mvbs_out, (T*)sum_out, cnt_out, au);                \
-  } while (0)
-#define EPA_U2M(N, K)                                                                                    \
-  do {                                                                                                   \
-    if (a.mm_keys) EPA_U2(N, K, true); else EPA_U2(N, K, false);                                         \
-  } while (0)
-    if (noise_out) { if (corr_out) EPA_U2M(true, true); else EPA_U2M(true, false); }
-    else { if (corr_out) EPA_U2M(false, true); else EPA_U2M(false, false); }
-#undef EPA_U2M
-#undef EPA_U2
+    if (int rc = run(kUniform, ugrid, ulds, au)) return rc;
     if (int rc = epa::check_launch("sv_denoise_mvbs_uniform_kernel")) return rc;
     static const bool drift_off = [] {  // development knob: EPA_CHAIN_DRIFT=0 skips the sound-speed-drift kernel
       const char* e = getenv("EPA_CHAIN_DRIFT");
       return e && e[0] == '0';
     }();
     if (!drift_off) {
-#define EPA_D2(N, K, M)                                                                                  \
-  do {                                                                                                   \
-    auto kern = sv_denoise_mvbs_drift_kernel<T, N, K, M>;                                                 \
-    if (int rc = set_lds(kern, ulds)) return rc;                                                         \
-    hipLaunchKernelGGL(kern, ugrid, dim3(epa::kBlock), ulds, st, raw,                                    \
-                       reinterpret_cast<const epa::CoefRow*>(coef), alpha2, noise, bin_start,            \
-                       (T*)noise_out, (T*)corr_out, (T*)mvbs_out, (T*)sum_out, cnt_out, au);                \
-  } while (0)
-#define EPA_D2M(N, K)                                                                                    \
-  do {                                                                                                   \
-    if (a.mm_keys) EPA_D2(N, K, true); else EPA_D2(N, K, false);                                         \
-  } while (0)
-      if (noise_out) { if (corr_out) EPA_D2M(true, true); else EPA_D2M(true, false); }
-      else { if (corr_out) EPA_D2M(false, true); else EPA_D2M(false, false); }
-#undef EPA_D2M
-#undef EPA_D2
+      if (int rc = run(kDrift, ugrid, ulds, au)) return rc;
       if (int rc = epa::check_launch("sv_denoise_mvbs_drift_kernel")) return rc;
     }
     a.flagged_only = 1;
   }
-#define EPA_P2(N, K)                                                                                     \
-  do {                                                                                                   \
-    if (a.mm_keys) EPA_P2M(N, K, true); else EPA_P2M(N, K, false);                                       \
-  } while (0)
-#define EPA_P2M(N, K, M)                                                                                 \
-  do {                                                                                                   \
-    auto kern = sv_denoise_mvbs_fast_kernel<T, N, K, M>;                                                 \
-    if (int rc = set_lds(kern, lds)) return rc;                                                          \
-    hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds, st, raw,                                      \
-                       reinterpret_cast<const epa::CoefRow*>(coef), alpha2, noise, bin_start,            \
-                       (T*)noise_out, (T*)corr_out, (T*)mvbs_out, (T*)sum_out, cnt_out, a);              \
-  } while (0)
-  if (noise_out) { if (corr_out) EPA_P2(true, true); else EPA_P2(true, false); }
-  else { if (corr_out) EPA_P2(false, true); else EPA_P2(false, false); }
-#undef EPA_P2
-#undef EPA_P2M
+  if (int rc = run(kGeneral, grid, lds.total, a)) return rc;
   return epa::check_launch("sv_denoise_mvbs_fast_kernel");
 }
 

@@ -478,9 +478,7 @@ int launch(CxArgs& a, int max_taps, hipStream_t st) {
 #define EPA_CX(NBV)                                                                              \
   do {                                                                                           \
     auto kern = sv_complex_kernel<InT, T, A, NBV>;                                               \
-    if (lds > 64 * 1024)                                                                         \
-      EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                     \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
+    if (int rc = epa::allow_lds(kern, lds)) return rc;                                           \
     hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds, st, a);                               \
   } while (0)
   if (b4) EPA_CX(4); else EPA_CX(0);

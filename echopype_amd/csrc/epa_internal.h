@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "echopype_amd.h"
 
@@ -65,6 +66,31 @@ int dispatch_real(const char* who, int dtype, F&& f) {
   return EPA_EINVAL;
 }
 
+// Boolean template flags of a kernel, chosen in ONE place: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...).
+//   return epa::dispatch_flags([&](auto w, auto r) { return launch<T, decltype(w)::value, decltype(r)::value>(...); },
+//                              sv_out != nullptr, rmax_key != nullptr);
+// Every combination of the flags it is given is instantiated: a launcher that serves only some of them selects those
+// itself and hands dispatch_flags the flags that are free.
+template <typename F>
+auto dispatch_flags(F&& f) {
+  return f();
+}
+template <typename F, typename... Rest>
+auto dispatch_flags(F&& f, bool b0, Rest... rest) {
+  return b0 ? dispatch_flags([&](auto... t) { return f(std::true_type{}, t...); }, rest...)
+            : dispatch_flags([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
+
+// A launch with more than 64 KiB of dynamic LDS has to be allowed per kernel (the one definition of what each
+// translation unit once wrote out as its own set_lds).
+template <typename K>
+int allow_lds(K kern, size_t bytes) {
+  if (bytes > 64 * 1024)
+    EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)bytes));
+  return EPA_OK;
+}
+
 // Launch trace (epa_launch_trace in echopype_amd.h): while it is on, every kernel launch notes its name -- the tests
 // assert WHICH kernel served a call (a specialised kernel silently declining a shape otherwise passes every
 // "fast == generic" comparison as generic == generic).
@@ -89,6 +115,23 @@ inline int check_launch(const char* what) {
 
 constexpr int kBlock = 256;  // 4 wavefronts of 64
 constexpr int kMinmaxMaxGrid = 1024;  // the most workgroups (= partials in its workspace) of an epa_nanminmax launch
+
+// the LDS tables of fast_math.h (build_math_tabs): 256 x f64 for 10^x, 128 x (f64, f64) for log10
+constexpr int kExpTabN = 256;
+constexpr int kLogTabN = 128;
+constexpr size_t kExpTabBytes = kExpTabN * sizeof(double);
+constexpr size_t kLogTabBytes = kLogTabN * 2 * sizeof(double);
+constexpr size_t kMathTabBytes = kExpTabBytes + kLogTabBytes;  // 4 KiB
+
+// Dynamic LDS of a kernel that bins into LDS accumulators: the accumulators, then (16-byte aligned) the math tables
+struct BinLds {
+  unsigned tab_off;
+  size_t total;
+};
+inline BinLds bin_lds_layout(size_t acc_bytes) {
+  const size_t tab_off = (acc_bytes + 15) & ~(size_t)15;
+  return {(unsigned)tab_off, tab_off + kMathTabBytes};
+}
 
 // may the 16-byte accesses of a vectorised kernel be used on this buffer?  (an optional buffer that is not given: yes)
 inline bool al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

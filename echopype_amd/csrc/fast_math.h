@@ -14,12 +14,7 @@
 
 namespace epa {
 
-constexpr int kExpTabN = 256;
-constexpr int kLogTabN = 128;
-constexpr size_t kExpTabBytes = kExpTabN * sizeof(double);
-constexpr size_t kLogTabBytes = kLogTabN * 2 * sizeof(double);
-constexpr size_t kMathTabBytes = kExpTabBytes + kLogTabBytes;  // 4 KiB
-
+// (kExpTabN, kLogTabN and the byte sizes: epa_internal.h, where the host lays the LDS out)
 struct MathTabs {
   const double* exp2_tab;  // [256]
   const double2* log_tab;  // [128] (inv, log10c)

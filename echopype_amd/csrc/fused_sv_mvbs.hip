@@ -17,6 +17,7 @@
 #include "fast_math.h"
 #include "ordered_key.h"
 #include "sample_math.h"
+#include "time_bin.h"
 
 namespace epa_fused {
 
@@ -43,7 +44,6 @@ struct Args {
 using epa::kKeyNoMax;
 using epa::kKeyNoMin;
 using epa::key_value;
-using epa::lds_add;
 using epa::ordered_key;
 using epa::vmax_num;
 using epa::vmin_num;
@@ -55,38 +55,12 @@ __device__ __noinline__ T log10_slow(T x) {
 
 // Lane-private state of one range column (kept across the pings of a time bin).
 template <typename T>
-struct Column {
-  double sra;       // fl(s * ra): first factor of the range product (range.py:138 order)
-  double blo, bhi;  // edges of the range bin the column currently sits in (empty: blo > bhi)
-  T nL;             // n * log10(s - d)
-  T acc_sum;
-  int acc_rb;
-  uint32_t acc_cnt;
+struct Column : epa::BinCursor<T> {
+  double sra;  // fl(s * ra): first factor of the range product (range.py:138 order)
+  T nL;        // n * log10(s - d)
   __device__ __forceinline__ void init() {
-    sra = 0.0; blo = 1.0; bhi = 0.0; nL = epa::M<T>::nan(); acc_sum = (T)0; acc_rb = -1; acc_cnt = 0u;
-  }
-  // ``n_clean``: the pings of this chunk the whole wavefront took on the lean path so far (a scalar: every column of
-  // every lane got one valid value from each of them).  A column counts only what the general path added, relative to
-  // the scalar's value when the column last changed its bin: values in the bin = acc_cnt + n_clean (mod 2^32).
-  __device__ __forceinline__ void flush(T* lsum, uint32_t* lcnt, uint32_t n_clean) {
-    const uint32_t n = acc_cnt + n_clean;
-    if (acc_rb >= 0 && n > 0u) {
-      lds_add(lsum + acc_rb, acc_sum);
-      atomicAdd(lcnt + acc_rb, n);
-    }
-  }
-  // the column has left the range bin it sat in: find the new one (``valid`` false: a NaN raw sample, parked outside)
-  __device__ __forceinline__ void rebin(double x, bool valid, double bin, double inv_bin, int n_rbins, T* lsum,
-                                        uint32_t* lcnt, uint32_t n_clean) {
-    const int rb = valid ? epa::range_bin_index(x, bin, inv_bin, n_rbins, false) : -1;
-    if (rb != acc_rb) {
-      flush(lsum, lcnt, n_clean);
-      acc_rb = rb;
-      acc_sum = (T)0;
-      acc_cnt = 0u - n_clean;
-    }
-    blo = rb >= 0 ? (double)rb * bin : 1.0;
-    bhi = rb >= 0 ? (double)(rb + 1) * bin : 0.0;
+    epa::BinCursor<T>::init();
+    sra = 0.0; nL = epa::M<T>::nan();
   }
 };
 
@@ -117,8 +91,8 @@ __device__ __forceinline__ float lin_bins(float u, const double*) { return ::exp
 template <typename T, bool STATS>
 __device__ __forceinline__ T process_sample(Column<T>& c, float raw, const epa::CoefRow& r, double r0v, T g, T a2,
                                             T A0v, T nL, T nspread, double bin, double inv_bin, int n_rbins,
-                                            const double* tab, T* lsum, uint32_t* lcnt, double& xmax, double& xmin,
-                                            unsigned& nnan, uint32_t n_clean) {
+                                            const double* tab, const epa::BinAcc<T>& acc, double& xmax,
+                                            double& xmin, unsigned& nnan, uint32_t n_clean) {
   const T NaN = epa::M<T>::nan();
   const double x = fma(c.sra, r.rb, r0v);  // echo_range = (s*ra)*rb [+0]
   if (STATS) {
@@ -141,8 +115,7 @@ __device__ __forceinline__ T process_sample(Column<T>& c, float raw, const epa::
   const T v = epa::lin_from_db_lean(sv, tab);  // (+-inf through a rare branch)
   // still inside the bin of the previous ping?  (A NaN raw sample makes Sv and v NaN: it is never accumulated, whatever
   // bin the column sits in; the slow path below still parks such a column outside the grid.)
-  const bool same = (x >= c.blo) & (x < c.bhi);
-  if (!same) c.rebin(x, raw == raw, bin, inv_bin, n_rbins, lsum, lcnt, n_clean);
+  if (!c.inside(x)) c.rebin(x, raw == raw, bin, inv_bin, n_rbins, acc, n_clean);
   // (a column outside the grid, acc_rb < 0, accumulates too: flush() drops it.)  v >= 0 or NaN: max(v, 0) adds nothing
   // for a NaN
   c.acc_sum += vmax_num(v, (T)0);
@@ -164,7 +137,7 @@ __device__ __forceinline__ T process_sample(Column<T>& c, float raw, const epa::
 template <typename T, bool STATS, bool WRITE_SV, int DEPTH>
 __device__ __forceinline__ void process_pair(Column<T>& c0, Column<T>& c1, float2 in, bool clean, const epa::CoefRow& r,
                                              double r0v, T g, T a2, T A0v, T nL0, T nL1, T nspread, double bin,
-                                             double inv_bin, int n_rbins, const double* tab, T* lsum, uint32_t* lcnt,
+                                             double inv_bin, int n_rbins, const double* tab, const epa::BinAcc<T>& acc,
                                              T* __restrict__ sv_dst, double& xmax, double& xmin, unsigned& nnan,
                                              uint32_t n_clean, double& xfirst, double& xlast, T dsc, T dof,
                                              T* __restrict__ depth_dst, double sra0, double sra1) {
@@ -224,8 +197,8 @@ __device__ __forceinline__ void process_pair(Column<T>& c0, Column<T>& c1, float
   }
   // still inside the bin of the previous ping?  (A NaN raw sample makes Sv and v NaN: it is never accumulated, whatever
   // bin the column sits in; rebin still parks such a column outside the grid.)
-  if (!((x0 >= c0.blo) & (x0 < c0.bhi))) c0.rebin(x0, in.x == in.x, bin, inv_bin, n_rbins, lsum, lcnt, n_clean);
-  if (!((x1 >= c1.blo) & (x1 < c1.bhi))) c1.rebin(x1, in.y == in.y, bin, inv_bin, n_rbins, lsum, lcnt, n_clean);
+  if (!c0.inside(x0)) c0.rebin(x0, in.x == in.x, bin, inv_bin, n_rbins, acc, n_clean);
+  if (!c1.inside(x1)) c1.rebin(x1, in.y == in.y, bin, inv_bin, n_rbins, acc, n_clean);
   if (clean) {
     c0.acc_sum += v0;
     c1.acc_sum += v1;
@@ -299,8 +272,7 @@ struct PingLoad<int16_t> {
   }
 };
 
-// Lane -> sample mapping inside a 1024-sample chunk (4 waves x 256 samples): lane l of wave w owns
-// the two PAIRS {base + 2l, +1} and {base + 128 + 2l, +1}, base = chunk0 + 256 w.  Every load
+// Lane -> sample mapping inside a 1024-sample chunk (4 waves x 256 samples): epa::PairLanes.  Every load
 // (8 B/lane) and every store (16 B/lane f64) of a wave is then one contiguous 512 B / 1 KiB
 // segment -- the 4-consecutive-samples-per-lane layout makes each f64 store instruction touch
 // only half of every 128-B line.
@@ -326,8 +298,7 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
     T* __restrict__ sum_out, uint32_t* __restrict__ cnt_out, const double* __restrict__ dscale,
     const double* __restrict__ doffset, Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* lsum = reinterpret_cast<T*>(smem);
-  uint32_t* lcnt = reinterpret_cast<uint32_t*>(smem + a.cnt_off);
+  const epa::BinAcc<T> acc(smem, a.cnt_off);
   const epa::MathTabs mt = epa::build_math_tabs(smem + a.tab_off);  // synchronised below
   const double* tab = mt.exp2_tab;
   // A column's cached n log10(s - d) lives in LDS, every lane its own four entries (written and read by the same lane:
@@ -355,10 +326,7 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
   const bool extra = tb == a.n_tbins;
   if (extra && !WRITE_SV) return;
   const int nseg = extra ? 2 : 1;
-  for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
-    lsum[i] = (T)0;
-    lcnt[i] = 0u;
-  }
+  acc.clear(n_rbins);
   __syncthreads();
 
   const T nspread = (T)a.nspread;
@@ -379,10 +347,10 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
   const int pb = extra ? (seg == 0 ? 0 : bin_start[a.n_tbins]) : bin_start[tb];
   const int pe = extra ? (seg == 0 ? bin_start[0] : a.P) : bin_start[tb + 1];
   for (int chunk0 = 0; chunk0 < S; chunk0 += kChunk) {
-    const int sA = chunk0 + wave * 256 + 2 * lane;  // first sample of pair A
-    const int sB = sA + 128;                        // first sample of pair B
+    const epa::PairLanes lm(chunk0, wave, lane, S);
+    const int sA = lm.sA, sB = lm.sB;
     if (sA >= S) continue;
-    const bool hasB = sB < S;
+    const bool hasB = lm.hasB;
     Column<T> col[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) col[j].init();
@@ -430,11 +398,11 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
         racur = __double_as_longlong(r.ra);
         bool fin = true;
         for (int j = 0; j < VEC; ++j) {
-          const double sj = (double)((j < 2 ? sA : sB) + (j & 1));
+          const double sj = (double)lm.sample(j);
           const T nl = nspread * log10_slow<T>((T)(sj - r.d));
-          if (NL_LDS) col_nL[eA + (j < 2 ? 0 : 128) + (j & 1)] = nl;  // (see col_nL)
+          if (NL_LDS) col_nL[eA + lm.offset(j)] = nl;  // (see col_nL)
           else col[j].nL = nl;
-          if (SRA_LDS) col_sra[eA + (j < 2 ? 0 : 128) + (j & 1)] = sj * r.ra;
+          if (SRA_LDS) col_sra[eA + lm.offset(j)] = sj * r.ra;
           else col[j].sra = sj * r.ra;
           fin = fin & ((j >= 2 && !hasB) | (fabs(nl) < (T)__builtin_inf()));
         }
@@ -464,14 +432,14 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
       const T dsc = (T)curDs, dof = (T)curDo;
       double xf, xl, xdummy;
       process_pair<T, RMAX, WRITE_SV, DEPTH>(col[0], col[1], inA, clean, r, r0v, g, a2, A0, NL_LDS ? col_nL[eA] : col[0].nL,
-                                             NL_LDS ? col_nL[eA + 1] : col[1].nL, nspread, bin, inv_bin, n_rbins, tab, lsum,
-                                             lcnt, WRITE_SV ? sv_c + row_off + sA : nullptr, xmax, xmin, nnan, n_clean, xf,
+                                             NL_LDS ? col_nL[eA + 1] : col[1].nL, nspread, bin, inv_bin, n_rbins, tab, acc,
+                                             WRITE_SV ? sv_c + row_off + sA : nullptr, xmax, xmin, nnan, n_clean, xf,
                                              xl, dsc, dof, DEPTH == 2 ? dp_c + row_off + sA : nullptr,
                                              SRA_LDS ? col_sra[eA] : col[0].sra, SRA_LDS ? col_sra[eA + 1] : col[1].sra);
       if (hasB)
         process_pair<T, RMAX, WRITE_SV, DEPTH>(col[2], col[3], inB, clean, r, r0v, g, a2, A0,
                                                NL_LDS ? col_nL[eA + 128] : col[2].nL, NL_LDS ? col_nL[eA + 129] : col[3].nL,
-                                               nspread, bin, inv_bin, n_rbins, tab, lsum, lcnt,
+                                               nspread, bin, inv_bin, n_rbins, tab, acc,
                                                WRITE_SV ? sv_c + row_off + sB : nullptr, xmax, xmin, nnan, n_clean, xdummy,
                                                xl, dsc, dof, DEPTH == 2 ? dp_c + row_off + sB : nullptr,
                                                SRA_LDS ? col_sra[eA + 128] : col[2].sra,
@@ -490,7 +458,7 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
       }
     }
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) col[j].flush(lsum, lcnt, n_clean);
+    for (int j = 0; j < VEC; ++j) col[j].flush(acc, n_clean);
   }
   }
   if (RMAX) {
@@ -522,16 +490,7 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
   if (extra) return;
   __syncthreads();
   const size_t cell0 = ((size_t)c * a.n_tbins + tb) * n_rbins;
-  T* out = mvbs_out + cell0;
-  T* gsum = sum_out ? sum_out + cell0 : nullptr;
-  uint32_t* gcnt = cnt_out ? cnt_out + cell0 : nullptr;
-  for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
-    const uint32_t n = lcnt[i];
-    const T s = lsum[i];
-    out[i] = n > 0u ? (T)10 * epa::M<T>::log10(s / (T)n) : (T)a.fill_value;
-    if (gsum) gsum[i] = s;
-    if (gcnt) gcnt[i] = n;
-  }
+  acc.store(mvbs_out, sum_out, cnt_out, cell0, n_rbins, (T)a.fill_value);
 }
 
 template <typename T, typename RawT>
@@ -539,37 +498,35 @@ int launch(Args& a, const RawT* raw, const int32_t* n_valid, const double* coef,
            void* sv_out, void* mvbs_out, void* sum_out, uint32_t* cnt_out, int C, size_t lds_bytes,
            hipStream_t st) {
   const dim3 grid((unsigned)a.n_tbins + 1u, (unsigned)C);  // +1: pings outside every time bin
-  a.tab_off = (unsigned)((lds_bytes + 15) & ~(size_t)15);
-  lds_bytes = a.tab_off + epa::kMathTabBytes;
+  const epa::BinLds lds = epa::bin_lds_layout(lds_bytes);
+  a.tab_off = lds.tab_off;
   a.xcd_map = epa::xcd_map_enabled() ? 1 : 0;
-#define EPA_FL(W, R) EPA_FLD(W, R, 0)
-#define EPA_FLD(W, R, D)                                                                       \
-  do {                                                                                         \
-    auto kern = fused_sv_mvbs_kernel<T, RawT, W, R, D>;                                        \
-    if (lds_bytes > 64 * 1024)                                                                 \
-      EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                   \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                        (int)lds_bytes));                                      \
-    hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds_bytes, st, raw, n_valid,             \
-                       reinterpret_cast<const epa::CoefRow*>(coef), bin_start, (T*)sv_out,     \
-                       (T*)mvbs_out, (T*)sum_out, cnt_out, a.dscale, a.doffset, a);            \
-  } while (0)
+  // one (WRITE_SV, RMAX, DEPTH) instance; only the combinations selected below exist
+  auto run = [&](auto w, auto r, auto d) -> int {
+    auto kern = fused_sv_mvbs_kernel<T, RawT, decltype(w)::value, decltype(r)::value, decltype(d)::value>;
+    if (int rc = epa::allow_lds(kern, lds.total)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds.total, st, raw, n_valid,
+                       reinterpret_cast<const epa::CoefRow*>(coef), bin_start, (T*)sv_out, (T*)mvbs_out, (T*)sum_out,
+                       cnt_out, a.dscale, a.doffset, a);
+    return EPA_OK;
+  };
+  using Depth0 = std::integral_constant<int, 0>;
+  using Depth1 = std::integral_constant<int, 1>;
+  using Depth2 = std::integral_constant<int, 2>;
+  int rc;
   if (a.dscale) {  // binned on depth (float samples, always with the statistics of the depth)
     if constexpr (std::is_same<RawT, float>::value) {
-      if (a.depth_out) EPA_FLD(true, true, 2);
-      else if (sv_out) EPA_FLD(true, true, 1);
-      else EPA_FLD(false, true, 1);
+      if (a.depth_out) rc = run(std::true_type{}, std::true_type{}, Depth2{});
+      else rc = epa::dispatch_flags([&](auto w) { return run(w, std::true_type{}, Depth1{}); }, sv_out != nullptr);
     } else {
       epa::set_error("epa_sv_mvbs_fused_depth: float power samples only");
       return EPA_EUNSUPPORTED;
     }
-  } else if (a.rmax_key) {
-    if (sv_out) EPA_FL(true, true); else EPA_FL(false, true);
   } else {
-    if (sv_out) EPA_FL(true, false); else EPA_FL(false, false);
+    rc = epa::dispatch_flags([&](auto w, auto r) { return run(w, r, Depth0{}); }, sv_out != nullptr,
+                             a.rmax_key != nullptr);
   }
-#undef EPA_FLD
-#undef EPA_FL
+  if (rc) return rc;
   return epa::check_launch("fused_sv_mvbs_kernel");
 }
 
@@ -612,38 +569,21 @@ __global__ __launch_bounds__(epa::kBlock) void selftest_log_inl_kernel(const dou
 // lane-private accumulation over the pings of a time bin; a NaN Sv is skipped (skipna), a NaN coefficient row bins
 // nothing.
 template <typename T>
-struct SvColumn {
-  double sra, blo, bhi;
-  T acc_sum;
-  int acc_rb;
-  uint32_t acc_cnt;
-  __device__ __forceinline__ void init() { sra = 0.0; blo = 1.0; bhi = 0.0; acc_sum = (T)0; acc_rb = -1; acc_cnt = 0u; }
-  __device__ __forceinline__ void flush(T* lsum, uint32_t* lcnt) {
-    if (acc_rb >= 0 && acc_cnt > 0u) {
-      lds_add(lsum + acc_rb, acc_sum);
-      atomicAdd(lcnt + acc_rb, acc_cnt);
-    }
+struct SvColumn : epa::BinCursor<T> {
+  double sra;
+  __device__ __forceinline__ void init() {
+    epa::BinCursor<T>::init();
+    sra = 0.0;
   }
 };
 
 template <typename T, bool AS_STORED>
 __device__ __forceinline__ void bin_sv_sample(SvColumn<T>& c, T sv, const epa::CoefRow& r, double bin, double inv_bin,
-                                              int n_rbins, const double* tab, T* lsum, uint32_t* lcnt) {
+                                              int n_rbins, const double* tab, const epa::BinAcc<T>& acc) {
   const double x0 = c.sra * r.rb + r.r0;
   const double x = AS_STORED ? (double)(T)x0 : x0;
   const T v = epa::lin_from_db(sv, tab);
-  const bool same = (x >= c.blo) & (x < c.bhi);
-  if (!same) {
-    const int rb = (x == x) ? epa::range_bin_index(x, bin, inv_bin, n_rbins, false) : -1;
-    if (rb != c.acc_rb) {
-      c.flush(lsum, lcnt);
-      c.acc_rb = rb;
-      c.acc_sum = (T)0;
-      c.acc_cnt = 0u;
-    }
-    c.blo = rb >= 0 ? (double)rb * bin : 1.0;
-    c.bhi = rb >= 0 ? (double)(rb + 1) * bin : 0.0;
-  }
+  if (!c.inside(x)) c.rebin(x, x == x, bin, inv_bin, n_rbins, acc, 0u);
   const bool take = (c.acc_rb >= 0) & (v == v);
   c.acc_sum += take ? v : (T)0;
   c.acc_cnt += take ? 1u : 0u;
@@ -668,8 +608,7 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 6 : 8) void mvbs_of_s
     T* __restrict__ mvbs_out, T* __restrict__ sum_out, uint32_t* __restrict__ cnt_out, Args a) {
   typedef T T2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* lsum = reinterpret_cast<T*>(smem);
-  uint32_t* lcnt = reinterpret_cast<uint32_t*>(smem + a.cnt_off);
+  const epa::BinAcc<T> acc(smem, a.cnt_off);
   const epa::MathTabs mt = epa::build_math_tabs(smem + a.tab_off);  // synchronised below
   const double* tab = mt.exp2_tab;
   __shared__ int differs;
@@ -678,10 +617,7 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 6 : 8) void mvbs_of_s
   const int S = a.S, n_rbins = a.n_rbins;
   const int pb = bin_start[tb], pe = bin_start[tb + 1], np = pe - pb;
   const size_t cell0 = ((size_t)c * a.n_tbins + tb) * n_rbins;
-  for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
-    lsum[i] = (T)0;
-    lcnt[i] = 0u;
-  }
+  acc.clear(n_rbins);
   if (threadIdx.x == 0) {
     differs = np > kFixedPings ? 1 : 0;
     rb_lo_key = kKeyNoMin;
@@ -710,17 +646,17 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 6 : 8) void mvbs_of_s
     return AS_STORED ? (double)(T)x0 : x0;
   };
   for (int chunk0 = 0; chunk0 < S; chunk0 += kChunk) {
-    const int sA = chunk0 + wave * 256 + 2 * lane;  // first sample of pair A
-    const int sB = sA + 128;                        // first sample of pair B
+    const epa::PairLanes lm(chunk0, wave, lane, S);
+    const int sA = lm.sA, sB = lm.sB;
     if (sA >= S) continue;
-    const bool hasB = sB < S;
+    const bool hasB = lm.hasB;
     int rbin[VEC];
     T acc_sum[VEC];
     uint32_t acc_cnt[VEC];
     unsigned fixed = 0;
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const int sx = (j < 2 ? sA : sB) + (j & 1);
+      const int sx = lm.sample(j);
       const int b_lo = epa::range_bin_index(range_of(sx, rb_lo), bin, inv_bin, n_rbins, false);
       const int b_hi = epa::range_bin_index(range_of(sx, rb_hi), bin, inv_bin, n_rbins, false);
       rbin[j] = b_lo;
@@ -760,13 +696,10 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 6 : 8) void mvbs_of_s
     }
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      if (((fixed >> j) & 1u) != 0u && rbin[j] >= 0 && acc_cnt[j] > 0u) {
-        lds_add(lsum + rbin[j], acc_sum[j]);
-        atomicAdd(lcnt + rbin[j], acc_cnt[j]);
-      }
+      if (((fixed >> j) & 1u) != 0u && rbin[j] >= 0 && acc_cnt[j] > 0u) acc.add(rbin[j], acc_sum[j], acc_cnt[j]);
     }
     // the columns near a range-bin edge: one at a time, the lanes spread over the pings
-    const unsigned loose = (~fixed) & (hasB ? 0xfu : 0x3u);
+    const unsigned loose = (~fixed) & lm.have();
     if (__ballot(loose != 0u) != 0ull) {
       // the lanes still here are 0 .. nact - 1 (sA grows with the lane): in the row's last, partial wavefront only
       // they exist to share the pings, so the stride is their number, not 64
@@ -777,31 +710,19 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 6 : 8) void mvbs_of_s
         while (todo != 0ull) {  // (wave-uniform)
           const int src = __ffsll((long long)todo) - 1;
           todo &= todo - 1ull;
-          const int sx = chunk0 + wave * 256 + 2 * src + (j < 2 ? 0 : 128) + (j & 1);
+          const int sx = epa::PairLanes::sample_of(chunk0, wave, src, j);
           for (int p = pb + lane; p < pe; p += nact) {
             const T v = epa::lin_from_db_lean(sv_c[(size_t)p * S + sx], tab);
             const double x = range_of(sx, rowp0[p].rb);
             const int rb = epa::range_bin_index(x, bin, inv_bin, n_rbins, false);
-            if ((rb >= 0) & (v == v)) {
-              lds_add(lsum + rb, v);
-              atomicAdd(lcnt + rb, 1u);
-            }
+            if ((rb >= 0) & (v == v)) acc.add(rb, v, 1u);
           }
         }
       }
     }
   }
   __syncthreads();
-  T* out = mvbs_out + cell0;
-  T* gsum = sum_out ? sum_out + cell0 : nullptr;
-  uint32_t* gcnt = cnt_out ? cnt_out + cell0 : nullptr;
-  for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
-    const uint32_t n = lcnt[i];
-    const T s = lsum[i];
-    out[i] = n > 0u ? (T)10 * epa::M<T>::log10(s / (T)n) : (T)a.fill_value;
-    if (gsum) gsum[i] = s;
-    if (gcnt) gcnt[i] = n;
-  }
+  acc.store(mvbs_out, sum_out, cnt_out, cell0, n_rbins, (T)a.fill_value);
 }
 
 template <typename T, bool AS_STORED>
@@ -810,17 +731,13 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES) void mvbs_of_sv_r
     T* __restrict__ mvbs_out, T* __restrict__ sum_out, uint32_t* __restrict__ cnt_out, Args a) {
   typedef T T2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* lsum = reinterpret_cast<T*>(smem);
-  uint32_t* lcnt = reinterpret_cast<uint32_t*>(smem + a.cnt_off);
+  const epa::BinAcc<T> acc(smem, a.cnt_off);
   const epa::MathTabs mt = epa::build_math_tabs(smem + a.tab_off);  // synchronised below
   const double* tab = mt.exp2_tab;
   const int c = blockIdx.y, tb = a.xcd_map ? epa::xcd_contiguous(blockIdx.x, a.n_tbins) : (int)blockIdx.x;
   const int S = a.S, n_rbins = a.n_rbins;
   if (a.flagged_only && !LeftToRows::is_marked(mvbs_out + ((size_t)c * a.n_tbins + tb) * n_rbins)) return;  // (uniform)
-  for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
-    lsum[i] = (T)0;
-    lcnt[i] = 0u;
-  }
+  acc.clear(n_rbins);
   __syncthreads();
   const double bin = a.range_bin, inv_bin = a.inv_range_bin;
   const epa::CoefRow* __restrict__ rowp0 = coef + (size_t)c * a.P;
@@ -828,10 +745,10 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES) void mvbs_of_sv_r
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int pb = bin_start[tb], pe = bin_start[tb + 1];
   for (int chunk0 = 0; chunk0 < S; chunk0 += kChunk) {
-    const int sA = chunk0 + wave * 256 + 2 * lane;  // first sample of pair A
-    const int sB = sA + 128;                        // first sample of pair B
+    const epa::PairLanes lm(chunk0, wave, lane, S);
+    const int sA = lm.sA, sB = lm.sB;
     if (sA >= S) continue;
-    const bool hasB = sB < S;
+    const bool hasB = lm.hasB;
     SvColumn<T> col[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) col[j].init();
@@ -854,61 +771,50 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES) void mvbs_of_sv_r
       }
       if (!(r.ra == racur)) {  // uniform; once per column for a file with a constant sample_interval
         racur = r.ra;
-        for (int j = 0; j < VEC; ++j) col[j].sra = (double)((j < 2 ? sA : sB) + (j & 1)) * r.ra;
+        for (int j = 0; j < VEC; ++j) col[j].sra = (double)lm.sample(j) * r.ra;
       }
-      bin_sv_sample<T, AS_STORED>(col[0], inA.x, r, bin, inv_bin, n_rbins, tab, lsum, lcnt);
-      bin_sv_sample<T, AS_STORED>(col[1], inA.y, r, bin, inv_bin, n_rbins, tab, lsum, lcnt);
+      bin_sv_sample<T, AS_STORED>(col[0], inA.x, r, bin, inv_bin, n_rbins, tab, acc);
+      bin_sv_sample<T, AS_STORED>(col[1], inA.y, r, bin, inv_bin, n_rbins, tab, acc);
       if (hasB) {
-        bin_sv_sample<T, AS_STORED>(col[2], inB.x, r, bin, inv_bin, n_rbins, tab, lsum, lcnt);
-        bin_sv_sample<T, AS_STORED>(col[3], inB.y, r, bin, inv_bin, n_rbins, tab, lsum, lcnt);
+        bin_sv_sample<T, AS_STORED>(col[2], inB.x, r, bin, inv_bin, n_rbins, tab, acc);
+        bin_sv_sample<T, AS_STORED>(col[3], inB.y, r, bin, inv_bin, n_rbins, tab, acc);
       }
     }
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) col[j].flush(lsum, lcnt);
+    for (int j = 0; j < VEC; ++j) col[j].flush(acc, 0u);
   }
   __syncthreads();
   const size_t cell0 = ((size_t)c * a.n_tbins + tb) * n_rbins;
-  T* out = mvbs_out + cell0;
-  T* gsum = sum_out ? sum_out + cell0 : nullptr;
-  uint32_t* gcnt = cnt_out ? cnt_out + cell0 : nullptr;
-  for (int i = threadIdx.x; i < n_rbins; i += epa::kBlock) {
-    const uint32_t n = lcnt[i];
-    const T s = lsum[i];
-    out[i] = n > 0u ? (T)10 * epa::M<T>::log10(s / (T)n) : (T)a.fill_value;
-    if (gsum) gsum[i] = s;
-    if (gcnt) gcnt[i] = n;
-  }
+  acc.store(mvbs_out, sum_out, cnt_out, cell0, n_rbins, (T)a.fill_value);
 }
 
 template <typename T>
 int launch_sv_rows(Args& a, const void* sv, const double* coef, const int32_t* bin_start, void* mvbs_out, void* sum_out,
                    uint32_t* cnt_out, int C, size_t lds_bytes, bool as_stored, hipStream_t st) {
   const dim3 grid((unsigned)a.n_tbins, (unsigned)C);
-  a.tab_off = (unsigned)((lds_bytes + 15) & ~(size_t)15);
-  lds_bytes = a.tab_off + epa::kMathTabBytes;
+  const epa::BinLds lds = epa::bin_lds_layout(lds_bytes);
+  a.tab_off = lds.tab_off;
   a.xcd_map = epa::xcd_map_enabled() ? 1 : 0;
   static const bool fixed_off = [] {  // development knob: EPA_MVBS_FIXED=0 sends every time bin to the per-sample form
     const char* e = getenv("EPA_MVBS_FIXED");
     return e && e[0] == '0';
   }();
-#define EPA_SR(KERN, AS)                                                                                 \
-  do {                                                                                                   \
-    auto kern = KERN<T, AS>;                                                                             \
-    if (lds_bytes > 64 * 1024)                                                                           \
-      EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                             \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));    \
-    hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds_bytes, st, (const T*)sv,                       \
-                       reinterpret_cast<const epa::CoefRow*>(coef), bin_start, (T*)mvbs_out, (T*)sum_out, \
-                       cnt_out, a);                                                                      \
-  } while (0)
+  auto run = [&](bool fixed) {  // (the two kernels take the same arguments)
+    return epa::dispatch_flags([&](auto as) -> int {
+      auto kern = fixed ? mvbs_of_sv_fixed_kernel<T, decltype(as)::value> : mvbs_of_sv_rows_kernel<T, decltype(as)::value>;
+      if (int rc = epa::allow_lds(kern, lds.total)) return rc;
+      hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds.total, st, (const T*)sv,
+                         reinterpret_cast<const epa::CoefRow*>(coef), bin_start, (T*)mvbs_out, (T*)sum_out, cnt_out, a);
+      return EPA_OK;
+    }, as_stored);
+  };
   a.flagged_only = 0;
   if (!fixed_off) {
-    if (as_stored) EPA_SR(mvbs_of_sv_fixed_kernel, true); else EPA_SR(mvbs_of_sv_fixed_kernel, false);
+    if (int rc = run(true)) return rc;
     if (int rc = epa::check_launch("mvbs_of_sv_fixed_kernel")) return rc;
     a.flagged_only = 1;
   }
-  if (as_stored) EPA_SR(mvbs_of_sv_rows_kernel, true); else EPA_SR(mvbs_of_sv_rows_kernel, false);
-#undef EPA_SR
+  if (int rc = run(false)) return rc;
   return epa::check_launch("mvbs_of_sv_rows_kernel");
 }
 

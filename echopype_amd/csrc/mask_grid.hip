@@ -306,9 +306,7 @@ template <bool AL, bool PER_PING, bool USE_LDS>
 int launch_regrid_sweep(const RegridArgs& a, dim3 grid, hipStream_t st) {
   auto kern = regrid_sweep_kernel<AL, PER_PING, USE_LDS>;
   const size_t lds = USE_LDS ? (((size_t)a.n_rbins * 4 + 15) & ~(size_t)15) : 0;
-  if (lds > 64 * 1024)
-    EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
+  if (int rc = epa::allow_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, a);
   return EPA_OK;
 }

@@ -232,9 +232,7 @@ extern "C" int epa_nasc(const void* sv, const void* depth, int C, int P, int S, 
   return epa::dispatch_real("epa_nasc", dtype, [&](auto tag) -> int {
     using T = typename decltype(tag)::type;
     auto kern = use_lds ? nasc_accumulate_kernel<T, true> : nasc_accumulate_kernel<T, false>;
-    if (lds > 64 * 1024)
-      EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = epa::allow_lds(kern, lds)) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, (const T*)sv, (const T*)depth, P, S, bin_start, n_dbins,
                        (int)nparts, range_bin, 1.0 / range_bin, n_rbins, cr, (Cell*)workspace);
     if (int rc = epa::check_launch("nasc_accumulate_kernel")) return rc;

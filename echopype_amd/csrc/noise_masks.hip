@@ -3194,14 +3194,6 @@ __global__ __launch_bounds__(kBlock) void mask_and_kernel(const uint8_t* __restr
 
 inline int row_grid(long long rows) { return (int)(rows < 65536 ? (rows > 0 ? rows : 1) : 65536); }
 
-template <typename K>
-int set_lds(K kern, size_t lds) {
-  if (lds > 64 * 1024)
-    EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return EPA_OK;
-}
-
 constexpr size_t kMaxLds = 156 * 1024;
 
 // dynamic LDS of pool_median_slide_kernel for a ring of W window elements
@@ -3234,7 +3226,7 @@ extern "C" int epa_range_bin_smooth(const void* sv, const void* range, int C, in
   return epa::dispatch_real("epa_range_bin_smooth", dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     auto kern = range ? range_bin_smooth_kernel<T, true> : range_bin_smooth_kernel<T, false>;
-    if (int rc = set_lds(kern, lds)) return rc;
+    if (int rc = epa::allow_lds(kern, lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(row_grid(rows)), dim3(kBlock), lds, st, (const T*)sv, (const T*)range, rows, S, nper,
                        r0, delta, nbins, seg_bins, (T*)up_out);
     return epa::check_launch("range_bin_smooth_kernel");
@@ -3284,7 +3276,7 @@ extern "C" int epa_pool_sv(const void* sv, int C, int P, int S, int first_sample
         a.sv = (const T*)sv; a.P = P; a.S = S; a.n = n; a.nseg = nseg; a.jobs = jobs; a.thr = (T)threshold;
         a.pooled = (T*)pooled_out; a.mask = mask_out; a.cap = (int)W; a.s0 = s0; a.m = m;
         auto kern = pool_median_slide_kernel<T, false>;
-        if (int rc = set_lds(kern, slide_lds)) return rc;
+        if (int rc = epa::allow_lds(kern, slide_lds)) return rc;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), slide_lds, st, a);
         return epa::check_launch("pool_median_slide_kernel");
       }
@@ -3308,13 +3300,13 @@ extern "C" int epa_pool_sv(const void* sv, int C, int P, int S, int first_sample
       const size_t lds = epa::kMathTabBytes + (2 * ninp + 2 * kBlock) * 8 + (2 * ninp + 2 * kBlock) * 2;
       const dim3 g1(row_grid(rows) < 16384 ? row_grid(rows) : 16384, (S - s0 + kScanTile - 1) / kScanTile);
       auto kern = box_range_scan_kernel<T>;
-      if (int rc = set_lds(kern, lds)) return rc;
+      if (int rc = epa::allow_lds(kern, lds)) return rc;
       hipLaunchKernelGGL(kern, g1, dim3(kBlock), lds, st, (const T*)sv, rows, S, s0, m, ws_sum, ws_cnt);
       if (int rc = epa::check_launch("box_range_scan_kernel")) return rc;
     } else if (s0 < S) {
       const dim3 g1(row_grid(rows) < 16384 ? row_grid(rows) : 16384, (S - s0 + kRangeTile - 1) / kRangeTile);
       auto kern = box_range_kernel<T>;
-      if (int rc = set_lds(kern, lds1)) return rc;
+      if (int rc = epa::allow_lds(kern, lds1)) return rc;
       hipLaunchKernelGGL(kern, g1, dim3(kBlock), lds1, st, (const T*)sv, rows, S, s0, m, ws_sum, ws_cnt);
       if (int rc = epa::check_launch("box_range_kernel")) return rc;
     }
@@ -3441,7 +3433,7 @@ int launch_pool_value(const void* sv, const void* range, const int32_t* nvalid, 
       FuseArgs fa{differ, nvalid, ilo, ihi, rh, rn, P, fuse ? 1 : 0, nullptr, fuse ? need_w : nullptr};
       if (fuse) {
         auto kern = row_interval_blocks_kernel<T>;
-        if (int rc = set_lds(kern, fuse_lds)) return rc;
+        if (int rc = epa::allow_lds(kern, fuse_lds)) return rc;
         hipLaunchKernelGGL(kern, rowg, dim3(kBlock), fuse_lds, st, (const T*)sv, rows, S, fa);
         if (int rc = epa::check_launch("row_interval_blocks_kernel")) return rc;
         if (elig) {
@@ -3517,7 +3509,7 @@ int launch_pool_value(const void* sv, const void* range, const int32_t* nvalid, 
     ma.cap = kMedValueCap; ma.pv = a; ma.ilo = ilo; ma.ihi = ihi; ma.differ = differ;
     const size_t lds = med_slide_lds(kMedValueCap);
     auto kern = pool_median_slide_kernel<T, true>;
-    if (int rc = set_lds(kern, lds)) return rc;
+    if (int rc = epa::allow_lds(kern, lds)) return rc;
     const int grid = (int)(ma.jobs < (1 << 22) ? ma.jobs : (1 << 22));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, ma);
     return epa::check_launch("pool_value_median_slide_kernel");

@@ -154,6 +154,27 @@ __device__ __forceinline__ void store_vec<float, 1>(float* p, const float (&v)[1
 //   f32 outputs: 4 consecutive samples per lane (16-B load, 16-B store)            NSEG=1, LEN=4
 //   f64 outputs: two pairs per lane, {2l, 2l+1} and {128+2l, 128+2l+1} within the wave's 256
 //                samples (8-B loads of the f32 input, 16-B stores / loads of f64)    NSEG=2, LEN=2
+// The pair map is PairLanes (the time-bin kernels use it for either output type): lane l of wave w owns the pairs
+// A = {sA, sA + 1} and B = {sB, sB + 1}, sA = chunk0 + 256 w + 2 l, sB = sA + 128; pair B only where sB < S (the row's
+// last wavefront).  The kernels that keep four range columns per lane number them j = 0, 1 (pair A), 2, 3 (pair B).
+struct PairLanes {
+  int sA, sB;  // first sample of pair A, of pair B
+  bool hasB;
+  __device__ __forceinline__ PairLanes(int chunk0, int wave, int lane, int S)
+      : sA(first(chunk0, wave, lane, 0)), sB(sA + 128), hasB(sB < S) {}
+  static __device__ __forceinline__ int first(int chunk0, int wave, int lane, int seg) {
+    return chunk0 + wave * 256 + seg * 128 + 2 * lane;
+  }
+  // column j relative to the lane's first sample (also: the lane's entry j of a per-chunk LDS array)
+  static __device__ __forceinline__ int offset(int j) { return (j < 2 ? 0 : 128) + (j & 1); }
+  __device__ __forceinline__ int sample(int j) const { return (j < 2 ? sA : sB) + (j & 1); }
+  __device__ __forceinline__ unsigned have() const { return hasB ? 0xfu : 0x3u; }  // the columns the lane has, a bit each
+  // the inverse: column j of lane `src` of this wavefront
+  static __device__ __forceinline__ int sample_of(int chunk0, int wave, int src, int j) {
+    return first(chunk0, wave, src, 0) + offset(j);
+  }
+};
+
 template <typename T>
 struct LaneMap;
 template <>
@@ -165,7 +186,7 @@ template <>
 struct LaneMap<double> {
   static constexpr int NSEG = 2, LEN = 2;
   static __device__ __forceinline__ int first(int chunk0, int seg) {
-    return chunk0 + ((int)threadIdx.x >> 6) * 256 + seg * 128 + 2 * ((int)threadIdx.x & 63);
+    return PairLanes::first(chunk0, (int)threadIdx.x >> 6, (int)threadIdx.x & 63, seg);
   }
 };
 

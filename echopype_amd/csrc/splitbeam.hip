@@ -666,9 +666,7 @@ int launch_direct(SbaArgs& a, int max_taps, hipStream_t st) {
   a.tiles = (a.S + kTile - 1) / kTile;
   const dim3 grid((unsigned)((long long)a.P * a.tiles), (unsigned)a.C);
   auto kern = sba_pc_direct_kernel<InT, T>;
-  if (lds > 64 * 1024)
-    EPA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
+  if (int rc = epa::allow_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, grid, dim3(epa::kBlock), lds, st, a);
   return epa::check_launch("sba_pc_direct_kernel");
 }
