@@ -74,33 +74,6 @@ struct ReduceArgs {
   unsigned tab_off;  // byte offset of the exp/log tables (fast_math.h) in dynamic LDS
 };
 
-// NaN-skipping min over the workgroup; returns NaN when no lane contributed.
-template <typename T>
-__device__ T block_nanmin(T v, bool valid, T* scratch /* >= 8 elements of LDS */) {
-  const T inf = (T)__builtin_inf();
-  T m = valid ? v : inf;
-  int any = valid ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    m = fmin(m, __shfl_down(m, o, 64));
-    any |= __shfl_down(any, o, 64);
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) {
-    scratch[wave] = m;
-    scratch[4 + wave] = (T)any;
-  }
-  __syncthreads();
-  T r = inf;
-  int a = 0;
-  for (int w = 0; w < epa::kBlock / 64; ++w) {
-    r = fmin(r, scratch[w]);
-    a |= (scratch[4 + w] != (T)0);
-  }
-  return a ? r : epa::M<T>::nan();
-}
-
 template <typename T, int SRC, int OP, int VEC>
 __global__ __launch_bounds__(epa::kBlock, 3) void block_reduce_kernel(ReduceArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -336,8 +309,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void block_reduce_kernel(ReduceArgs
   }
   }
   if (a.range_max_out) {  // nanmax(echo_range) by-product: order-preserving u64 key, decoded by the launcher
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) xmax = fmax(xmax, __shfl_down(xmax, o, 64));
+    xmax = epa::wave_max(xmax);
     if ((threadIdx.x & 63) == 0 && xmax > -__builtin_inf()) {
       const unsigned long long key = epa::ordered_key(xmax);
       atomicMax(reinterpret_cast<unsigned long long*>(a.range_max_out), key);
@@ -388,7 +360,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void block_reduce_kernel(ReduceArgs
       }
     }
     __syncthreads();  // all reads of lsum done before it is reused as scratch
-    T m = block_nanmin<T>(best, any, lsum);
+    T m = epa::block_nanmin<T>(best, any, lsum);
     if (threadIdx.x == 0) {
       double r = (double)m;
       if (a.noise_max == a.noise_max) r = (r < a.noise_max) ? r : a.noise_max;  // api.py:418-422
@@ -429,7 +401,7 @@ __global__ __launch_bounds__(epa::kBlock) void noise_rowmin_kernel(const T* __re
       }
     }
   }
-  T m = block_nanmin<T>(best, any, scratch);
+  T m = epa::block_nanmin<T>(best, any, scratch);
   if (threadIdx.x == 0) {
     double r = (double)m;
     if (noise_max == noise_max) r = (r < noise_max) ? r : noise_max;
@@ -465,11 +437,7 @@ __global__ __launch_bounds__(epa::kBlock) void block_nanmin_kernel(const T* __re
         any = 1;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      m = fmin(m, __shfl_down(m, o, 64));
-      any |= __shfl_down(any, o, 64);
-    }
+    epa::wave_nanmin(m, any);
     if (lane == 0) out[cell] = any ? m : epa::M<T>::nan();
   }
 }
@@ -920,7 +888,7 @@ __global__ __launch_bounds__(epa::kBlock) void noise_rows_f64_kernel(const doubl
       }
     }
   }
-  const double m = block_nanmin<double>(best, any, scratch);
+  const double m = epa::block_nanmin<double>(best, any, scratch);
   if (threadIdx.x == 0) {
     double r = m;
     if (noise_max == noise_max) r = (r < noise_max) ? r : noise_max;

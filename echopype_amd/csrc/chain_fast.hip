@@ -412,7 +412,7 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
     }
     if (g < nb) flush(g);  // the last, shorter ping block of the array (nothing left in the columns otherwise)
   }
-  if (RMAX) {  // {max, min, NaN count} of the echo_range: per workgroup, one lane, no return value (see wg_minmax_keys)
+  if (RMAX) {  // {max, min, NaN count} of the echo_range: per workgroup, one lane, no return value
     __shared__ unsigned long long wr[2];
     __shared__ unsigned wn;
     if (threadIdx.x == 0) {
@@ -421,23 +421,7 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
       wn = 0u;
     }
     __syncthreads();
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) xmax = fmax(xmax, __shfl_down(xmax, o, 64));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) xmin = fmin(xmin, __shfl_down(xmin, o, 64));  // (nnan is the wavefront's already)
-    if (lane == 0) {
-      if (xmax > -__builtin_inf()) atomicMax(&wr[0], ordered_key(xmax));
-      if (xmin < __builtin_inf()) atomicMin(&wr[1], ordered_key(xmin));
-      if (nnan > 0u) atomicAdd(&wn, nnan);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      if (wr[0] != kKeyNoMax) atomicMax(a.rmax_key, wr[0]);
-      if (a.rstat) {  // the rest of {nanmin, nanmax, NaN count} of the echo_range
-        if (wr[1] != kKeyNoMin) atomicMin(a.rstat, wr[1]);
-        if (wn > 0u) atomicAdd(a.rstat + 1, (unsigned long long)wn);
-      }
-    }
+    epa::wg_publish_range_keys(xmax, xmin, nnan, wr, &wn, a.rmax_key, a.rstat);
   }
   // min over the range blocks of 10 log10(block mean) (clean/api.py:402-411), optional clamp (:418-422)
   for (int g = 0; g < nb; ++g) {
@@ -461,11 +445,7 @@ __global__ __launch_bounds__(epa::kBlock, sizeof(T) == 8 ? 4 : 1) void sv_noise_
         }
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      best = fmin(best, __shfl_down(best, o, 64));
-      any |= __shfl_down(any, o, 64);
-    }
+    epa::wave_nanmin(best, any);
     if (lane == 0) {
       red[wave] = best;
       red[4 + wave] = (T)any;
@@ -660,13 +640,7 @@ __global__ __launch_bounds__(epa::kBlock, 3) void sv_denoise_mvbs_fast_kernel(
   }
   }
   if (MINMAX) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mm[0] = fmin(mm[0], __shfl_down(mm[0], o, 64));
-      mm[1] = fmax(mm[1], __shfl_down(mm[1], o, 64));
-      mm[2] = fmin(mm[2], __shfl_down(mm[2], o, 64));
-      mm[3] = fmax(mm[3], __shfl_down(mm[3], o, 64));
-    }
+    epa::wave_fold_minmax4(mm);
     wg_minmax_keys(mm, a.mm_keys, lane);
   }
   if (extra) return;
@@ -841,13 +815,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_uniform_kernel
     flush(g);
   }
   if (MINMAX) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mm[0] = fmin(mm[0], __shfl_down(mm[0], o, 64));
-      mm[1] = fmax(mm[1], __shfl_down(mm[1], o, 64));
-      mm[2] = fmin(mm[2], __shfl_down(mm[2], o, 64));
-      mm[3] = fmax(mm[3], __shfl_down(mm[3], o, 64));
-    }
+    epa::wave_fold_minmax4(mm);
     wg_minmax_keys(mm, a.mm_keys, lane);
   }
   __syncthreads();
@@ -1115,13 +1083,7 @@ __global__ __launch_bounds__(epa::kBlock, 4) void sv_denoise_mvbs_drift_kernel(
     double mm[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) mm[k] = (double)mm_slot[k * epa::kBlock + threadIdx.x];  // (the lane's own slots: no barrier)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mm[0] = fmin(mm[0], __shfl_down(mm[0], o, 64));
-      mm[1] = fmax(mm[1], __shfl_down(mm[1], o, 64));
-      mm[2] = fmin(mm[2], __shfl_down(mm[2], o, 64));
-      mm[3] = fmax(mm[3], __shfl_down(mm[3], o, 64));
-    }
+    epa::wave_fold_minmax4(mm);
     wg_minmax_keys(mm, a.mm_keys, lane);
   }
   __syncthreads();

@@ -22,6 +22,7 @@
 // window over the staged tile (LDS rows padded 9/8 -> conflict-free ds_read_b64 / b128).
 // Not a GEMM, no MFMA (BASELINE north_star); vector-FP32/FP64 FMA bound (8*m flops / sample).
 #include "fast_math.h"
+#include "wg_reduce.h"
 
 namespace {
 
@@ -202,8 +203,7 @@ __global__ __launch_bounds__(epa::kBlock, EPA_EK80_MIN_WAVES) void sv_complex_ke
       rep[j] = t;
       part += t.re * t.re + t.im * t.im;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o, 64);
+    part = epa::wave_sum(part);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
     __syncthreads();
     norm2 = red[0] + red[1] + red[2] + red[3];
@@ -404,31 +404,16 @@ __global__ __launch_bounds__(epa::kBlock) void sv_complex_cw_kernel(CxArgs a) {
     }
   }
   if (STATS) {  // one merge per workgroup into one of kCwStatSlots slots (f64 atomics)
-    __shared__ double sred[12];
-    double cnt = (double)rnan;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      rmin = fmin(rmin, __shfl_down(rmin, o, 64));
-      rmax = fmax(rmax, __shfl_down(rmax, o, 64));
-      cnt += __shfl_down(cnt, o, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-      sred[3 * wave] = rmin;
-      sred[3 * wave + 1] = rmax;
-      sred[3 * wave + 2] = cnt;
-    }
-    __syncthreads();
+    __shared__ double sred[3 * epa::kWaves];
+    epa::RangeStats st{rmin, rmax, (double)rnan};
+    st.block_fold(sred);
     if (threadIdx.x == 0) {
       double* dst = a.stats_part + 3 * ((row * a.tiles + piece) & (size_t)(kCwStatSlots - 1));
-      const double mn = fmin(fmin(sred[0], sred[3]), fmin(sred[6], sred[9]));
-      const double mx = fmax(fmax(sred[1], sred[4]), fmax(sred[7], sred[10]));
-      const double nn = (sred[2] + sred[5]) + (sred[8] + sred[11]);
-      if (mn <= mx) {
-        atomicMin(dst, mn);
-        atomicMax(dst + 1, mx);
+      if (st.lo <= st.hi) {
+        atomicMin(dst, st.lo);
+        atomicMax(dst + 1, st.hi);
       }
-      if (nn > 0.0) atomicAdd(dst + 2, nn);
+      if (st.nn > 0.0) atomicAdd(dst + 2, st.nn);
     }
   }
 }

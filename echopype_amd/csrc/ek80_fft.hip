@@ -46,6 +46,7 @@
 #include "fast_math.h"
 #include "lds_fft.h"
 #include "ordered_key.h"
+#include "wg_reduce.h"
 
 namespace {
 
@@ -134,8 +135,7 @@ __global__ __launch_bounds__(epa::kBlock) void replica_prepare_kernel(const floa
       atomicMax(&tap_hi, n + 1);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o, 64);  // ||tx||^2 (ek80_complex.py:372-391)
+  part = epa::wave_sum(part);  // ||tx||^2 (ek80_complex.py:372-391)
   if ((j & 63) == 0) red[j >> 6] = part;
   const LaneMap lm = lane_map();
   fwd_pass0<double>(v, tw[j]);
@@ -636,6 +636,8 @@ __device__ __forceinline__ void process_tile(const FftArgs& a, const TileLds<F, 
   if (clean) epilogue(std::true_type{});
   else epilogue(std::false_type{});
   if (a.stats_part) {  // {nanmin, nanmax, NaN count} of the echo_range written by this workgroup
+    // (written out: through epa::RangeStats two instances of the kernel change their VGPR count, and through its
+    // wave_fold alone one changes its SGPR spills -- profiles/wg_reduce_device_code.txt)
     double cnt = (double)rnan;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {

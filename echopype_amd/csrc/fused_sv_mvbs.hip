@@ -461,32 +461,7 @@ __global__ __launch_bounds__(epa::kBlock, EPA_FUSED_MIN_WAVES > 4 ? EPA_FUSED_MI
     for (int j = 0; j < VEC; ++j) col[j].flush(acc, n_clean);
   }
   }
-  if (RMAX) {
-    // {max, min, NaN count} of the binned coordinate seen by this workgroup: wavefront reduction, then the workgroup's
-    // four wavefronts meet in LDS, then ONE lane sends at most three atomics WITHOUT a return value -- nobody waits for
-    // them.  Measured round 6 (4 x 100 000 x 2000 fp64, ms per launch): one atomic per wavefront and key 1.96-2.12
-    // (2.5 with the three words in one 128-byte line: the L2 serialises a line's atomics); per workgroup, filtered by a
-    // read of the current keys 2.05 (the read is what a workgroup then waits for); per workgroup, unconditional 1.82 =
-    // the kernel without the statistics.  The words live in different 128-byte lines where the caller's layout allows.
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) xmax = fmax(xmax, __shfl_down(xmax, o, 64));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) xmin = fmin(xmin, __shfl_down(xmin, o, 64));  // (nnan is the wavefront's already)
-    if (lane == 0) {
-      if (xmax > -__builtin_inf()) atomicMax(&wg_keys[0], ordered_key(xmax));
-      if (xmin < __builtin_inf()) atomicMin(&wg_keys[1], ordered_key(xmin));
-      if (nnan > 0u) atomicAdd(&wg_nnan, nnan);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned long long kmax = wg_keys[0], kmin = wg_keys[1];
-      if (kmax != kKeyNoMax) atomicMax(a.rmax_key, kmax);
-      if (a.rstat) {  // the rest of {nanmin, nanmax, NaN count}: what compute_MVBS asks of its range variable
-        if (kmin != kKeyNoMin) atomicMin(a.rstat, kmin);
-        if (wg_nnan > 0u) atomicAdd(a.rstat + 1, (unsigned long long)wg_nnan);
-      }
-    }
-  }
+  if (RMAX) epa::wg_publish_range_keys(xmax, xmin, nnan, wg_keys, &wg_nnan, a.rmax_key, a.rstat);
   if (extra) return;
   __syncthreads();
   const size_t cell0 = ((size_t)c * a.n_tbins + tb) * n_rbins;

@@ -8,13 +8,14 @@
 // cm = B / A and then takes I about THAT cm from the registers -- never the expanded form sum r^2 w - 2 cm sum r w +
 // cm^2 sum w, which for a thin layer far away cancels most digits (0.1 m at 10 km: eleven).  Rows too long for
 // registers are read twice, the second time from L2.  No atomics: the result does not depend on scheduling.
-#include "epa_internal.h"
+#include "wg_reduce.h"
 
 namespace {
 
 using epa::kBlock;
 
-constexpr int kWave = 64;
+using epa::kWave;
+using epa::kWaves;
 constexpr int kGroups = 8;  // groups of 4 samples of each array a lane keeps in registers
 constexpr long long kWaveRow = (long long)kWave * 4 * kGroups;    // 2048: longest row one wave holds
 constexpr long long kBlockRow = (long long)kBlock * 4 * kGroups;  // 8192: longest row one workgroup holds
@@ -122,23 +123,17 @@ __device__ __forceinline__ double mt_group_centred(const T (&lin)[4], const T (&
   return I;
 }
 
-__device__ __forceinline__ double mt_wave_sum(double x) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, kWave);
-  return x;  // the same bits in every lane: each step adds the same two numbers on both sides
-}
-
 // the sum over the owners of a row, known to all of them.  LANES = kBlock: through slot (a row of red, one per
 // quantity, so that consecutive sums need no barrier between them beyond their own)
 template <int LANES>
-__device__ __forceinline__ double mt_owner_sum(double x, double (*red)[kBlock / kWave], int slot) {
-  x = mt_wave_sum(x);
+__device__ __forceinline__ double mt_owner_sum(double x, double (*red)[kWaves], int slot) {
+  x = epa::wave_sum_all(x);
   if (LANES == kWave) return x;
   if ((threadIdx.x & (kWave - 1)) == 0) red[slot][threadIdx.x / kWave] = x;
   __syncthreads();
   double t = 0.0;
 #pragma unroll
-  for (int w = 0; w < kBlock / kWave; ++w) t += red[slot][w];
+  for (int w = 0; w < kWaves; ++w) t += red[slot][w];
   return t;
 }
 
@@ -156,12 +151,12 @@ __device__ __forceinline__ void mt_store(const MetricsArgs& a, long long row, co
 // the workgroup.  Owners beyond the grid's take further rows.
 template <typename T, bool AL, int LANES>
 __global__ __launch_bounds__(kBlock) void metrics_rows_kernel(MetricsArgs a) {
-  __shared__ double red[8][kBlock / kWave];
+  __shared__ double red[8][kWaves];
   const long long S = a.S;
   const int t = LANES == kWave ? (int)(threadIdx.x & (kWave - 1)) : (int)threadIdx.x;  // the lane among the owners
   const int wave0 = t & ~(kWave - 1);                                                    // first lane of this wave
-  const long long owners = LANES == kWave ? (long long)gridDim.x * (kBlock / kWave) : (long long)gridDim.x;
-  long long row = LANES == kWave ? (long long)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave : (long long)blockIdx.x;
+  const long long owners = LANES == kWave ? (long long)gridDim.x * kWaves : (long long)gridDim.x;
+  long long row = LANES == kWave ? (long long)blockIdx.x * kWaves + threadIdx.x / kWave : (long long)blockIdx.x;
   int parity = 0;  // the rows of red alternate from row to row: a fast wave may not overwrite what a slow one still reads
   for (; row < a.R; row += owners, parity ^= 4) {
     const T* sv = static_cast<const T*>(a.sv) + row * S;
@@ -204,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void metrics_rows_kernel(MetricsArgs a) {
 // takes the linear values anew.
 template <typename T, bool AL>
 __global__ __launch_bounds__(kBlock) void metrics_loop_kernel(MetricsArgs a) {
-  __shared__ double red[8][kBlock / kWave];
+  __shared__ double red[8][kWaves];
   const long long S = a.S;
   int parity = 0;
   for (long long row = blockIdx.x; row < a.R; row += gridDim.x, parity ^= 4) {
@@ -248,7 +243,7 @@ int launch_metrics(const MetricsArgs& a, hipStream_t st) {
   const bool rows_al = a.R == 1 || (a.S * sizeof(T)) % 16 == 0;
   const bool al = reinterpret_cast<uintptr_t>(a.sv) % 16 == 0 && reinterpret_cast<uintptr_t>(a.range) % 16 == 0 && rows_al;
   if (a.S <= kWaveRow) {
-    const long long need = (a.R + kBlock / kWave - 1) / (kBlock / kWave);
+    const long long need = (a.R + kWaves - 1) / kWaves;
     const int grid = (int)(need < a.max_grid ? need : a.max_grid);
     if (al) {
       hipLaunchKernelGGL((metrics_rows_kernel<T, true, kWave>), dim3(grid), dim3(kBlock), 0, st, a);

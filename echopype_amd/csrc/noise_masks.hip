@@ -1370,15 +1370,13 @@ __global__ __launch_bounds__(kBlock, 3) void pool_value_mean_staged_kernel(PoolV
         }
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      vmin = fmin(vmin, __shfl_down(vmin, o, 64));
-      vmax = fmax(vmax, __shfl_down(vmax, o, 64));
-    }
+    // (the slots stay written out: through MinMax::store / combine the kernel's scratch and VGPR counts change)
+    epa::MinMax span{vmin, vmax};
+    span.wave_fold();
     __syncthreads();  // (the previous group is done with red / kspan / the staged span)
     if (lane == 0) {
-      red_lo[wave] = vmin;
-      red_hi[wave] = vmax;
+      red_lo[wave] = span.lo;
+      red_hi[wave] = span.hi;
     }
     __syncthreads();
     const T gmin = (T)fmin(fmin(red_lo[0], red_lo[1]), fmin(red_lo[2], red_lo[3]));
@@ -1652,15 +1650,13 @@ __global__ __launch_bounds__(kBlock, EPA_LEAN_WGS) void pool_value_mean_lean_ker
         }
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      vmin = fmin(vmin, __shfl_down(vmin, o, 64));
-      vmax = fmax(vmax, __shfl_down(vmax, o, 64));
-    }
+    // (the slots stay written out, as in the staged kernel: through MinMax::store / combine the VGPR spills change)
+    epa::MinMax span{vmin, vmax};
+    span.wave_fold();
     __syncthreads();  // (the previous group is done with red / kspan / the staged span)
     if (lane == 0) {
-      red_lo[wave] = vmin;
-      red_hi[wave] = vmax;
+      red_lo[wave] = span.lo;
+      red_hi[wave] = span.hi;
     }
     __syncthreads();
     const T gmin = (T)fmin(fmin(red_lo[0], red_lo[1]), fmin(red_lo[2], red_lo[3]));
@@ -3126,7 +3122,7 @@ template <typename T>
 __global__ __launch_bounds__(kBlock) void apply_masks_kernel(const T* __restrict__ src, MaskSet ms, size_t n, T fill,
                                                              const T* __restrict__ fill_arr, size_t fill_period,
                                                              T* __restrict__ out, double* __restrict__ part) {
-  double lo = __builtin_inf(), hi = -__builtin_inf();
+  epa::MinMax mm;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     bool keep = true;
 #pragma unroll
@@ -3134,26 +3130,14 @@ __global__ __launch_bounds__(kBlock) void apply_masks_kernel(const T* __restrict
       if (k < ms.n) keep = keep & (ms.m[k][ms.period[k] == n ? i : i % ms.period[k]] != 0);
     const T v = keep ? src[i] : (fill_arr ? fill_arr[fill_period == n ? i : i % fill_period] : fill);
     out[i] = v;
-    if (part) {  // fmin / fmax ignore a NaN operand
-      lo = fmin(lo, (double)v);
-      hi = fmax(hi, (double)v);
-    }
+    if (part) mm.take((double)v);
   }
   if (part) {
-    __shared__ double slo[kBlock / 64], shi[kBlock / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo = fmin(lo, __shfl_down(lo, o, 64));
-      hi = fmax(hi, __shfl_down(hi, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-      slo[threadIdx.x >> 6] = lo;
-      shi[threadIdx.x >> 6] = hi;
-    }
-    __syncthreads();
+    __shared__ double red[2 * epa::kWaves];
+    mm.block_fold(red);
     if (threadIdx.x == 0) {
-      part[2 * (size_t)blockIdx.x] = fmin(fmin(slo[0], slo[1]), fmin(slo[2], slo[3]));
-      part[2 * (size_t)blockIdx.x + 1] = fmax(fmax(shi[0], shi[1]), fmax(shi[2], shi[3]));
+      part[2 * (size_t)blockIdx.x] = mm.lo;
+      part[2 * (size_t)blockIdx.x + 1] = mm.hi;
     }
   }
 }
@@ -3161,27 +3145,16 @@ __global__ __launch_bounds__(kBlock) void apply_masks_kernel(const T* __restrict
 // {min, max} pairs of the workgroups -> out[0], out[1] (NaN when nothing was a number)
 __global__ __launch_bounds__(kBlock) void minmax_pairs_kernel(const double* __restrict__ part, int npairs,
                                                               double* __restrict__ out) {
-  __shared__ double slo[kBlock / 64], shi[kBlock / 64];
-  double lo = __builtin_inf(), hi = -__builtin_inf();
+  __shared__ double red[2 * epa::kWaves];
+  epa::MinMax mm;
   for (int i = threadIdx.x; i < npairs; i += kBlock) {
-    lo = fmin(lo, part[2 * i]);
-    hi = fmax(hi, part[2 * i + 1]);
+    mm.lo = fmin(mm.lo, part[2 * i]);
+    mm.hi = fmax(mm.hi, part[2 * i + 1]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fmin(lo, __shfl_down(lo, o, 64));
-    hi = fmax(hi, __shfl_down(hi, o, 64));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    slo[threadIdx.x >> 6] = lo;
-    shi[threadIdx.x >> 6] = hi;
-  }
-  __syncthreads();
+  mm.block_fold(red);
   if (threadIdx.x == 0) {
-    lo = fmin(fmin(slo[0], slo[1]), fmin(slo[2], slo[3]));
-    hi = fmax(fmax(shi[0], shi[1]), fmax(shi[2], shi[3]));
-    out[0] = lo <= hi ? lo : __builtin_nan("");
-    out[1] = lo <= hi ? hi : __builtin_nan("");
+    out[0] = mm.lo <= mm.hi ? mm.lo : __builtin_nan("");
+    out[1] = mm.lo <= mm.hi ? mm.hi : __builtin_nan("");
   }
 }
 

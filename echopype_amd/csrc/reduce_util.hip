@@ -5,28 +5,15 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "sample_math.h"
+#include "wg_reduce.h"
 
 namespace {
 
 template <typename T>
-__device__ __forceinline__ void wave_minmax(double& lo, double& hi) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fmin(lo, __shfl_down(lo, o, 64));
-    hi = fmax(hi, __shfl_down(hi, o, 64));
-  }
-}
-
-template <typename T>
 __global__ __launch_bounds__(epa::kBlock) void minmax_partial_kernel(const T* __restrict__ x, size_t n,
                                                                      double* __restrict__ part) {
-  __shared__ double slo[4], shi[4], snan[4];
-  double lo = __builtin_inf(), hi = -__builtin_inf(), nn = 0.0;
-  auto take = [&](double v) {
-    lo = fmin(lo, v);  // fmin / fmax ignore a NaN operand
-    hi = fmax(hi, v);
-    nn += v == v ? 0.0 : 1.0;
-  };
+  __shared__ double red[3 * epa::kWaves];
+  epa::RangeStats st;
   // four elements per lane and trip in 16-byte loads (an aligned base: torch allocations are), then the tail
   constexpr int kPer = 16 / sizeof(T);
   typedef T vec_t __attribute__((ext_vector_type(kPer)));
@@ -37,56 +24,38 @@ __global__ __launch_bounds__(epa::kBlock) void minmax_partial_kernel(const T* __
     const vec_t a = xv[2 * i], b = xv[2 * i + 1];
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
-      take((double)a[j]);
-      take((double)b[j]);
+      st.take((double)a[j]);
+      st.take((double)b[j]);
     }
   }
   for (size_t i = nvec * 2 * kPer + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (size_t)gridDim.x * blockDim.x)
-    take((double)x[i]);
-  wave_minmax<T>(lo, hi);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) nn += __shfl_down(nn, o, 64);
-  if ((threadIdx.x & 63) == 0) {
-    slo[threadIdx.x >> 6] = lo;
-    shi[threadIdx.x >> 6] = hi;
-    snan[threadIdx.x >> 6] = nn;
-  }
-  __syncthreads();
+    st.take((double)x[i]);
+  st.block_fold(red);
   if (threadIdx.x == 0) {
-    part[3 * blockIdx.x] = fmin(fmin(slo[0], slo[1]), fmin(slo[2], slo[3]));
-    part[3 * blockIdx.x + 1] = fmax(fmax(shi[0], shi[1]), fmax(shi[2], shi[3]));
-    part[3 * blockIdx.x + 2] = (snan[0] + snan[1]) + (snan[2] + snan[3]);
+    part[3 * blockIdx.x] = st.lo;
+    part[3 * blockIdx.x + 1] = st.hi;
+    part[3 * blockIdx.x + 2] = st.nn;
   }
 }
 
 __global__ __launch_bounds__(epa::kBlock) void minmax_final_kernel(const double* __restrict__ part,
                                                                    int nparts,
                                                                    double* __restrict__ out, int stride = 3) {
-  __shared__ double slo[4], shi[4], snan[4];
-  double lo = __builtin_inf(), hi = -__builtin_inf(), nn = 0.0;
+  __shared__ double red[3 * epa::kWaves];
+  epa::RangeStats st;
   for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-    lo = fmin(lo, part[(size_t)stride * i]);
-    hi = fmax(hi, part[(size_t)stride * i + 1]);
-    nn += part[(size_t)stride * i + 2];
+    st.lo = fmin(st.lo, part[(size_t)stride * i]);
+    st.hi = fmax(st.hi, part[(size_t)stride * i + 1]);
+    st.nn += part[(size_t)stride * i + 2];
   }
-  wave_minmax<double>(lo, hi);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) nn += __shfl_down(nn, o, 64);
-  if ((threadIdx.x & 63) == 0) {
-    slo[threadIdx.x >> 6] = lo;
-    shi[threadIdx.x >> 6] = hi;
-    snan[threadIdx.x >> 6] = nn;
-  }
-  __syncthreads();
+  st.block_fold(red);
   if (threadIdx.x == 0) {
-    lo = fmin(fmin(slo[0], slo[1]), fmin(slo[2], slo[3]));
-    hi = fmax(fmax(shi[0], shi[1]), fmax(shi[2], shi[3]));
     // no finite-or-inf value seen at all -> NaN (numpy nanmin/nanmax of an all-NaN array)
-    const bool none = lo > hi;
-    out[0] = none ? __builtin_nan("") : lo;
-    out[1] = none ? __builtin_nan("") : hi;
-    out[2] = (snan[0] + snan[1]) + (snan[2] + snan[3]);  // number of NaN elements
+    const bool none = st.lo > st.hi;
+    out[0] = none ? __builtin_nan("") : st.lo;
+    out[1] = none ? __builtin_nan("") : st.hi;
+    out[2] = st.nn;  // number of NaN elements
   }
 }
 
@@ -111,31 +80,22 @@ __global__ __launch_bounds__(epa::kBlock) void affine_rows_kernel(const T* __res
 template <typename T>
 __global__ __launch_bounds__(epa::kBlock) void step_rows_kernel(const T* __restrict__ x, long long rows,
                                                                 int S, double* __restrict__ part) {
-  __shared__ double ssum[4], scnt[4];
+  __shared__ double red[2 * epa::kWaves];
   for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
     const T* xr = x + (size_t)row * S;
-    double sum = 0.0, cnt = 0.0;
+    epa::SumCount sc;
     for (int s = threadIdx.x; s + 1 < S; s += blockDim.x) {
       const T d = xr[s + 1] - xr[s];  // in the storage type, as np.diff
       if (d == d) {
-        sum += (double)d;
-        cnt += 1.0;
+        sc.sum += (double)d;
+        sc.cnt += 1.0;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      sum += __shfl_down(sum, o, 64);
-      cnt += __shfl_down(cnt, o, 64);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-      ssum[threadIdx.x >> 6] = sum;
-      scnt[threadIdx.x >> 6] = cnt;
-    }
-    __syncthreads();
+    __syncthreads();  // (the previous row is done with red)
+    sc.block_fold(red);
     if (threadIdx.x == 0) {
-      part[2 * row] = (ssum[0] + ssum[1]) + (ssum[2] + ssum[3]);
-      part[2 * row + 1] = (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
+      part[2 * row] = sc.sum;
+      part[2 * row + 1] = sc.cnt;
     }
   }
 }
@@ -144,19 +104,16 @@ __global__ __launch_bounds__(epa::kBlock) void step_final_kernel(const double* _
                                                                  double* __restrict__ out) {
   __shared__ double ssum[4], scnt[4];
   const double* pc = part + (size_t)blockIdx.x * P * 2;
-  double sum = 0.0, cnt = 0.0;
+  epa::SumCount sc;
   for (int p = threadIdx.x; p < P; p += blockDim.x) {
-    sum += pc[2 * p];
-    cnt += pc[2 * p + 1];
+    sc.sum += pc[2 * p];
+    sc.cnt += pc[2 * p + 1];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_down(sum, o, 64);
-    cnt += __shfl_down(cnt, o, 64);
-  }
+  // (the slots stay written out: through SumCount::block_fold the kernel takes 17 VGPRs where it took 14)
+  sc.wave_fold();
   if ((threadIdx.x & 63) == 0) {
-    ssum[threadIdx.x >> 6] = sum;
-    scnt[threadIdx.x >> 6] = cnt;
+    ssum[threadIdx.x >> 6] = sc.sum;
+    scnt[threadIdx.x >> 6] = sc.cnt;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -196,8 +153,8 @@ __global__ __launch_bounds__(epa::kBlock) void depth_rows_kernel(const T* __rest
                                                                  const double* __restrict__ offset, long long rows,
                                                                  int S, T* __restrict__ out,
                                                                  double* __restrict__ part) {
-  __shared__ double slo[4], shi[4], snan[4];
-  double lo = __builtin_inf(), hi = -__builtin_inf(), nn = 0.0;
+  __shared__ double red[3 * epa::kWaves];
+  epa::RangeStats st;
   for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
     const T a = (T)scale[row], b = (T)offset[row];
     const size_t base = (size_t)row * S;
@@ -214,29 +171,16 @@ __global__ __launch_bounds__(epa::kBlock) void depth_rows_kernel(const T* __rest
       }
       const T d = epa::depth_of(a, b, r);
       orow[s] = d;
-      if (part) {
-        const double dd = (double)d;
-        lo = fmin(lo, dd);  // fmin / fmax ignore a NaN operand
-        hi = fmax(hi, dd);
-        nn += dd == dd ? 0.0 : 1.0;
-      }
+      if (part) st.take((double)d);
     }
   }
   if (part) {
-    wave_minmax<double>(lo, hi);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nn += __shfl_down(nn, o, 64);
-    if ((threadIdx.x & 63) == 0) {
-      slo[threadIdx.x >> 6] = lo;
-      shi[threadIdx.x >> 6] = hi;
-      snan[threadIdx.x >> 6] = nn;
-    }
-    __syncthreads();
+    st.block_fold(red);
     if (threadIdx.x == 0) {
       double* pp = part + 3 * (size_t)blockIdx.x;
-      pp[0] = fmin(fmin(slo[0], slo[1]), fmin(slo[2], slo[3]));
-      pp[1] = fmax(fmax(shi[0], shi[1]), fmax(shi[2], shi[3]));
-      pp[2] = (snan[0] + snan[1]) + (snan[2] + snan[3]);
+      pp[0] = st.lo;
+      pp[1] = st.hi;
+      pp[2] = st.nn;
     }
   }
 }
@@ -318,13 +262,13 @@ __global__ __launch_bounds__(epa::kBlock) void rows_piece_kernel(const float* __
     if ((threadIdx.x & 63) == 0 && nn > 0u) atomicAdd(&wnn, nn);
     __syncthreads();
     if (threadIdx.x < 64) {
-      double l2 = (double)wlo[threadIdx.x & 31], h2 = (double)whi[threadIdx.x & 31];
-      wave_minmax<double>(l2, h2);
+      epa::MinMax mm{(double)wlo[threadIdx.x & 31], (double)whi[threadIdx.x & 31]};
+      mm.wave_fold();
       if (threadIdx.x == 0) {
         double* sl = slots + (size_t)(blockIdx.x & (kPieceSlots - 1)) * kPieceSlotStride;
-        if (l2 <= h2) {
-          unsafeAtomicMin(sl + 0, l2);
-          unsafeAtomicMax(sl + 1, h2);
+        if (mm.lo <= mm.hi) {
+          unsafeAtomicMin(sl + 0, mm.lo);
+          unsafeAtomicMax(sl + 1, mm.hi);
         }
         if (wnn > 0u) unsafeAtomicAdd(sl + 2, (double)wnn);
       }

@@ -26,7 +26,7 @@ namespace {
 
 using epa::uf::ld;
 
-constexpr int kWaves = epa::kBlock / 64;
+using epa::kWaves;
 constexpr int kPings = 32;       // pings walked by one wave
 constexpr int kMaxBlocks = 4096;  // workgroups of the sweep (each builds the 10^x table once, then strides over the tiles)
 

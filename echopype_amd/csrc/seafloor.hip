@@ -39,7 +39,7 @@ using epa::uf::st;
 using epa::uf::uf_root;
 using epa::uf::uf_union;
 
-constexpr int kWaves = epa::kBlock / 64;
+using epa::kWaves;
 constexpr int kMaxBlocks = 16384;
 
 // state words (EPA_SEAFLOOR_STATE_WORDS u64, zeroed by the caller)
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(epa::kBlock) void sf_box_cols_kernel(const double* 
     cnt += m ? 1 : 0;
   }
   // one atomic per wave
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  cnt = epa::wave_sum(cnt);
   if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&state[kMasked], cnt);
 }
 

@@ -28,8 +28,7 @@ __device__ __forceinline__ int reflect_index(int i, int n) {
 // workgroup reductions (256 threads = 4 wavefronts); every thread gets the result
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned block_sum(unsigned v, unsigned* sh4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  v = epa::wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
   __syncthreads();

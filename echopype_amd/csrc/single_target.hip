@@ -24,14 +24,14 @@
 // six counters per wave, then per workgroup; n_targets is a plain store per row, and the per-channel counters take
 // one atomic per counter when a workgroup leaves a channel.
 // Both passes judge a candidate with the same function: what the count pass counted is what the emit pass writes.
-#include "epa_internal.h"
+#include "wg_reduce.h"
 
 namespace {
 
 using epa::kBlock;
 
-constexpr int kWave = 64;
-constexpr int kWaves = kBlock / kWave;
+using epa::kWave;
+using epa::kWaves;
 constexpr int kTile = EPA_SINGLE_TARGET_TILE;
 constexpr int kSteps = kTile / kBlock;  // samples of a tile a lane judges
 constexpr int kHalo = 64;
@@ -200,12 +200,6 @@ __device__ __forceinline__ void load_tile(T* win, const T* ts, int S, int t0, in
   }
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned x) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, kWave);
-  return x;
-}
-
 template <typename T, bool EMIT>
 __global__ __launch_bounds__(kBlock) void sweep(Args a) {
   __shared__ T win[kTile + 2 * kHalo];
@@ -323,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void sweep(Args a) {
       __syncthreads();  // thread 0 has read the counters of the row before
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
-        const unsigned s = wave_sum(mine[k]);
+        const unsigned s = epa::wave_sum_all(mine[k]);
         if (lane == 0) red[k][wave] = s;
       }
       __syncthreads();

@@ -13,6 +13,7 @@
 #include "log_tab_data.h"
 #include "ordered_key.h"
 #include "sample_math.h"
+#include "wg_reduce.h"
 
 namespace {
 
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(epa::kBlock) void sv_power_kernel(const float* __re
   if (!STATS && !act[0]) return;
   // STATS: {min, max, NaN count} of the echo_range (written when RANGE, else left to epa_range_power for whoever asks
   // for the array), one partial per workgroup (no lane leaves early: the wavefront reduction at the end needs them all)
-  double lo = __builtin_inf(), hi = -__builtin_inf(), nn = 0.0;
+  epa::RangeStats st;
   epa::ColumnLog<T, LEN> col[NSEG];
   for (long long row = blockIdx.x; row < rows && act[0]; row += gridDim.x) {
     const epa::RowK<T> rk(coef[row]);
@@ -57,34 +58,20 @@ __global__ __launch_bounds__(epa::kBlock) void sv_power_kernel(const float* __re
         const double r = rk.range(s0[g] + j);
         o[j] = epa::cal_power_sample<T>(in.v[j], s0[g] + j, rk, nspread, col[g].nL[j], guard, r);
         if (RANGE || STATS) rg[j] = (mask_range && !(in.v[j] == in.v[j])) ? epa::M<T>::nan() : (T)r;
-        if (STATS) {
-          const double x = (double)rg[j];
-          lo = fmin(lo, x);  // fmin / fmax ignore a NaN operand
-          hi = fmax(hi, x);
-          nn += x == x ? 0.0 : 1.0;
-        }
+        if (STATS) st.take((double)rg[j]);
       }
       epa::store_vec<T, LEN>(out + off, o);
       if (RANGE) epa::store_vec<T, LEN>(range_out + off, rg);
     }
   }
   if (STATS) {
-    __shared__ double slo[4], shi[4], snn[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo = fmin(lo, __shfl_down(lo, o, 64));
-      hi = fmax(hi, __shfl_down(hi, o, 64));
-      nn += __shfl_down(nn, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; snn[threadIdx.x >> 6] = nn;
-    }
-    __syncthreads();
+    __shared__ double red[3 * epa::kWaves];
+    st.block_fold(red);
     if (threadIdx.x == 0) {
       double* pp = part + 3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
-      pp[0] = fmin(fmin(slo[0], slo[1]), fmin(slo[2], slo[3]));
-      pp[1] = fmax(fmax(shi[0], shi[1]), fmax(shi[2], shi[3]));
-      pp[2] = (snn[0] + snn[1]) + (snn[2] + snn[3]);
+      pp[0] = st.lo;
+      pp[1] = st.hi;
+      pp[2] = st.nn;
     }
   }
 }
@@ -122,27 +109,22 @@ __device__ __forceinline__ T piece_nlog(double sd, T nspread) {
 __global__ __launch_bounds__(epa::kBlock) void d_span_kernel(const epa::CoefRow* __restrict__ coef, int P,
                                                              unsigned long long* __restrict__ dkeys) {
   const int c = blockIdx.y;
-  double lo = __builtin_inf(), hi = -__builtin_inf();
+  epa::MinMax mm;
   bool bad = false;
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
     const double d = coef[(size_t)c * P + p].d;
     bad |= !(d == d);
-    lo = fmin(lo, d);
-    hi = fmax(hi, d);
+    mm.take(d);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fmin(lo, __shfl_down(lo, o, 64));
-    hi = fmax(hi, __shfl_down(hi, o, 64));
-  }
+  mm.wave_fold();
   const bool any_bad = __ballot(bad) != 0ull;
   if ((threadIdx.x & 63) == 0) {
     if (any_bad) {
       atomicMin(dkeys + 2 * c, kKeyNoMax);
       atomicMax(dkeys + 2 * c + 1, kKeyNoMin);
-    } else if (lo <= hi) {
-      atomicMin(dkeys + 2 * c, ordered_key(lo));
-      atomicMax(dkeys + 2 * c + 1, ordered_key(hi));
+    } else if (mm.lo <= mm.hi) {
+      atomicMin(dkeys + 2 * c, ordered_key(mm.lo));
+      atomicMax(dkeys + 2 * c + 1, ordered_key(mm.hi));
     }
   }
 }
@@ -264,11 +246,8 @@ __global__ __launch_bounds__(epa::kBlock) void sv_power_piece_kernel(const float
         const int s_i = LM::first(chunk * 1024, i / LEN) + i % LEN;  // (an idle lane's placeholder is not a value)
         nn += (unsigned)__builtin_popcountll(__ballot(s_i < S && !(x == x)));
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        lo = fmin(lo, __shfl_down(lo, o, 64));
-        hi = fmax(hi, __shfl_down(hi, o, 64));
-      }
+      lo = epa::wave_min(lo);
+      hi = epa::wave_max(hi);
     }
     if ((threadIdx.x & 63) == 0) {
       if (send_hi && hi > -__builtin_inf()) atomicMax(k + 0, ordered_key(hi));

@@ -21,11 +21,11 @@
 // order.  Every kernel is memory-safe on ANY table content: the segment starts are lower bounds inside [0, n] whatever
 // the order of the rows, a pair is linked only if the two rows' own indices say so (same channel, later ping), so
 // the links cannot form a cycle, and every stored row number is one this library wrote.
-#include "epa_internal.h"
+#include "wg_reduce.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using epa::kWave;
 constexpr int kLinkBlock = kWave;  // propose / accept: one wave per (channel, ping) segment
 constexpr int kTile = EPA_TRACK_TILE;
 constexpr int kMaxGrid = 1 << 20;  // workgroups of a link launch; each takes further segments in a loop
@@ -266,12 +266,9 @@ __global__ __launch_bounds__(epa::kBlock) void order_kernel(TableArgs a) {
   a.track_id[i] = id;
 }
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, kWave);
-  return x;
-}
-__device__ __forceinline__ double wave_max(double x) {
+using epa::wave_sum_all;
+// every lane holds the result: the larger of two by comparison (not fmax)
+__device__ __forceinline__ double wave_max_all(double x) {
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) {
     const double y = __shfl_xor(x, o, kWave);
@@ -281,10 +278,10 @@ __device__ __forceinline__ double wave_max(double x) {
 }
 
 // One wave per track.  Lane l adds the members l, l + 64, ... in chain order, then the 64 partial sums are added in
-// the fixed tree of wave_sum: an order set by the track's length alone.
+// the fixed tree of wave_sum_all: an order set by the track's length alone.
 __global__ __launch_bounds__(epa::kBlock) void table_kernel(TableArgs a) {
   const int lane = threadIdx.x & (kWave - 1);
-  const long long t = (long long)blockIdx.x * (epa::kBlock / kWave) + threadIdx.x / kWave;
+  const long long t = (long long)blockIdx.x * epa::kWaves + threadIdx.x / kWave;
   if (t >= a.T) return;  // (uniform over the wave)
   const long long s0 = a.start[t];
   long long len = a.icols[1 * a.T + t];
@@ -303,7 +300,7 @@ __global__ __launch_bounds__(epa::kBlock) void table_kernel(TableArgs a) {
       path += ::sqrt(dx * dx + dy * dy + dz * dz);
     }
   }
-  lin = wave_sum(lin), rsum = wave_sum(rsum), path = wave_sum(path), top = wave_max(top);
+  lin = wave_sum_all(lin), rsum = wave_sum_all(rsum), path = wave_sum_all(path), top = wave_max_all(top);
   if (lane != 0) return;
   const int f = mem[0], l = mem[len - 1];
   int* ic = a.icols + t;
@@ -424,7 +421,7 @@ extern "C" int epa_track_table(const int* channel_index, const int* ping_index, 
   EPA_CHECK_HIP(hipMemsetAsync(start, 0xff, (size_t)T * sizeof(int), st));  // -1: a track the order pass never met
   order_kernel<<<blocks_for(n), epa::kBlock, 0, st>>>(a);
   if (int rc = epa::check_launch("track_order_kernel")) return rc;
-  const int per = epa::kBlock / kWave;
+  const int per = epa::kWaves;
   table_kernel<<<(int)((T + per - 1) / per), epa::kBlock, 0, st>>>(a);
   return epa::check_launch("track_table_kernel");
 }

@@ -32,12 +32,11 @@ constexpr long long kMaxGrid = 262144;
 inline unsigned grid_for(long long rows) { return (unsigned)(rows < kMaxGrid ? (rows > 0 ? rows : 1) : kMaxGrid); }
 
 __device__ __forceinline__ double block_sum_f64(double v, double* sh4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  v = epa::wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
   __syncthreads();
-  return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
+  return epa::slots_sum(sh4);
 }
 
 // m[from .. n) = v by the workgroup: 4-byte stores over the aligned middle, single bytes at the two ragged ends

@@ -37,7 +37,7 @@ using epa::kBlock;
 constexpr int TP = EPA_WINDOW_FILTER_TP, TS = EPA_WINDOW_FILTER_TS;
 constexpr int kHaloMax = EPA_WINDOW_FILTER_MAX / 2;
 constexpr int kTileElems = (TP + 2 * kHaloMax) * (TS + 2 * kHaloMax);
-constexpr int kWaves = kBlock / 64;
+using epa::kWaves;
 constexpr int kRows = TP / kWaves;        // consecutive rows of one column that a lane computes
 constexpr int kWindowMaxGrid = 1 << 20;  // workgroups of a launch: further tiles are taken in a loop
 static_assert(TS == 64 && kRows * kWaves == TP, "a wave spans a tile row, the waves share its rows evenly");

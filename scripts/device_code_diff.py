@@ -4,10 +4,14 @@
     python scripts/device_code_diff.py OLD_TREE NEW_TREE [file.hip ...]     (default: build.py's SOURCES)
 
 Each file is compiled to device assembly with build.py's FLAGS of its own tree; every function body and every kernel
-descriptor (registers, LDS, scratch) is then compared as text.  Function-local labels carry the function's ordinal in
-the file, which moves when the instantiation order does, so that ordinal is dropped first.  Exit status 1 when a
-symbol is missing, added or different.  Runs on the CPU: nothing is launched.
+descriptor (registers, LDS, scratch, and with it the spill counts of the kernel's metadata and the occupancy the
+compiler notes) is then compared as text.  Function-local labels carry the function's ordinal in
+the file, which moves when the instantiation order does, so that ordinal is dropped first.  A body that differs is
+reported with its instruction count on both sides and the opcodes whose number changed (none: registers renamed or
+instructions reordered).  Exit status 1 when a symbol is missing, added or different.  Runs on the CPU: nothing is
+launched.
 """
+import collections
 import os
 import re
 import runpy
@@ -19,6 +23,16 @@ FUNC = re.compile(r"; -- Begin function (\S+)\n(.*?); -- End function", re.S)
 DESC = re.compile(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", re.S)
 LOCAL = re.compile(r"(\.LBB|\bBB|\.Lfunc_begin|\.Lfunc_end|\.LJTI)\d+")
 BLANKS = re.compile(r"[ \t]+")  # a label's comment is aligned to a column: a longer ordinal moves it
+SPILLS = re.compile(r"^    \.(name|sgpr_spill_count|vgpr_spill_count):\s+(\S+)$", re.M)  # of one amdhsa.kernels entry
+OCCUPANCY = re.compile(r"\.set (\S+)\.has_indirect_call, \d+\n.*?; Occupancy: (\d+)", re.S)
+OPCODE = re.compile(r"^ ([a-z][a-z0-9_]+)\b", re.M)  # (after BLANKS: an instruction line starts with one blank)
+
+
+def opcode_delta(old_body, new_body):
+    """'N -> M instructions' and the opcodes whose count changed, parent against branch."""
+    a, b = (collections.Counter(OPCODE.findall(t)) for t in (old_body, new_body))
+    moved = " ".join(f"{op}{b[op] - a[op]:+d}" for op in sorted(set(a) | set(b)) if a[op] != b[op])
+    return f"{sum(a.values())} -> {sum(b.values())} instructions; {moved or 'same opcodes: registers renamed or reordered'}"
 
 
 def device_symbols(tree, name):
@@ -30,6 +44,13 @@ def device_symbols(tree, name):
     asm = r.stdout
     syms = {"func " + m.group(1): BLANKS.sub(" ", LOCAL.sub(r"\1", m.group(2))) for m in FUNC.finditer(asm)}
     syms.update({"desc " + m.group(1): m.group(2) for m in DESC.finditer(asm)})
+    for entry in asm.split("\n  - ")[1:]:
+        d = dict(SPILLS.findall(entry))
+        if "desc " + d.get("name", "") in syms:
+            syms["desc " + d["name"]] += f".sgpr_spill_count {d['sgpr_spill_count']}\n.vgpr_spill_count {d['vgpr_spill_count']}\n"
+    for name, occ in OCCUPANCY.findall(asm):
+        if "desc " + name in syms:
+            syms["desc " + name] += f".occupancy {occ}\n"
     return syms
 
 
@@ -41,19 +62,21 @@ def main(argv):
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
         olds = list(ex.map(lambda f: device_symbols(old, f), files))
         news = list(ex.map(lambda f: device_symbols(new, f), files))
-    bad = 0
+    bad = bad_desc = 0
     for name, a, b in zip(files, olds, news):
         missing = sorted(set(a) - set(b))
         added = sorted(set(b) - set(a))
         differ = sorted(s for s in set(a) & set(b) if a[s] != b[s])
         for what, syms in (("missing", missing), ("added", added), ("differs", differ)):
             for s in syms:
-                print(f"{name}: {what}: {s}")
+                note = f": {opcode_delta(a[s], b[s])}" if what == "differs" and s.startswith("func ") else ""
+                print(f"{name}: {what}: {s}{note}")
         bad += len(missing) + len(added) + len(differ)
         nfunc = sum(s.startswith("func ") for s in b)
         print(f"{name}: {nfunc} functions, {len(b) - nfunc} kernel descriptors: "
               f"{'identical' if not (missing or added or differ) else 'DIFFERENT'}")
-    print(f"{bad} differences in {len(files)} files")
+        bad_desc += sum(s.startswith("desc ") for s in missing + added + differ)
+    print(f"{bad} differences in {len(files)} files, {bad_desc} of them kernel descriptors")
     return 1 if bad else 0
 
 
