@@ -78,6 +78,11 @@ TRACK_ICOL_NAMES = ("channel_index", "n_targets", "ping_first", "ping_last", "ta
                     "target_last")  # the rows of a track's icols
 TRACK_FCOL_NAMES = ("TS_mean", "TS_max", "range_mean", "x_first", "y_first", "z_first", "x_last", "y_last", "z_last",
                     "path_length", "displacement", "tortuosity", "delta_range")  # the rows of a track's fcols
+TARGET_SPECTRA_MAX_HALF_WINDOW, TARGET_SPECTRA_MAX_FREQ, TARGET_SPECTRA_MAX_TAPS = 127, 1024, 2048  # EPA_TARGET_SPECTRA_MAX_*
+TARGET_SPECTRA_FPARAMS, TARGET_SPECTRA_PPARAMS, TARGET_SPECTRA_TABLE_ROWS = 8, 3, 3  # EPA_TARGET_SPECTRA_FPARAMS, _PPARAMS, _TABLE_ROWS
+TARGET_SPECTRA_FPARAM_NAMES = ("frequency", "sound_absorption", "gain_correction", "impedance_transducer", "beamwidth_alongship",
+                               "beamwidth_athwartship", "angle_offset_alongship", "angle_offset_athwartship")  # the rows of fparams
+TARGET_SPECTRA_PPARAM_NAMES = ("transmit_power", "sound_speed", "impedance_transceiver")  # the rows of pparams
 
 
 class EpaError(RuntimeError):
@@ -223,6 +228,8 @@ SIGNATURES = {
     "epa_track_roots": [_vp, _ll, _i, _vp, _vp, _vp, _vp, _vp],
     "epa_track_chains": [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp],
     "epa_track_table": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
+    "epa_target_spectra": [_vp, _vp, _i, _ll, _ll, _ll, _i, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _i, _i, _vp, _vp, _i,
+                           _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp],
 }
 
 for _name, _args in SIGNATURES.items():

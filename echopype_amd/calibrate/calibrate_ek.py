@@ -456,15 +456,13 @@ class CalibrateEK80(CalibrateEK):
             B = 0.5 * 6.0206 * (fa + ft - 0.18 * fa * ft)
         return np.where(np.isnan(B), 0.0, B)
 
-    def _complex_inputs(self, cal_type):
-        """Everything epa_sv_complex needs, assembled on the host from O(C*P) parameters: the sample planes on the
-        device, the (C, P, 6) coefficient rows, the flattened replicas + offsets (BB), tau_effective."""
-        C, P, S = self._shape()
-        B = self.beam["backscatter_r"].shape[3]
-        bb = self.waveform_mode == "BB"
+    def _transmit_replicas(self):
+        """(tau_effective, replicas): the transmit replica of every channel (a dict by channel) or, with several filter
+        intervals, of every (channel, interval) pair of the plan (a list) -- what the matched filter of compute_Sv /
+        compute_TS and targets.target_spectra correlate with."""
         tau_eff, tx = self._tau_effective(True)
         plan = self._plan
-        if plan is not None and bb and any(t is None for t in tx):
+        if plan is not None and self.waveform_mode == "BB" and any(t is None for t in tx):
             raise ValueError("a filter interval without a usable transmit replica: broadband samples cannot be "
                              "pulse-compressed (assume_single_filter_time=True calibrates with the first filter set)")
         if plan is None and tx is None:
@@ -473,6 +471,25 @@ class CalibrateEK80(CalibrateEK):
                                         self.cal_params["receiver_sampling_frequency"],
                                         self.drop_last_hanning_zero,
                                         whole_file=(self.file_scalars or {}).get("transmit_params"))
+        return tau_eff, tx
+
+    def _replica_arrays(self, tx):
+        """The replicas as the kernels take them: (complex64 taps of all replicas end to end, int32 offsets
+        [n_replicas + 1], the most taps of one)."""
+        chans = list(self.beam["channel"].values)
+        taps = [np.asarray(tx[ch]) for ch in chans] if self._plan is None else [np.asarray(t) for t in tx]
+        off_h = np.concatenate([[0], np.cumsum([t.size for t in taps])]).astype(np.int32)
+        flat = np.concatenate(taps).astype(np.complex64)
+        return flat, off_h, int(max(t.size for t in taps))
+
+    def _complex_inputs(self, cal_type):
+        """Everything epa_sv_complex needs, assembled on the host from O(C*P) parameters: the sample planes on the
+        device, the (C, P, 6) coefficient rows, the flattened replicas + offsets (BB), tau_effective."""
+        C, P, S = self._shape()
+        B = self.beam["backscatter_r"].shape[3]
+        bb = self.waveform_mode == "BB"
+        plan = self._plan
+        tau_eff, tx = self._transmit_replicas()
         # the (C, P, 8) coefficient rows are built on the device (epa_complex_coef_ek80): parameters go up in the shape
         # they have -- scalar, (C,), or (C, P) (straight from HBM when the echodata is resident) -- no (C, P) NumPy math
         def dv(v, name):
@@ -508,15 +525,11 @@ class CalibrateEK80(CalibrateEK):
         rep = off = rid = None
         max_taps = 0
         if bb:
-            chans = list(self.beam["channel"].values)
-            taps = [np.asarray(tx[ch]) for ch in chans] if plan is None else [np.asarray(t) for t in tx]
             if plan is not None:
                 rid = self._dev(np.ascontiguousarray(plan["replica_id"]))
-            off_h = np.concatenate([[0], np.cumsum([t.size for t in taps])]).astype(np.int32)
-            flat = np.concatenate(taps).astype(np.complex64)
+            flat, off_h, max_taps = self._replica_arrays(tx)
             rep = self._dev(np.ascontiguousarray(flat.view(np.float32)))
             off = self._dev(off_h)
-            max_taps = int(max(t.size for t in taps))
         re = self._dev(self.beam["backscatter_r"].data)
         im = self._dev(self.beam["backscatter_i"].data)
         if re.dtype not in (torch.float32, torch.float64):

@@ -151,7 +151,8 @@ def from_ek60_arrays(d, source_file="synthetic_ek60.raw"):
 
 def from_ek80_arrays(d, filters, encode="complex", source_file="synthetic_ek80.raw", filter_time_idx=None):
     """EK80 EchoData (complex samples in Beam_group1; convert/set_groups_ek80.py:796-840,967-1068,
-    1234-1518).  ``filters`` = dict(wbt_fil, wbt_decifac, pc_fil, pc_decifac) applied to every channel."""
+    1234-1518).  ``filters`` = dict(wbt_fil, wbt_decifac, pc_fil, pc_decifac) applied to every channel, or a list of
+    one such dict per channel."""
     ch = list(d["channel"])
     pt = _time1(d["ping_time"])
     C, P, S, B = d["backscatter_r"].shape
@@ -180,24 +181,27 @@ def from_ek80_arrays(d, filters, encode="complex", source_file="synthetic_ek80.r
     beam["angle_sensitivity_alongship"] = (("channel",), np.full(C, 23.0))
     beam["angle_sensitivity_athwartship"] = (("channel",), np.full(C, 23.0))
     _add_split_beam(beam, d, params=False)
-    nw, npc = filters["wbt_fil"].size, filters["pc_fil"].size
+    per_ch = list(filters) if isinstance(filters, (list, tuple)) else [filters] * C  # (a list: one filter set per channel)
+    nw, npc = max(f["wbt_fil"].size for f in per_ch), max(f["pc_fil"].size for f in per_ch)
     vend = Dataset(coords={"channel": ch, "pulse_length_bin": np.arange(5), "WBT_filter_n": np.arange(nw + 3),
                            "PC_filter_n": np.arange(npc + 2)})
 
     vend_dim = {"WBT_coeffs_real": "WBT_filter_n", "WBT_coeffs_imag": "WBT_filter_n",
                 "PC_coeffs_real": "PC_filter_n", "PC_coeffs_imag": "PC_filter_n"}
 
-    def _pad(c, n):  # NaN padded like the converter (set_groups_ek80.py:1411-1518)
+    def _pad(key, part, n):  # NaN padded like the converter (set_groups_ek80.py:1411-1518)
         out = np.full((C, n), np.nan)
-        out[:, : c.size] = c
+        for i, f in enumerate(per_ch):
+            c = getattr(f[key], part)
+            out[i, : c.size] = c
         return out
 
-    vend["WBT_coeffs_real"] = (("channel", "WBT_filter_n"), _pad(filters["wbt_fil"].real, nw + 3))
-    vend["WBT_coeffs_imag"] = (("channel", "WBT_filter_n"), _pad(filters["wbt_fil"].imag, nw + 3))
-    vend["PC_coeffs_real"] = (("channel", "PC_filter_n"), _pad(filters["pc_fil"].real, npc + 2))
-    vend["PC_coeffs_imag"] = (("channel", "PC_filter_n"), _pad(filters["pc_fil"].imag, npc + 2))
-    vend["WBT_deci_fac"] = (("channel",), np.full(C, filters["wbt_decifac"]))
-    vend["PC_deci_fac"] = (("channel",), np.full(C, filters["pc_decifac"]))
+    vend["WBT_coeffs_real"] = (("channel", "WBT_filter_n"), _pad("wbt_fil", "real", nw + 3))
+    vend["WBT_coeffs_imag"] = (("channel", "WBT_filter_n"), _pad("wbt_fil", "imag", nw + 3))
+    vend["PC_coeffs_real"] = (("channel", "PC_filter_n"), _pad("pc_fil", "real", npc + 2))
+    vend["PC_coeffs_imag"] = (("channel", "PC_filter_n"), _pad("pc_fil", "imag", npc + 2))
+    vend["WBT_deci_fac"] = (("channel",), np.asarray([f["wbt_decifac"] for f in per_ch]))
+    vend["PC_deci_fac"] = (("channel",), np.asarray([f["pc_decifac"] for f in per_ch]))
     if filter_time_idx is not None:
         # the same filter set recorded at several filter_time stamps (a file whose filter datagrams
         # were re-sent): (channel, filter_time, n) as in set_groups_ek80.py:1411-1518

@@ -1106,6 +1106,74 @@ def single_target_emit(ts, along, athw, range, prm, limits, n_targets, offsets, 
     return icols, fcols
 
 
+# ---- target strength spectra (targets.target_spectra) -----------------------------------------------------------------
+def target_spectra(re, im, replica, replica_off, max_taps, rep_dt, fparams, pparams, half_window, chan_map, channel_index,
+                   ping_index, range_sample, target_range, angle_alongship, angle_athwartship, *, replica_id=None,
+                   dtype="float64"):
+    """TS(f) of the rows of a single-target table (``epa_target_spectra``; targets/spectra.py states the rules).
+
+    ``re``, ``im``: the sector samples (C, P, S, B), float32 or float64.  ``replica``: float32 (2 * n,) interleaved
+    (re, im) of all replicas end to end; ``replica_off`` int32 (R + 1,); ``max_taps`` the most taps of one (at most
+    ``_lib.TARGET_SPECTRA_MAX_TAPS``); ``replica_id`` int32 (C, P) or None (replica c for channel c).  ``rep_dt``
+    float64 (R,): the sample interval of a replica's pings.  ``fparams`` float64 (R, 8, F) in the order of
+    ``_lib.TARGET_SPECTRA_FPARAM_NAMES``; ``pparams`` float64 (3, C, P) in the order of
+    ``_lib.TARGET_SPECTRA_PPARAM_NAMES``.  ``chan_map`` int32 (n,): the channel of the cubes behind every channel of the
+    table.  The columns: int32 ``channel_index``, ``ping_index``, ``range_sample`` and float64 ``target_range``,
+    ``angle_alongship``, ``angle_athwartship``, (N,) each.
+    -> (``TS_spectrum`` (N, F), ``TS_spectrum_uncomp`` (N, F) of ``dtype``, ``n_window_samples`` int32 (N,)).  No rows:
+    nothing is launched."""
+    who = "target_spectra"
+    td = torch_dtype(dtype)
+    if re.dim() != 4 or re.dtype not in _DT or im.dtype != re.dtype or im.shape != re.shape:
+        raise ValueError(f"{who}: re and im must be float32 / float64 of one shape (C, P, S, B), got {re.dtype} "
+                         f"{tuple(re.shape)} and {im.dtype} {tuple(im.shape)}")
+    C, P, S, B = re.shape
+    max_taps, h = int(max_taps), int(half_window)
+    if not 1 <= max_taps <= _lib.TARGET_SPECTRA_MAX_TAPS:
+        raise ValueError(f"{who}: replicas of up to {_lib.TARGET_SPECTRA_MAX_TAPS} taps are served, got max_taps {max_taps}")
+    if not 0 <= h <= _lib.TARGET_SPECTRA_MAX_HALF_WINDOW:
+        raise ValueError(f"{who}: half_window {h} outside 0 .. {_lib.TARGET_SPECTRA_MAX_HALF_WINDOW}")
+    if replica.dtype != torch.float32 or replica.dim() != 1 or replica.numel() % 2 or replica_off.dtype != torch.int32 \
+            or replica_off.dim() != 1 or replica_off.numel() < 2:
+        raise ValueError(f"{who}: replica float32 (2 n,) and replica_off int32 (R + 1,) expected")
+    R = replica_off.numel() - 1
+    if replica_id is not None and (replica_id.dtype != torch.int32 or tuple(replica_id.shape) != (C, P)):
+        raise ValueError(f"{who}: replica_id must be int32 of shape {(C, P)}")
+    if replica_id is None and R < C:
+        raise ValueError(f"{who}: without replica_id every channel needs its replica ({R} replicas, {C} channels)")
+    if fparams.dtype != torch.float64 or fparams.dim() != 3 or fparams.shape[:2] != (R, _lib.TARGET_SPECTRA_FPARAMS):
+        raise ValueError(f"{who}: fparams must be float64 of shape ({R}, {_lib.TARGET_SPECTRA_FPARAMS}, F), got "
+                         f"{fparams.dtype} {tuple(fparams.shape)}")
+    F = fparams.shape[2]
+    if not 1 <= F <= _lib.TARGET_SPECTRA_MAX_FREQ:
+        raise ValueError(f"{who}: {F} frequencies outside 1 .. {_lib.TARGET_SPECTRA_MAX_FREQ}")
+    if rep_dt.dtype != torch.float64 or tuple(rep_dt.shape) != (R,):
+        raise ValueError(f"{who}: rep_dt must be float64 of shape ({R},)")
+    if pparams.dtype != torch.float64 or tuple(pparams.shape) != (_lib.TARGET_SPECTRA_PPARAMS, C, P):
+        raise ValueError(f"{who}: pparams must be float64 of shape {(_lib.TARGET_SPECTRA_PPARAMS, C, P)}")
+    if chan_map.dtype != torch.int32 or chan_map.dim() != 1 or chan_map.numel() < 1:
+        raise ValueError(f"{who}: chan_map must be int32 (n,), n >= 1")
+    N = channel_index.numel()
+    for name, t, want in (("channel_index", channel_index, torch.int32), ("ping_index", ping_index, torch.int32),
+                          ("range_sample", range_sample, torch.int32), ("target_range", target_range, torch.float64),
+                          ("angle_alongship", angle_alongship, torch.float64),
+                          ("angle_athwartship", angle_athwartship, torch.float64)):
+        if t.dtype != want or tuple(t.shape) != (N,):
+            raise ValueError(f"{who}: {name} must be {want} of shape ({N},), got {t.dtype} {tuple(t.shape)}")
+    dev = re.device
+    ts = torch.empty((N, F), dtype=td, device=dev)
+    ts_uncomp = torch.empty((N, F), dtype=td, device=dev)
+    n_window = torch.empty(N, dtype=torch.int32, device=dev)
+    if N == 0:
+        return ts, ts_uncomp, n_window
+    table = _scratch("target_spectra.table", dev, R, F)
+    call("epa_target_spectra", _p(re), _p(im), _DT[re.dtype], C, P, S, B, _p(replica), _p(replica_off), _p(replica_id), R,
+         replica.numel() // 2, max_taps, _p(rep_dt), _p(fparams), F, h, _p(pparams), _p(chan_map), chan_map.numel(),
+         _p(channel_index), _p(ping_index), _p(range_sample), _p(target_range), _p(angle_alongship),
+         _p(angle_athwartship), N, _p(table), _p(ts), _p(ts_uncomp), _DT[td], _p(n_window), _stream())
+    return ts, ts_uncomp, n_window
+
+
 # ---- target tracking (targets.track_targets) --------------------------------------------------------------------------
 TRACK_TILE = _lib.TRACK_TILE  # rows of a run a workgroup of propose / accept stages in LDS at a time (EPA_TRACK_TILE)
 

@@ -562,3 +562,82 @@ def single_target_scene(P=37, S=257, seed=20261020, dtype=np.float64, seam=1024,
                         put(p, m - 4 * k, sh[::-1])    # the peak on the seam, the long side before it
     return {"TS": ts.astype(dtype), "angle_alongship": al.astype(dtype), "angle_athwartship": at.astype(dtype),
             "echo_range": (dr * np.arange(S)).astype(dtype)}
+
+
+# ---------------------------------------------------------------------------------------- target strength spectra
+# (targets.target_spectra; new generators with their own seeds: the ones above are untouched)
+def ek80_bandpass_filters(f_start=None, f_stop=None):
+    """Band-pass stand-ins for the Vendor_specific WBT / PC filter coefficients, one dict per channel (a list, which
+    ``echodata.from_ek80_arrays`` takes).  ``ek80_filters()`` does not pass the transmit band: the replica spectrum A(f)
+    of targets.target_spectra is 40 to 100 dB down in band on it.  Here, for the band ``f_start .. f_stop`` of a
+    channel (default: ``EK80_BB``), centre fc and width bw:
+      stage 1: firwin(47, 0.65 bw, fs=1.5e6) times exp(2 pi i fc k / 1.5e6), decimated by 6;
+      stage 2: firwin(91, 0.6 bw, fs=250e3) times exp(2 pi i fc k / 250e3), decimated by 2."""
+    from scipy import signal
+
+    f0 = np.asarray(EK80_BB["f_start"] if f_start is None else f_start, dtype=np.float64)
+    f1 = np.asarray(EK80_BB["f_stop"] if f_stop is None else f_stop, dtype=np.float64)
+    out = []
+    for a, b in zip(f0, f1):
+        fc, bw = (a + b) / 2, b - a
+        wbt = signal.firwin(47, 0.65 * bw, fs=1.5e6) * np.exp(2j * np.pi * fc * np.arange(47) / 1.5e6)
+        pc = signal.firwin(91, 0.6 * bw, fs=250e3) * np.exp(2j * np.pi * fc * np.arange(91) / 250e3)
+        out.append(dict(wbt_fil=wbt.astype(np.complex64), wbt_decifac=6, pc_fil=pc.astype(np.complex64), pc_decifac=2))
+    return out
+
+
+def target_spectra_scene(C=2, P=3, S=400, B=4, seed=20261021, dtype=np.float64, noise=1e-4, tail=40, echoes=None):
+    """An EK80 FM data set with point echoes of KNOWN strength for targets.target_spectra: ``ek80_numpy``'s dictionary
+    (its own stream, unchanged) with ``filters`` = ``ek80_bandpass_filters()``, ``beam_type`` 1 and the samples replaced
+    by
+    - a noise floor: complex normal of standard deviation ``noise`` per part (0: none);
+    - echoes ``K tx`` -- ``tx`` the channel's transmit replica rounded to complex64, the values compute_TS uploads --
+      planted from sample ``s`` on with the sector phases of ``splitbeam_sector_phases`` for the electrical angles
+      ``(e_al, e_at)`` in degrees; ``echoes``: a list of (c, p, s, K, e_al, e_at), default: six per channel -- whole
+      echoes 200 samples or more apart, among them one at sample 0, one that ends just in front of the NaN tail and one
+      that ends with the row (7 samples earlier on the second channel), and one at the last sample, cut off by the end
+      of the row;
+    - NaN tails: the last ``tail`` samples of ping 1 of every channel, all sectors;
+    - one mixed-sector patch: sector 1 NaN at samples S/2 + 3 .. S/2 + 7 of (channel 0, ping 0), inside the echo at
+      S/2, and the imaginary part alone of the last sector at sample 200 of the last (channel, ping).
+    The sector mean of an echo is ``K cos(e_al / 2) cos(e_at / 2) tx`` (beam type 1).  Returns (d, replicas, echoes):
+    the dictionary (samples of ``dtype``), the complex64 replicas per channel and the list of echoes."""
+    from .calibrate.ek80_complex import filter_decimate_chirp, tapered_chirp
+
+    d = ek80_numpy(C=C, P=P, S=S, B=B, seed=seed, waveform="BB")
+    filters = ek80_bandpass_filters(d["f_start"], d["f_stop"])
+    replicas = []
+    for c in range(C):
+        y, _ = tapered_chirp(d["fs"][c], d["tau"][c], d["slope"][c], d["f_start"][c], d["f_stop"][c])
+        tx, _ = filter_decimate_chirp(filters[c], y, d["fs"][c])
+        replicas.append(np.asarray(tx).astype(np.complex64))
+    rng = np.random.default_rng(seed + 11)
+    x = (rng.standard_normal((C, P, S, B)) + 1j * rng.standard_normal((C, P, S, B))) * noise
+    if echoes is None:
+        echoes = []
+        for c in range(C):
+            L = replicas[c].size
+            # whole echoes, 200 samples or more apart, the last of a ping ending with the row (or in front of the NaN
+            # tail), and one cut off by the end of the row
+            echoes += [(c, 0, 0, 0.31, 0.0, 0.0), (c, 0, S // 2, 0.08, 40.0, -25.0),
+                       (c, 1 % P, max(S - tail - L - 1, 0), 0.22, 15.0, 35.0),
+                       (c, P - 1, 30, 0.12, 0.0, 0.0), (c, P - 1, max(S - L - (7 if c else 0), 0), 0.27, 30.0, 30.0),
+                       (c, P - 1, S - 1, 0.5, -20.0, -45.0)]
+    for c, p, s, K, e_al, e_at in echoes:
+        tx = replicas[c].astype(np.complex128)
+        n = min(tx.size, S - s)
+        sec = splitbeam_sector_phases(np.float64(e_al), np.float64(e_at), 1)[:B]
+        x[c, p, s:s + n, :] += K * tx[:n, None] * sec[None, :]
+    re = np.ascontiguousarray(x.real).astype(dtype)
+    im = np.ascontiguousarray(x.imag).astype(dtype)
+    if P > 1 and tail > 0:
+        re[:, 1, S - tail:, :] = np.nan
+        im[:, 1, S - tail:, :] = np.nan
+    if B > 1 and S > 200:
+        re[0, 0, S // 2 + 3:S // 2 + 8, 1] = np.nan
+        im[0, 0, S // 2 + 3:S // 2 + 8, 1] = np.nan
+        im[C - 1, P - 1, 200, B - 1] = np.nan
+    d["backscatter_r"], d["backscatter_i"] = re, im
+    d["beam_type"] = np.ones(C, dtype=np.int64)
+    d["filters"] = filters
+    return d, replicas, list(echoes)

@@ -1222,6 +1222,36 @@ int epa_track_table(const int* channel_index, const int* ping_index, const doubl
                     long long n, long long T, long long M, int* track_id, int* order, int* start, int* icols,
                     double* fcols, epa_stream_t stream);
 
+/* ---- target strength spectra: targets.target_spectra (targets/spectra.py) ---------------------------------------------
+ * TS(f) of every row of a single-target table from the complex sector samples of EK80 FM pings, by this project's
+ * restatement of Andersen et al. (2021); targets/spectra.py states the eight rules.  All arithmetic is f64.
+ * re, im: [C*P*S*B] of in_dtype F32 / F64, the sectors of a sample adjacent.  replica: interleaved (re, im) f32 of
+ * replica_len complex elements; replica r is [replica_off[r], replica_off[r+1]) (i32 [n_replicas + 1]) and may hold 1 ..
+ * max_taps <= EPA_TARGET_SPECTRA_MAX_TAPS taps; ping (c, p) uses replica replica_id[c*P + p] (i32, optional; NULL: replica
+ * c).  rep_dt f64 [n_replicas]: the sample interval of the pings of a replica.  fparams f64
+ * [n_replicas][EPA_TARGET_SPECTRA_FPARAMS][F]: per replica and frequency f (Hz), absorption, gain, z_et, beamwidth
+ * alongship / athwartship, angle offset alongship / athwartship.  pparams f64 [EPA_TARGET_SPECTRA_PPARAMS][C*P]:
+ * transmit power, sound speed, z_er.  chan_map i32 [n_map]: the channel of the cubes a table channel stands for.
+ * The table: t_channel, t_ping, t_sample i32 [N], t_range, t_along, t_athw f64 [N].  A row whose indices, replica index or
+ * replica offsets lie outside what the arrays hold gives NaN and n_window 0; no byte outside the arrays is read, whatever
+ * the table holds.
+ * table: scratch, f64 [n_replicas][EPA_TARGET_SPECTRA_TABLE_ROWS][F], sized by
+ * epa_scratch_bytes("target_spectra.table", n_replicas, F).  ts_out, ts_uncomp_out: [N][F] of out_dtype; n_window i32 [N]:
+ * the samples of the window inside the ping with a valid sector.  N == 0 launches nothing. */
+#define EPA_TARGET_SPECTRA_MAX_HALF_WINDOW 127
+#define EPA_TARGET_SPECTRA_MAX_FREQ 1024
+#define EPA_TARGET_SPECTRA_MAX_TAPS 2048
+#define EPA_TARGET_SPECTRA_FPARAMS 8
+#define EPA_TARGET_SPECTRA_PPARAMS 3
+#define EPA_TARGET_SPECTRA_TABLE_ROWS 3
+int epa_target_spectra(const void* re, const void* im, int in_dtype, long long C, long long P, long long S, int B,
+                       const float* replica, const int32_t* replica_off, const int32_t* replica_id, int n_replicas,
+                       long long replica_len, int max_taps, const double* rep_dt, const double* fparams, int F,
+                       int half_window, const double* pparams, const int32_t* chan_map, int n_map,
+                       const int32_t* t_channel, const int32_t* t_ping, const int32_t* t_sample, const double* t_range,
+                       const double* t_along, const double* t_athw, long long N, double* table, void* ts_out,
+                       void* ts_uncomp_out, int out_dtype, int32_t* n_window, epa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
