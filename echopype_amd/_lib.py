@@ -83,6 +83,12 @@ TARGET_SPECTRA_FPARAMS, TARGET_SPECTRA_PPARAMS, TARGET_SPECTRA_TABLE_ROWS = 8, 3
 TARGET_SPECTRA_FPARAM_NAMES = ("frequency", "sound_absorption", "gain_correction", "impedance_transducer", "beamwidth_alongship",
                                "beamwidth_athwartship", "angle_offset_alongship", "angle_offset_athwartship")  # the rows of fparams
 TARGET_SPECTRA_PPARAM_NAMES = ("transmit_power", "sound_speed", "impedance_transceiver")  # the rows of pparams
+SV_SPECTRUM_MAX_WINDOW, SV_SPECTRUM_MAX_FREQ, SV_SPECTRUM_MAX_TAPS = 1024, 1024, 2048  # EPA_SV_SPECTRUM_MAX_*
+SV_SPECTRUM_MAX_TILE_CELLS = 128  # EPA_SV_SPECTRUM_MAX_TILE_CELLS
+SV_SPECTRUM_FPARAMS, SV_SPECTRUM_PPARAMS, SV_SPECTRUM_TABLE_ROWS = 5, 4, 3  # EPA_SV_SPECTRUM_FPARAMS, _PPARAMS, _TABLE_ROWS
+SV_SPECTRUM_FPARAM_NAMES = ("frequency", "sound_absorption", "gain_correction", "impedance_transducer",
+                            "equivalent_beam_angle")  # the rows of its fparams
+SV_SPECTRUM_PPARAM_NAMES = ("transmit_power", "sound_speed", "impedance_transceiver", "sample_interval")  # ... of its pparams
 
 
 class EpaError(RuntimeError):
@@ -230,6 +236,9 @@ SIGNATURES = {
     "epa_track_table": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
     "epa_target_spectra": [_vp, _vp, _i, _ll, _ll, _ll, _i, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _i, _i, _vp, _vp, _i,
                            _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp],
+    "epa_sv_spectrum": [_vp, _vp, _i, _ll, _ll, _ll, _i, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _i, _vp, _vp, _i, _ll, _ll,
+                        _vp, _vp, _i, _vp, _vp],
+    "epa_sv_spectrum_plan": [_i, _i, _ll, _ll, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_sz)],
 }
 
 for _name, _args in SIGNATURES.items():

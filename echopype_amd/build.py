@@ -25,7 +25,7 @@ SOURCES = ["runtime.hip", "power_coef.hip", "sv_power.hip", "block_reduce.hip", 
            "ek80_complex.hip", "ek80_fft.hip", "noise_masks.hip", "nasc.hip", "chain_fast.hip", "edge_exchange.hip",
            "splitbeam.hip", "seafloor.hip", "shoal.hip", "transient.hip", "mask_grid.hip", "line_mask.hip", "regrid.hip", "window_filter.hip", "metrics.hip", "align.hip", "qc.hip",
            "combine.hip", "raw_ingest.hip", "nmea.hip", "region_stats.hip", "single_target.hip", "track.hip",
-           "target_spectrum.hip"]
+           "target_spectrum.hip", "sv_spectrum.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 EXTRA = os.environ.get("EPA_EXTRA_FLAGS", "").split()
 FLAGS = [*EXTRA, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",

@@ -253,6 +253,7 @@ size_t transient_matecho_flag(long long C, long long P, long long);             
 size_t time_rebuild_tile_workspace(long long N, long long, long long);            // qc.hip
 size_t regrid_mask_out(long long G, long long n_tbins, long long n_rbins);        // mask_grid.hip
 size_t target_spectra_table(long long R, long long F, long long);                 // target_spectrum.hip
+size_t sv_spectrum_table(long long R, long long F, long long);                    // sv_spectrum.hip
 }  // namespace scratch
 
 // `used` bytes are about to be written to a scratch buffer the caller sized as `have` = its scratch:: function

@@ -112,6 +112,7 @@ int epa_scratch_bytes(const char* what, long long a, long long b, long long c, s
       {"time_rebuild.tile_workspace", s::time_rebuild_tile_workspace},
       {"regrid_mask.out", s::regrid_mask_out},
       {"target_spectra.table", s::target_spectra_table},
+      {"sv_spectrum.table", s::sv_spectrum_table},
   };
   EPA_CHECK_ARG(what != nullptr && bytes_out != nullptr, "epa_scratch_bytes: NULL argument");
   EPA_CHECK_ARG(a >= 0 && b >= 0 && c >= 0, "epa_scratch_bytes: %s: negative size (%lld, %lld, %lld)", what, a, b, c);

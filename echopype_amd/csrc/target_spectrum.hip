@@ -4,6 +4,7 @@
 // states them word for word and tests/target_spectra_ref.py is the NumPy judge.  One entry, two kernels:
 //   target_spectrum_replica_kernel   per replica: E = sum |tx|^2, the autocorrelation a(m), |m| <= min(h, L - 1), and
 //                                    per frequency the step w = exp(-2 pi i f dt) and 1 / |A(f)|^2 -> `table`
+//                                    (spectrum_common.h: shared with sv_spectrum.hip, as is the staging of a span)
 //   target_spectrum_kernel           per target: window staged, pulse compression, F Fourier sums, rules 5 to 7
 //
 // A target belongs to one workgroup (256 lanes), which takes further targets in a loop.  The samples s-h .. s+h+L-1 of
@@ -15,13 +16,17 @@
 // sums are one lane per frequency: Y(f) = sum_n pc(s+n) w^n is evaluated by Horner's rule on the window in LDS (every
 // lane reads the same sample: a broadcast), and since only |Y / A| enters rule 5 the unit factor w^-h is left out.
 // All arithmetic is float64.  Not a GEMM: 2h+1 outputs per target are too few rows for MFMA tiles.
-#include "wg_reduce.h"
+#include "spectrum_common.h"
 
 namespace {
 
 using epa::kBlock;
 using epa::kWave;
 using epa::kWaves;
+using epa::spectrum::Cd;
+using epa::spectrum::replica_taps;
+using epa::spectrum::stage_replica;
+using epa::spectrum::stage_window;
 
 constexpr int kMaxH = EPA_TARGET_SPECTRA_MAX_HALF_WINDOW;
 constexpr int kMaxF = EPA_TARGET_SPECTRA_MAX_FREQ;
@@ -32,11 +37,8 @@ constexpr int kMaxBeams = 8;
 constexpr int kMaxGrid = 1 << 20;  // workgroups of a launch; each takes further targets in a loop
 static_assert(2 * kMaxH + 1 <= kBlock, "one lane per compressed sample");
 
-struct Cd {
-  double re, im;
-};
-
 struct Args {
+  static constexpr int kFParams = kFP, kTableRows = kTab;  // (what spectrum_common.h reads)
   const void* re;
   const void* im;
   long long C, P, S;
@@ -66,106 +68,6 @@ struct Args {
   int32_t* n_window;
   unsigned xs_off, part_off, pc_off, mask_off;  // byte offsets in dynamic LDS (the replica is first)
 };
-
-// the taps of replica r, or 0 when its offsets do not describe 1 .. max_taps taps inside the array
-__device__ __forceinline__ int replica_taps(const Args& a, int r, int& r0) {
-  r0 = a.replica_off[r];
-  const long long r1 = a.replica_off[r + 1];
-  const long long L = r1 - r0;
-  return (r0 >= 0 && r1 <= a.replica_len && L >= 1 && L <= a.max_taps) ? (int)L : 0;
-}
-
-// replica -> LDS as float64 (conj is applied in the MAC); E = sum |tx|^2, the same bits in every lane and in both kernels
-__device__ __forceinline__ double stage_replica(const Args& a, int r0, int L, Cd* rep, double* red) {
-  double part = 0.0;
-  for (int k = threadIdx.x; k < L; k += kBlock) {
-    const Cd t{(double)a.replica[2 * (size_t)(r0 + k)], (double)a.replica[2 * (size_t)(r0 + k) + 1]};
-    rep[k] = t;
-    part += t.re * t.re + t.im * t.im;
-  }
-  part = epa::wave_sum(part);
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = part;
-  __syncthreads();
-  return epa::slots_sum(red);
-}
-
-__global__ __launch_bounds__(kBlock) void replica_table_kernel(Args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Cd* rep = reinterpret_cast<Cd*>(smem);
-  Cd* ac = reinterpret_cast<Cd*>(smem + a.xs_off);  // a(0 .. hh)
-  __shared__ double red[kWaves];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  double* tab = a.table + (size_t)r * kTab * a.F;
-  int r0;
-  const int L = replica_taps(a, r, r0);
-  if (L == 0) {  // (uniform) no target is served by this replica
-    for (int j = tid; j < a.F; j += kBlock) tab[j] = tab[a.F + j] = tab[2 * a.F + j] = __builtin_nan("");
-    return;
-  }
-  const double E = stage_replica(a, r0, L, rep, red);
-  const int hh = a.h < L - 1 ? a.h : L - 1;
-  // a(m) = (1/E) sum_k tx(k+m) conj(tx(k)): a wavefront per lag, the lanes stride over k
-  for (int m = wave; m <= hh; m += kWaves) {
-    double sr = 0.0, si = 0.0;
-    for (int k = lane; k + m < L; k += kWave) {
-      const Cd x = rep[k + m], t = rep[k];
-      sr += x.re * t.re + x.im * t.im;
-      si += x.im * t.re - x.re * t.im;
-    }
-    sr = epa::wave_sum(sr), si = epa::wave_sum(si);
-    if (lane == 0) ac[m] = Cd{sr / E, si / E};
-  }
-  __syncthreads();
-  const double dt = a.rep_dt[r];
-  const double* fp = a.fparams + (size_t)r * kFP * a.F;
-  for (int j = tid; j < a.F; j += kBlock) {
-    double ws, wc;
-    ::sincospi(-2.0 * (fp[j] * dt), &ws, &wc);  // w = exp(-2 pi i f dt)
-    // A = a(0) + sum_{m >= 1} a(m) w^m + conj(a(m)) conj(w^m)      (a(-m) = conj(a(m)), |w| = 1)
-    double Ar = ac[0].re, Ai = ac[0].im, pr = 1.0, pi = 0.0;
-    for (int m = 1; m <= hh; ++m) {
-      const double qr = pr * wc - pi * ws, qi = pr * ws + pi * wc;
-      pr = qr, pi = qi;
-      const Cd v = ac[m];
-      Ar += 2.0 * (v.re * pr - v.im * pi);  // a w^m + conj(a w^m) ... conj(a) conj(p) = conj(a p)
-    }
-    tab[j] = wc;
-    tab[a.F + j] = ws;
-    tab[2 * a.F + j] = 1.0 / (Ar * Ar + Ai * Ai);
-  }
-}
-
-// samples [first, first + len) of one ping -> xs: the sum of the valid sectors (only < 0) or sector `only` alone; the
-// validity bits of every sample -> vmask (only < 0).  Samples outside [0, S) are zero with no valid sector.
-template <typename InT>
-__device__ __forceinline__ unsigned stage_window(const InT* __restrict__ re, const InT* __restrict__ im, size_t ping_base,
-                                                 long long S, int B, long long first, int len, int only, Cd* xs,
-                                                 uint8_t* vmask) {
-  unsigned mixed = 0;
-  const unsigned full = (1u << B) - 1u;
-  for (int i = threadIdx.x; i < len; i += kBlock) {
-    const long long n = first + i;
-    double sr = 0.0, si = 0.0;
-    unsigned m = 0;
-    if (n >= 0 && n < S) {
-      const InT* pr = re + ping_base + (size_t)n * B;
-      const InT* pi = im + ping_base + (size_t)n * B;
-      for (int b = 0; b < B; ++b) {
-        const InT vr = pr[b], vi = pi[b];
-        if (vr == vr && vi == vi) {
-          m |= 1u << b;
-          if (only < 0 || only == b) sr += (double)vr, si += (double)vi;
-        }
-      }
-    }
-    xs[i] = Cd{sr, si};
-    if (only < 0) {
-      vmask[i] = (uint8_t)m;
-      if (m != 0u && m != full) mixed = 1u;
-    }
-  }
-  return mixed;
-}
 
 // y(i) = sum_k xs(i + k) conj(rep(k)), i < W: the tap sum of output i split over G lanes, added in lane order by lane i.
 // (barriers inside: every lane of the workgroup calls it)
@@ -360,8 +262,9 @@ extern "C" int epa_target_spectra(const void* re, const void* im, int in_dtype, 
   {
     // (the replica, then the lags a(0 .. h) where the main kernel keeps its window)
     const size_t lds = (size_t)l.xs_off + (size_t)(half_window + 1) * sizeof(Cd);
-    if (int rc = epa::allow_lds(replica_table_kernel, lds)) return rc;
-    hipLaunchKernelGGL(replica_table_kernel, dim3((unsigned)n_replicas), dim3(kBlock), lds, st, a);
+    auto kern = epa::spectrum::replica_table_kernel<Args>;
+    if (int rc = epa::allow_lds(kern, lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_replicas), dim3(kBlock), lds, st, a);
     if (int rc = epa::check_launch("target_spectrum_replica_kernel")) return rc;
   }
   const unsigned grid = (unsigned)(N < kMaxGrid ? N : kMaxGrid);

@@ -1174,6 +1174,81 @@ def target_spectra(re, im, replica, replica_off, max_taps, rep_dt, fparams, ppar
     return ts, ts_uncomp, n_window
 
 
+# ---- volume backscattering spectra (calibrate.compute_Sv_spectrum) -------------------------------------------------------
+def sv_spectrum_cells(S, window_samples, step_samples):
+    """The cells of a ping of ``S`` samples: ``floor((S - window_samples) / step_samples) + 1``."""
+    return (int(S) - int(window_samples)) // int(step_samples) + 1
+
+
+def sv_spectrum_plan(max_taps, window_samples, step_samples, M):
+    """The tile ``epa_sv_spectrum`` takes -> (cells of a tile, tiles of a ping, bytes of LDS of a workgroup)."""
+    t, n, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    call("epa_sv_spectrum_plan", int(max_taps), int(window_samples), int(step_samples), int(M), ctypes.byref(t),
+         ctypes.byref(n), ctypes.byref(b))
+    return t.value, n.value, b.value
+
+
+def sv_spectrum(re, im, replica, replica_off, max_taps, rep_dt, fparams, pparams, window, step_samples, *, replica_id=None,
+                dtype="float64", out=None):
+    """Sv(f) of the range cells of every ping (``epa_sv_spectrum``; calibrate/sv_spectrum.py states the rules).
+
+    ``re``, ``im``, ``replica``, ``replica_off``, ``max_taps``, ``replica_id``, ``rep_dt``: as for ``target_spectra``
+    (``max_taps`` at most ``_lib.SV_SPECTRUM_MAX_TAPS``).  ``fparams`` float64 (R, 5, F) in the order of
+    ``_lib.SV_SPECTRUM_FPARAM_NAMES``; ``pparams`` float64 (4, C, P) in the order of ``_lib.SV_SPECTRUM_PPARAM_NAMES``.
+    ``window`` float64 (N_w,): the normalised window; ``step_samples``: the hop.  ``out``: optionally the two results to
+    write into.  -> (``Sv_spectrum`` (C, P, M, F) of ``dtype``, ``echo_range`` float64 (C, P, M)), M =
+    ``sv_spectrum_cells(S, N_w, hop)``."""
+    who = "sv_spectrum"
+    td = torch_dtype(dtype)
+    if re.dim() != 4 or re.dtype not in _DT or im.dtype != re.dtype or im.shape != re.shape:
+        raise ValueError(f"{who}: re and im must be float32 / float64 of one shape (C, P, S, B), got {re.dtype} "
+                         f"{tuple(re.shape)} and {im.dtype} {tuple(im.shape)}")
+    C, P, S, B = re.shape
+    max_taps, hop = int(max_taps), int(step_samples)
+    if not 1 <= max_taps <= _lib.SV_SPECTRUM_MAX_TAPS:
+        raise ValueError(f"{who}: replicas of up to {_lib.SV_SPECTRUM_MAX_TAPS} taps are served, got max_taps {max_taps}")
+    if window.dtype != torch.float64 or window.dim() != 1 or not 2 <= window.numel() <= _lib.SV_SPECTRUM_MAX_WINDOW:
+        raise ValueError(f"{who}: window must be float64 of 2 .. {_lib.SV_SPECTRUM_MAX_WINDOW} samples, got {window.dtype} "
+                         f"{tuple(window.shape)}")
+    Nw = window.numel()
+    if not 1 <= hop < 2 ** 31 - 1:
+        raise ValueError(f"{who}: step_samples {hop} outside 1 .. 2**31 - 2")
+    if S < Nw:
+        raise ValueError(f"{who}: a window of {Nw} samples on pings of {S}")
+    if replica.dtype != torch.float32 or replica.dim() != 1 or replica.numel() % 2 or replica_off.dtype != torch.int32 \
+            or replica_off.dim() != 1 or replica_off.numel() < 2:
+        raise ValueError(f"{who}: replica float32 (2 n,) and replica_off int32 (R + 1,) expected")
+    R = replica_off.numel() - 1
+    if replica_id is not None and (replica_id.dtype != torch.int32 or tuple(replica_id.shape) != (C, P)):
+        raise ValueError(f"{who}: replica_id must be int32 of shape {(C, P)}")
+    if replica_id is None and R < C:
+        raise ValueError(f"{who}: without replica_id every channel needs its replica ({R} replicas, {C} channels)")
+    if fparams.dtype != torch.float64 or fparams.dim() != 3 or fparams.shape[:2] != (R, _lib.SV_SPECTRUM_FPARAMS):
+        raise ValueError(f"{who}: fparams must be float64 of shape ({R}, {_lib.SV_SPECTRUM_FPARAMS}, F), got "
+                         f"{fparams.dtype} {tuple(fparams.shape)}")
+    F = fparams.shape[2]
+    if not 1 <= F <= _lib.SV_SPECTRUM_MAX_FREQ:
+        raise ValueError(f"{who}: {F} frequencies outside 1 .. {_lib.SV_SPECTRUM_MAX_FREQ}")
+    if rep_dt.dtype != torch.float64 or tuple(rep_dt.shape) != (R,):
+        raise ValueError(f"{who}: rep_dt must be float64 of shape ({R},)")
+    if pparams.dtype != torch.float64 or tuple(pparams.shape) != (_lib.SV_SPECTRUM_PPARAMS, C, P):
+        raise ValueError(f"{who}: pparams must be float64 of shape {(_lib.SV_SPECTRUM_PPARAMS, C, P)}")
+    M = sv_spectrum_cells(S, Nw, hop)
+    dev = re.device
+    if out is None:
+        sv = torch.empty((C, P, M, F), dtype=td, device=dev)
+        rng = torch.empty((C, P, M), dtype=torch.float64, device=dev)
+    else:
+        sv, rng = out
+        if sv.dtype != td or tuple(sv.shape) != (C, P, M, F) or rng.dtype != torch.float64 or tuple(rng.shape) != (C, P, M):
+            raise ValueError(f"{who}: out must be ({td} {(C, P, M, F)}, float64 {(C, P, M)})")
+    table = _scratch("sv_spectrum.table", dev, R, F)
+    call("epa_sv_spectrum", _p(re), _p(im), _DT[re.dtype], C, P, S, B, _p(replica), _p(replica_off), _p(replica_id), R,
+         replica.numel() // 2, max_taps, _p(rep_dt), _p(fparams), F, _p(pparams), _p(window), Nw, hop, M, _p(table), _p(sv),
+         _DT[td], _p(rng), _stream())
+    return sv, rng
+
+
 # ---- target tracking (targets.track_targets) --------------------------------------------------------------------------
 TRACK_TILE = _lib.TRACK_TILE  # rows of a run a workgroup of propose / accept stages in LDS at a time (EPA_TRACK_TILE)
 

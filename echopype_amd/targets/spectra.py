@@ -16,18 +16,14 @@ Device work (csrc/target_spectrum.hip, ``epa_target_spectra``): one small kernel
 frequency, the Fourier step and 1 / |A(f)|^2, then one kernel with a workgroup per target.  Host work: the O(C F)
 parameter tables.  Host synchronisations: one, through ``_to_host``: which pings hold targets (their sample interval must
 be one value per replica).  An empty table ends before it, without a launch."""
-import numbers
-
 import numpy as np
 import torch
 
 from .. import _lib, ops
-from ..calibrate.cal_params import get_cal_params_EK
-from ..calibrate.calibrate_base import cp_array
-from ..calibrate.calibrate_ek import CalibrateEK80, retrieve_correct_beam_group
-from ..calibrate.env_params import get_env_params_EK
+from ..calibrate.spectrum_common import (_first_valid, band_edges, check_band, check_int, fm_beam_group,  # noqa: F401
+                                         fm_calibrator, frequency_grid, frequency_params, replica_inputs,
+                                         replica_sample_interval)
 from ..device_view import as_tensor, resolve_device
-from ..echodata import EchoData, as_lite_echodata
 from ..xr_lite import DataArray, Dataset, DeviceArray, from_xarray, is_device, xarray_io
 
 _REQUIRED = ("half_window", "n_frequencies")
@@ -41,11 +37,6 @@ def _to_host(t):
     return t.cpu()
 
 
-def _is_real(v):
-    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (numbers.Real, np.integer, np.floating)) \
-        and np.isfinite(float(v))
-
-
 def _check_params(params):
     """The keys and numbers of ``params``, checked on the host -> (half_window, n_frequencies, band_margin,
     frequency_limits as a float64 (n, 2) array or None)."""
@@ -57,94 +48,10 @@ def _check_params(params):
     missing = [k for k in _REQUIRED if k not in params]
     if missing:
         raise ValueError(f"Missing target-spectra parameter(s) {missing}")
-    for k, lo, hi in (("half_window", 0, _lib.TARGET_SPECTRA_MAX_HALF_WINDOW),
-                      ("n_frequencies", 1, _lib.TARGET_SPECTRA_MAX_FREQ)):
-        v = params[k]
-        if not _is_real(v) or float(v) != int(v) or not lo <= int(v) <= hi:
-            raise ValueError(f"{k} must be an integer from {lo} to {hi}, got {v!r}")
-    m = params.get("band_margin", 0.1)
-    if not _is_real(m) or not 0.0 <= float(m) < 0.5:
-        raise ValueError(f"band_margin must be a real number in [0, 0.5), got {m!r}")
-    lim = params.get("frequency_limits")
-    if lim is not None:
-        try:
-            lim = np.asarray(lim, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"frequency_limits must hold real numbers, got {params['frequency_limits']!r}") from None
-        if lim.ndim not in (1, 2) or lim.shape[-1] != 2 or not np.isfinite(lim).all():
-            raise ValueError(f"frequency_limits must be one finite (lo, hi) pair or one per channel, got shape {lim.shape}")
-        lim = lim.reshape(-1, 2)
-        if not ((lim[:, 0] > 0) & (lim[:, 0] <= lim[:, 1])).all():
-            raise ValueError(f"frequency_limits need 0 < lo <= hi, got {lim.tolist()}")
-    return int(params["half_window"]), int(params["n_frequencies"]), float(m), lim
-
-
-def frequency_grid(f_start, f_stop, n_frequencies, band_margin=0.1, frequency_limits=None):
-    """The frequencies (channel, frequency_index) in Hz: ``f_j = lo + j (hi - lo) / (F - 1)`` with
-    ``lo = f_start + m (f_stop - f_start)`` and ``hi = f_stop - m (f_stop - f_start)``; ``F = 1`` gives the centre
-    ``(lo + hi) / 2``.  ``frequency_limits`` ((lo, hi), or one pair per channel) overrides the band."""
-    f0 = np.atleast_1d(np.asarray(f_start, dtype=np.float64))
-    f1 = np.atleast_1d(np.asarray(f_stop, dtype=np.float64))
-    F = int(n_frequencies)
-    lo, hi = f0 + band_margin * (f1 - f0), f1 - band_margin * (f1 - f0)
-    if frequency_limits is not None:
-        lim = np.asarray(frequency_limits, dtype=np.float64).reshape(-1, 2)
-        if lim.shape[0] not in (1, f0.size):
-            raise ValueError(f"frequency_limits holds {lim.shape[0]} pairs for {f0.size} channels")
-        lim = np.broadcast_to(lim, (f0.size, 2))
-        lo, hi = lim[:, 0].copy(), lim[:, 1].copy()
-    if F == 1:
-        return ((lo + hi) / 2)[:, None]
-    return lo[:, None] + np.arange(F, dtype=np.float64)[None, :] * (hi - lo)[:, None] / (F - 1)
-
-
-def _first_valid(a):
-    """Per row of a (C, P) array its first value that is not NaN (NaN if there is none)."""
-    ok = ~np.isnan(a)
-    first = np.where(ok.any(axis=1), ok.argmax(axis=1), 0)
-    return a[np.arange(a.shape[0]), first]
-
-
-def frequency_params(cal, freq, env_params=None, cal_params=None):
-    """The parameters of rule 8 on the (channel, frequency) grid ``freq`` -> float64 (8, C, F) in the order of
-    ``_lib.TARGET_SPECTRA_FPARAM_NAMES``.  ``cal``: the file's ``CalibrateEK80`` (its beam group and vendor group).
-
-    ``get_cal_params_EK("BB", ...)`` and ``get_env_params_EK(..., freq=...)`` -- the routines ``compute_TS`` evaluates at
-    the centre frequency -- are handed the grid in place of the centre frequency, on a stand-in beam group whose ping
-    axis is the frequency axis: a file's calibration tables, the user's dictionaries and the fallbacks
-    (beamwidth x f_n / f, ...) are the same rules.  The pulse-length table of the gain fallback is read at the pulse
-    duration of each channel's first valid ping (the replica's: the transmit parameters do not change along a file or
-    filter interval)."""
-    beam, vend = cal.beam, cal.vend
-    C, F = freq.shape
-    P = beam["backscatter_r"].shape[1]
-    pt = np.asarray(beam["ping_time"].values)
-    stand = Dataset(coords={"channel": np.asarray(beam["channel"].values), "ping_time": np.repeat(pt[:1], F)})
-    tau = _first_valid(cp_array(beam["transmit_duration_nominal"], C, P))
-    stand["transmit_duration_nominal"] = (("channel", "ping_time"), np.repeat(tau[:, None], F, axis=1))
-    for name, da in beam.data_vars.items():
-        if tuple(da.dims) == ("channel",):
-            stand[name] = (("channel",), np.asarray(da.values))
-    grid = DataArray(np.ascontiguousarray(freq), ("channel", "ping_time"))
-    env = get_env_params_EK("EK80", stand, cal.echodata["Environment"], dict(env_params or {}), freq=grid)
-    calp = get_cal_params_EK("BB", grid, stand, vend, dict(cal_params or {}), sonar_type="EK80")
-
-    def on_grid(v, name):
-        dims = tuple(v.dims) if isinstance(v, DataArray) else None
-        a = np.asarray(getattr(v, "values", v), dtype=np.float64)
-        if dims == ("ping_time", "channel"):
-            a = a.T
-        if a.ndim == 1 and a.shape[0] == C and dims != ("ping_time",):
-            a = a[:, None]
-        try:
-            return np.broadcast_to(a, (C, F))
-        except ValueError:
-            raise ValueError(f"{name} of shape {a.shape} cannot be evaluated on the (channel={C}, frequency={F}) grid") \
-                from None
-
-    rows = [freq, on_grid(env["sound_absorption"], "sound_absorption")]
-    rows += [on_grid(calp[k], k) for k in _lib.TARGET_SPECTRA_FPARAM_NAMES[2:]]
-    return np.ascontiguousarray(np.stack(rows), dtype=np.float64)
+    h = check_int(params, "half_window", 0, _lib.TARGET_SPECTRA_MAX_HALF_WINDOW)
+    F = check_int(params, "n_frequencies", 1, _lib.TARGET_SPECTRA_MAX_FREQ)
+    m, lim = check_band(params)
+    return h, F, m, lim
 
 
 def _index_column(da, dev):
@@ -162,49 +69,15 @@ def spectra_inputs(cal, freq, chan_map, env_params=None, cal_params=None):
     The replicas are the complex64 values ``compute_TS`` uploads, picked through the same triple."""
     beam = cal.beam
     C, P = beam["backscatter_r"].shape[:2]
-    _, tx = cal._transmit_replicas()
-    flat, off_h, max_taps = cal._replica_arrays(tx)
-    if max_taps > _lib.TARGET_SPECTRA_MAX_TAPS:
-        raise ValueError(f"a replica of {max_taps} taps: target_spectra serves up to {_lib.TARGET_SPECTRA_MAX_TAPS}")
-    plan = cal._plan
-    rid_h = np.ascontiguousarray(plan["replica_id"]) if plan is not None else \
-        np.ascontiguousarray(np.broadcast_to(np.arange(C, dtype=np.int32)[:, None], (C, P)))
-    rep_chan = np.asarray([p[0] for p in plan["pairs"]], dtype=np.int64) if plan is not None else np.arange(C)
+    k = replica_inputs(cal, "target_spectra", _lib.TARGET_SPECTRA_MAX_TAPS)
     fp = frequency_params(cal, freq, env_params, cal_params)  # (8, C, F)
-    fparams = np.ascontiguousarray(fp[:, rep_chan].transpose(1, 0, 2))  # (R, 8, F)
+    fparams = np.ascontiguousarray(fp[:, k.pop("rep_chan")].transpose(1, 0, 2))  # (R, 8, F)
     f64 = torch.float64
     pparams = torch.stack([cal._cp_dev(beam["transmit_power"], C, P, "transmit_power", f64),
                            cal._cp_dev(cal.env_params["sound_speed"], C, P, "sound_speed", f64),
                            cal._cp_dev(cal.cal_params["impedance_transceiver"], C, P, "impedance_transceiver", f64)])
-    re, im = cal._dev(beam["backscatter_r"].data), cal._dev(beam["backscatter_i"].data)
-    if re.dtype not in (torch.float32, torch.float64) or im.dtype != re.dtype:
-        re, im = re.double(), im.double()
-    return dict(re=re.contiguous(), im=im.contiguous(),
-                replica=cal._dev(np.ascontiguousarray(flat.view(np.float32))), replica_off=cal._dev(off_h),
-                replica_id=cal._dev(rid_h) if plan is not None else None,
-                fparams=cal._dev(fparams), pparams=pparams.contiguous(),
-                chan_map=cal._dev(np.asarray(chan_map, dtype=np.int32)),
-                max_taps=max_taps, replica_id_host=rid_h,
-                sample_interval=cp_array(beam["sample_interval"], C, P))
-
-
-def replica_sample_interval(rid, si, hold):
-    """``sample_interval`` per replica: the one value of the pings that hold targets (``hold`` (C, P) bool), of the
-    replica's first ping where none does (NaN for a replica without pings).  Several values over the pings that hold
-    targets raise ``ValueError``: A(f) is a function of the replica and the sample interval."""
-    R = int(rid.max()) + 1 if rid.size else 0
-    dt = np.full(max(R, 0), np.nan)
-    for r in range(R):
-        mine = rid == r
-        held = si[mine & hold]
-        if held.size:
-            if not (held == held[0]).all():
-                raise ValueError(f"sample_interval takes several values ({np.unique(held)[:4].tolist()} ...) over the pings "
-                                 f"of replica {r} that hold targets: one value per replica is required")
-            dt[r] = held[0]
-        elif mine.any():
-            dt[r] = si[mine][0]
-    return dt
+    return dict(k, fparams=cal._dev(fparams), pparams=pparams.contiguous(),
+                chan_map=cal._dev(np.asarray(chan_map, dtype=np.int32)))
 
 
 @xarray_io()
@@ -281,17 +154,7 @@ def target_spectra(targets, echodata, params, *, env_params=None, cal_params=Non
         raise ValueError(f"target_spectra takes fewer than 2**31 - 1 rows, got {n}")
     chan = np.asarray(getattr(ds.coords["channel"], "values", ds.coords["channel"]))
 
-    if not isinstance(echodata, EchoData):
-        echodata = as_lite_echodata(echodata)
-    if echodata.sonar_model not in ("EK80", "ES80", "EA640"):
-        raise TypeError(f"target_spectra needs the complex samples of EK80 FM pings, got a {echodata.sonar_model} file")
-    try:
-        group = retrieve_correct_beam_group(echodata, "BB", "complex")
-    except RuntimeError as e:
-        raise TypeError(f"File does not contain BB mode complex samples! ({e})") from None
-    beam = echodata[group]
-    if "backscatter_i" not in beam or beam["backscatter_r"].ndim != 4:
-        raise TypeError("File does not contain BB mode complex samples!")
+    echodata, beam = fm_beam_group(echodata, "target_spectra")
     have = [str(c) for c in np.asarray(beam["channel"].values).reshape(-1)]
     missing = [str(c) for c in chan if str(c) not in have]
     if missing:
@@ -300,13 +163,9 @@ def target_spectra(targets, echodata, params, *, env_params=None, cal_params=Non
     if limits is not None and limits.shape[0] not in (1, len(chan)):
         raise ValueError(f"frequency_limits holds {limits.shape[0]} pairs for {len(chan)} channels of the table")
 
-    n_filter = echodata["Vendor_specific"].sizes.get("filter_time", 1)
-    cal = CalibrateEK80(echodata, env_params=env_params, cal_params=cal_params, ecs_file=None, waveform_mode="BB",
-                        encode_mode="complex", slice_dict={"filter_intervals": True} if n_filter > 1 else {},
-                        dtype="float64", device=device)
+    cal = fm_calibrator(echodata, env_params, cal_params, device)
     C, P = cal.beam["backscatter_r"].shape[:2]
-    f0 = _first_valid(cp_array(cal.beam["transmit_frequency_start"], C, P))
-    f1 = _first_valid(cp_array(cal.beam["transmit_frequency_stop"], C, P))
+    f0, f1 = band_edges(cal)
     freq = frequency_grid(f0, f1, F, margin)
     if limits is not None and len(chan):
         freq[chan_map] = frequency_grid(f0[chan_map], f1[chan_map], F, margin, limits)

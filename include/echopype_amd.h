@@ -1252,6 +1252,36 @@ int epa_target_spectra(const void* re, const void* im, int in_dtype, long long C
                        const double* t_along, const double* t_athw, long long N, double* table, void* ts_out,
                        void* ts_uncomp_out, int out_dtype, int32_t* n_window, epa_stream_t stream);
 
+/* ---- volume backscattering spectra: calibrate.compute_Sv_spectrum (calibrate/sv_spectrum.py) --------------------------
+ * Sv(f) of range cells (a short-time Fourier analysis of the pulse-compressed pings) from the complex sector samples of
+ * EK80 FM pings, by this project's restatement of Andersen et al. (2021); calibrate/sv_spectrum.py states the ten rules.
+ * All arithmetic is f64.  re, im, replica, replica_off, replica_id, rep_dt: as for epa_target_spectra, with max_taps <=
+ * EPA_SV_SPECTRUM_MAX_TAPS.  fparams f64 [n_replicas][EPA_SV_SPECTRUM_FPARAMS][F]: per replica and frequency f (Hz),
+ * absorption, gain, z_et, equivalent beam angle (dB).  pparams f64 [EPA_SV_SPECTRUM_PPARAMS][C*P]: transmit power, sound
+ * speed, z_er, sample interval.  window f64 [window_samples]: the normalised window w~.  Cell m of a ping holds the
+ * samples m * step_samples .. m * step_samples + window_samples - 1; M = (S - window_samples) / step_samples + 1 cells.
+ * table: scratch, f64 [n_replicas][EPA_SV_SPECTRUM_TABLE_ROWS][F], sized by epa_scratch_bytes("sv_spectrum.table",
+ * n_replicas, F).  sv_out [C*P][M][F] of out_dtype; range_out f64 [C*P][M]: the cell centres, written for every cell.  A
+ * ping whose replica index or replica offsets lie outside what the arrays hold gives NaN cells; no byte outside the arrays
+ * is read.  A workgroup serves a tile of consecutive cells of one ping: as many as keep its LDS within a third of a CU's
+ * 160 KiB, at most EPA_SV_SPECTRUM_MAX_TILE_CELLS, evenly filled (epa_sv_spectrum_plan tells); one cell of the largest
+ * window with the largest replica takes 107 KiB, so every combination within the limits is served. */
+#define EPA_SV_SPECTRUM_MAX_WINDOW 1024
+#define EPA_SV_SPECTRUM_MAX_FREQ 1024
+#define EPA_SV_SPECTRUM_MAX_TAPS 2048
+#define EPA_SV_SPECTRUM_MAX_TILE_CELLS 128
+#define EPA_SV_SPECTRUM_FPARAMS 5
+#define EPA_SV_SPECTRUM_PPARAMS 4
+#define EPA_SV_SPECTRUM_TABLE_ROWS 3
+int epa_sv_spectrum(const void* re, const void* im, int in_dtype, long long C, long long P, long long S, int B,
+                    const float* replica, const int32_t* replica_off, const int32_t* replica_id, int n_replicas,
+                    long long replica_len, int max_taps, const double* rep_dt, const double* fparams, int F,
+                    const double* pparams, const double* window, int window_samples, long long step_samples, long long M,
+                    double* table, void* sv_out, int out_dtype, double* range_out, epa_stream_t stream);
+/* the tile epa_sv_spectrum takes for M cells per ping: cells of a tile, tiles of a ping, bytes of LDS of a workgroup */
+int epa_sv_spectrum_plan(int max_taps, int window_samples, long long step_samples, long long M, int* tile_cells, int* tiles,
+                         size_t* lds_bytes_out);
+
 #ifdef __cplusplus
 }
 #endif
