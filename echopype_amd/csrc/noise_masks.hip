@@ -3608,13 +3608,15 @@ size_t epa::scratch::pool_sv_value_ws_median(long long C, long long S, long long
 extern "C" int epa_apply_masks(const void* src, const uint8_t* const* masks, const size_t* mask_periods, int n_masks,
                                size_t n, double fill_value, const void* fill_array, size_t fill_period, void* out,
                                double* workspace, double* minmax_out, int dtype, epa_stream_t stream) {
-  EPA_CHECK_ARG(src && masks && mask_periods && out, "epa_apply_masks: NULL array argument");
+  // (an array of no elements may be NULL: n == 0 reads and writes none of src, the masks, the fill array and out)
+  EPA_CHECK_ARG(((src && out) || n == 0) && masks && mask_periods, "epa_apply_masks: NULL array argument");
   EPA_CHECK_ARG(n_masks >= 1 && n_masks <= 4, "epa_apply_masks: 1 to 4 masks (got %d)", n_masks);
   MaskSet ms{};
   ms.n = n_masks;
   for (int k = 0; k < n_masks; ++k) {
-    EPA_CHECK_ARG(masks[k] != nullptr, "epa_apply_masks: mask %d is NULL", k);
-    EPA_CHECK_ARG(mask_periods[k] > 0 && n % mask_periods[k] == 0, "epa_apply_masks: mask %d does not tile the source", k);
+    EPA_CHECK_ARG(masks[k] != nullptr || n == 0, "epa_apply_masks: mask %d is NULL", k);
+    EPA_CHECK_ARG(n == 0 || (mask_periods[k] > 0 && n % mask_periods[k] == 0),
+                  "epa_apply_masks: mask %d does not tile the source", k);
     ms.m[k] = masks[k];
     ms.period[k] = mask_periods[k];
   }
@@ -3622,10 +3624,14 @@ extern "C" int epa_apply_masks(const void* src, const uint8_t* const* masks, con
                 "epa_apply_masks: fill array does not tile the source");
   EPA_CHECK_REAL("epa_apply_masks", dtype);
   EPA_CHECK_ARG(!minmax_out || workspace, "epa_apply_masks: minmax_out needs the workspace");
-  if (n == 0) return EPA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {  // nothing to select from: the {min, max} of no values is {NaN, NaN}, and it is written all the same
+    if (!minmax_out) return EPA_OK;
+    hipLaunchKernelGGL(minmax_pairs_kernel, dim3(1), dim3(kBlock), 0, st, workspace, 0, minmax_out);
+    return epa::check_launch("minmax_pairs_kernel");
+  }
   const size_t blocks = (n + kBlock - 1) / kBlock;
   const int grid = (int)(blocks < (size_t)kApplyMasksMaxGrid ? blocks : kApplyMasksMaxGrid);
-  hipStream_t st = (hipStream_t)stream;
   double* part = minmax_out ? workspace : nullptr;
   if (part)
     EPA_CHECK_SCRATCH("epa_apply_masks", "workspace", 2 * sizeof(double) * (size_t)grid,

@@ -77,7 +77,7 @@ reversal_medians_kernel(const int64_t* __restrict__ t, int win_len, const int64_
     if (r < count) {
       ni = list[r];
       lo = ni > win_len ? ni - win_len : 0;
-      n = (int)(ni - lo);  // 0 .. win_len <= EPA_QC_MAX_WIN; 0 (a reversal in the first difference): nothing is written
+      n = (int)(ni - lo);  // 0 .. win_len <= EPA_QC_MAX_WIN; 0 (a reversal in the first difference): NaT is written
     }
     for (int j = lane; j < n; j += 64) win[j] = wrap_sub(t[lo + j + 1], t[lo + j]);
     __syncthreads();
@@ -95,7 +95,9 @@ reversal_medians_kernel(const int64_t* __restrict__ t, int win_len, const int64_
       if (rank == k_hi) mid_all[wave][1] = v;
     }
     __syncthreads();
-    if (lane == 0 && n > 0) sub[ni] = (n & 1) ? mid_all[wave][0] : mid_of(mid_all[wave][0], mid_all[wave][1]);
+    // (an empty window, the reversal in the first difference: NaT, the median of nothing -- every listed entry is written)
+    if (lane == 0 && r < count)
+      sub[ni] = n == 0 ? kNaT : (n & 1) ? mid_all[wave][0] : mid_of(mid_all[wave][0], mid_all[wave][1]);
   }
 }
 

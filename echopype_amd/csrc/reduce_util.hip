@@ -393,7 +393,8 @@ int epa_minmax_final(const double* part, int nparts, double* out, hipStream_t st
 
 extern "C" int epa_nanminmax(const void* x, size_t n, int dtype, double* workspace, double* out,
                              epa_stream_t stream) {
-  EPA_CHECK_ARG(x && workspace && out, "epa_nanminmax: NULL array argument");
+  // (n == 0: x may be NULL, nothing is read; the one workgroup leaves the empty partial and out is {NaN, NaN, 0})
+  EPA_CHECK_ARG((x || n == 0) && workspace && out, "epa_nanminmax: NULL array argument");
   EPA_CHECK_REAL("epa_nanminmax", dtype);
   const size_t blocks = (n + epa::kBlock - 1) / epa::kBlock;
   const int grid = (int)(blocks < (size_t)epa::kMinmaxMaxGrid ? (blocks ? blocks : 1) : epa::kMinmaxMaxGrid);

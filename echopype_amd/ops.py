@@ -523,14 +523,21 @@ def mvbs(sv, bin_start, n_tbins, range_bin, n_rbins, *, range=None, coef=None, s
     return dict(MVBS=out, sum=ssum, cnt=cnt)
 
 
+def _selftest_f64(x, who):
+    if x.dtype != torch.float64:  # (the entries take doubles and nothing else: another type would be read and written past its end)
+        raise ValueError(f"{who}: a float64 tensor expected, got {x.dtype}")
+
+
 def selftest_lin_from_db(u):
     """10^(u/10) through the fused kernel's table-driven f64 routine (accuracy self-test)."""
+    _selftest_f64(u, "selftest_lin_from_db")
     out = torch.empty_like(u)
     call("epa_selftest_lin_from_db", _p(u), _p(out), u.numel(), _stream())
     return out
 
 
 def selftest_log10(x, inline=False):
+    _selftest_f64(x, "selftest_log10")
     out = torch.empty_like(x)
     call("epa_selftest_log10_inline" if inline else "epa_selftest_log10", _p(x), _p(out), x.numel(), _stream())
     return out
@@ -1664,7 +1671,8 @@ def time_reversals(t, want_list=False):
 
 def reversal_medians(t, facts, lst, win_len, sub=None):
     """``sub`` (N - 1,) int64 with, at every reversal ``ni`` of ``lst``, the median of the original differences
-    ``d[max(0, ni - win_len) : ni]`` (``epa_reversal_medians``; the other entries are not written).  ``facts`` and ``lst``
+    ``d[max(0, ni - win_len) : ni]`` -- INT64_MIN (NaT) where that window is empty, a reversal in the first difference --
+    (``epa_reversal_medians``; the other entries are not written).  ``facts`` and ``lst``
     as :func:`time_reversals` left them for the same ``t``, which must hold no NaT."""
     N = _qc_times(t, "reversal_medians")
     if sub is None:

@@ -1030,7 +1030,7 @@ int epa_time_reversals(const int64_t* t, long long N, int64_t* facts, long long*
  * differences are recomputed from t, so a reversal inside another one's window enters that median as it is.  An even
  * number of values gives the wrapping sum of the two middle ones divided by 2, truncated toward zero (np.median of
  * timedelta64: [3, 8] -> 5, [-3, -8] -> -5, [-3, 8] -> 2, [-8, 3] -> -2).  sub [N-1] int64: only the reversal positions
- * are written, the rest keeps whatever it held; ni = 0 (an empty window) is not written either.  t must hold no NaT
+ * are written, the rest keeps whatever it held; ni = 0 (an empty window) gets INT64_MIN (NaT).  t must hold no NaT
  * (facts[EPA_QC_NAT] == 0): a NaT takes part as the integer it is.
  * EPA_EINVAL: N < 2, win_len outside 1 .. EPA_QC_MAX_WIN, a NULL array. */
 int epa_reversal_medians(const int64_t* t, long long N, int win_len, const int64_t* facts, const long long* list,
