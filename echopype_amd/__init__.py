@@ -13,12 +13,12 @@ loudly if it has not been built (``python echopype_amd/build.py``).
 from . import _lib  # noqa: F401,E402  (loads the HIP library; raises if missing)
 from . import calibrate, clean, commongrid, consolidate, convert, mask, metrics, ops, pipeline, qc, synth, targets, utils  # noqa: F401,E402
 from .combine import combine_echodata  # noqa: F401,E402
-from .convert import open_raw  # noqa: F401,E402
+from .convert import open_raw, open_raw_ek80  # noqa: F401,E402
 from .echodata import EchoData  # noqa: F401,E402
 from .fused import compute_Sv_clean_MVBS, compute_Sv_MVBS  # noqa: F401,E402
 from .xr_lite import DataArray, Dataset, DeviceArray  # noqa: F401,E402
 
 __version__ = "0.1.0"
-__all__ = ["calibrate", "clean", "commongrid", "consolidate", "convert", "open_raw", "mask", "metrics", "qc", "utils", "ops", "synth", "pipeline", "compute_Sv_MVBS", "compute_Sv_clean_MVBS", "combine_echodata",
+__all__ = ["calibrate", "clean", "commongrid", "consolidate", "convert", "open_raw", "open_raw_ek80", "mask", "metrics", "qc", "utils", "ops", "synth", "pipeline", "compute_Sv_MVBS", "compute_Sv_clean_MVBS", "combine_echodata",
            "EchoData", "Dataset", "DataArray",
            "DeviceArray", "targets"]

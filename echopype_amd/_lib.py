@@ -223,6 +223,7 @@ SIGNATURES = {
     "epa_concat_rows": [_vp, _vp, _vp, _vp, _i, _i, _ll, _i, _i, _vp, _vp],
     "epa_raw_index": [_vp, _ll, _vp, _ll, ctypes.POINTER(_ll), ctypes.POINTER(_ll)],
     "epa_raw0_unpack": [_vp, _ll, _ll, _vp, _vp, _i, _ll, _ll, _i, _vp, _vp, _vp, _vp],
+    "epa_raw3_unpack": [_vp, _ll, _ll, _vp, _vp, _i, _ll, _ll, _i, _vp, _vp, _vp],
     "epa_nmea_positions": [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _vp],
     "epa_region_stats": [_vp, _ll, _ll, _vp, _vp, _i, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp],
     "epa_region_labels": [_vp, _ll, _ll, _vp, _ll, _vp, _vp],

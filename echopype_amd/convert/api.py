@@ -10,8 +10,9 @@ and ``sentence_type`` on ``time1``, which is what ``consolidate.add_location`` r
 ``parse_nmea`` (the reference calls ``pynmea2``, which has never been run against them); a sentence outside the plain
 form the kernel decides goes through ``parse_nmea.parse_sentence`` on the host.  ``Platform/NMEA`` keeps every sentence.
 
-Scope: EK60 (``CON0`` / ``RAW0`` / ``NME0``).  EK80, AZFP, ``.bot`` / ``.idx`` files, ``use_swap`` and the positions of
-``MRU1`` / ``IDX`` datagrams are not built.
+Scope: EK60 (``CON0`` / ``RAW0`` / ``NME0``).  EK80 files are read by ``open_raw_ek80`` (:mod:`.api_ek80`), a function of
+its own: ``open_raw(..., "EK80")`` raises ``NotImplementedError``.  AZFP, ``.bot`` / ``.idx`` files, ``use_swap`` and the
+positions of ``MRU1`` / ``IDX`` datagrams are not built.
 
 Deviations from the reference, all on purpose:
 
@@ -253,6 +254,9 @@ def open_raw(raw_file, sonar_model, xml_path=None, include_bot=False, include_id
     ``sonar_model="EK60"`` (any letter case) and the defaults of ``xml_path``, ``include_bot``, ``include_idx``,
     ``storage_options`` and ``use_swap`` raises ``NotImplementedError``; ``convert_params`` and ``max_chunk_size`` have
     nothing to act on and are ignored.  See the module docstring for the scope and the deviations.
+
+    EK80 files are NOT read through this function: ``sonar_model="EK80"`` raises ``NotImplementedError`` like every other
+    model, and ``open_raw_ek80`` is the entry point for them.  Routing ``open_raw`` there is a later change.
 
     ``ValueError``: the file does not start with ``CON0``, holds no ping with power, or its framing is broken (no
     resynchronisation).  A file cut inside a datagram keeps the pings in front and logs a warning."""

@@ -6,6 +6,9 @@
 //   epa_raw0_unpack   power[c][p][s] = float32(int16 at off_p + 2s) * float32(10 log10(2) / 256)   (parse_base.py:24,302)
 //                     athwartship / alongship[c][p][s] = int8 at off_a + 2s / off_a + 2s + 1       (set_groups_ek60.py:681-694)
 //                     NaN behind a row's count and in a row without a datagram (offset -1)
+//   epa_raw3_unpack   convert.open_raw_ek80: backscatter_r / _i[c][p][s][b] = the float32 pair at off + 8 (s B_row + b), bit
+//                     copies, an imaginary part equal to 0.0 made NaN (parse_base.py:312-314); NaN behind the count, in
+//                     sectors the row lacks and in a row without a datagram
 //
 // A wavefront owns one output row.  NME0 datagrams between the pings have any length, so a sample block starts at ANY
 // byte offset: the int16 samples are not 2-byte aligned in general.  The file is therefore read as the aligned dwords
@@ -206,7 +209,142 @@ raw0_unpack_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict_
   }
 }
 
+// ---- convert.open_raw_ek80: the RAW3 complex sample blocks ---------------------------------------------------------------
+// A block holds count * B_row pairs (real, imaginary) of float32, sample by sample, sector by sector.  Values are bit
+// copies; the one rule is the reference's (parse_base.py:312-314): an imaginary part that equals 0.0 becomes NaN.
+constexpr uint32_t kNanBits = 0x7FC00000u;
+constexpr int kMaxBeams = 8;  // as ek80_complex.hip
+
+__device__ __forceinline__ uint32_t imag_of(uint32_t v) { return (v & 0x7fffffffu) ? v : kNanBits; }
+
+// the 4 bytes at byte offset b (all inside the file): the second dword only when the value straddles it
+__device__ __forceinline__ uint32_t load4(words_ptr words, long long b) {
+  const long long w = b >> 2;
+  const unsigned sh = (unsigned)(b & 3) * 8u;
+  const uint32_t a = words[w];
+  const uint32_t hi = sh ? words[w + 1] : 0u;
+  return funnel(a, hi, sh);
+}
+
+// chunks [0, nfull) of a row whose B_row is B, all elements present: a flat de-interleave, 8 file dwords -> 4 real + 4
+// imaginary words.  dre / dim and the file offset b0 are those of chunk 0.
+template <bool SHIFTED>
+__device__ __forceinline__ void complex_chunks(words_ptr words, long long b0, uint32_t* __restrict__ dre,
+                                               uint32_t* __restrict__ dim, long long nfull, int lane) {
+  const long long w0 = b0 >> 2;
+  const unsigned sh = (unsigned)(b0 & 3) * 8u;
+#pragma unroll 2
+  for (long long ch = lane; ch < nfull; ch += 64) {
+    uint32_t r[8];
+    load_row_dwords<8, SHIFTED>(words, w0 + 8 * ch, sh, r);
+    const u4 re = u4{r[0], r[2], r[4], r[6]};
+    const u4 im = u4{imag_of(r[1]), imag_of(r[3]), imag_of(r[5]), imag_of(r[7])};
+    __builtin_nontemporal_store(re, reinterpret_cast<u4*>(dre + 4 * ch));
+    __builtin_nontemporal_store(im, reinterpret_cast<u4*>(dim + 4 * ch));
+  }
+}
+
+__global__ void __launch_bounds__(epa::kBlock)
+raw3_unpack_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ table, long long rows, long long S, int B,
+                   uint32_t* __restrict__ re_out, uint32_t* __restrict__ im_out, int xcd_map) {
+  const words_ptr words = (words_ptr)(uintptr_t)bytes;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long g = xcd_map ? epa::xcd_contiguous((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+  const long long row = g * kWaves + wave;  // wave-uniform
+  if (row >= rows) return;
+  const long long off = table[3 * row], count = table[3 * row + 1];
+  const int brow = (int)table[3 * row + 2];
+  const long long N = S * B;                                       // elements of an output row
+  const long long nel = (off >= 0 && brow > 0) ? count * B : 0;    // elements in front of the first padded SAMPLE
+  const bool flat = brow == B;                                     // wave-uniform: the block is the row's front, interleaved
+  uint32_t* __restrict__ dre = re_out + row * N;
+  uint32_t* __restrict__ dim = im_out + row * N;                   // (the two planes have ONE geometry: see the entry point)
+  long long head = (long long)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(dre) & 15u)) & 15u) / 4u);
+  if (head > N) head = N;
+  const long long nchunk = (N - head) / 4;
+  const long long tail0 = head + nchunk * 4;
+  // element j of the output row: present when its sample lies in front of the count and its sector exists
+  auto fetch = [&](long long j, uint32_t& vr, uint32_t& vi) {
+    vr = kNanBits;
+    vi = kNanBits;
+    if (j < nel) {
+      long long e = j;
+      if (!flat) {
+        const long long s = j / B;
+        const int b = (int)(j - s * B);
+        e = b < brow ? s * brow + b : -1;
+      }
+      if (e >= 0) {
+        vr = load4(words, off + 8 * e);
+        vi = imag_of(load4(words, off + 8 * e + 4));
+      }
+    }
+  };
+  auto one = [&](long long j) {
+    uint32_t vr, vi;
+    fetch(j, vr, vi);
+    __builtin_nontemporal_store(vr, dre + j);
+    __builtin_nontemporal_store(vi, dim + j);
+  };
+  if (lane < head) one(lane);
+  if (tail0 + lane < N) one(tail0 + lane);  // (fewer than 4 elements)
+  // chunks that lie wholly inside a flat row's elements: no branch in the loop (the shift is the row's, wave-uniform)
+  const long long full = (flat && nel > head) ? ((nel - head) / 4 < nchunk ? (nel - head) / 4 : nchunk) : 0;
+  if (full > 0) {
+    const long long b0 = off + 8 * head;
+    if (__builtin_amdgcn_readfirstlane((int)(b0 & 3))) complex_chunks<true>(words, b0, dre + head, dim + head, full, lane);
+    else complex_chunks<false>(words, b0, dre + head, dim + head, full, lane);
+  }
+  // the chunk that straddles the count and the NaN chunks behind it; every chunk of a row with fewer sectors than B
+  for (long long ch = full + lane; ch < nchunk; ch += 64) {
+    const long long j = head + ch * 4;
+    u4 vr, vi;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      uint32_t a, b;
+      fetch(j + e, a, b);
+      vr[e] = a;
+      vi[e] = b;
+    }
+    __builtin_nontemporal_store(vr, reinterpret_cast<u4*>(dre + j));
+    __builtin_nontemporal_store(vi, reinterpret_cast<u4*>(dim + j));
+  }
+}
+
 }  // namespace
+
+extern "C" int epa_raw3_unpack(const uint8_t* bytes, long long n_bytes, long long n_alloc, const int64_t* table_host,
+                               const int64_t* table, int C, long long P, long long S, int B, float* backscatter_r,
+                               float* backscatter_i, epa_stream_t stream) {
+  EPA_CHECK_ARG(bytes && table_host && table && backscatter_r && backscatter_i, "epa_raw3_unpack: NULL array argument");
+  EPA_CHECK_ARG(C >= 1 && P >= 1 && S >= 1 && P <= (1LL << 40) && S <= (1LL << 40),
+                "epa_raw3_unpack: C=%d, P=%lld, S=%lld must all be at least 1", C, P, S);
+  EPA_CHECK_ARG(B >= 1 && B <= kMaxBeams, "epa_raw3_unpack: 1 .. %d sectors are served (got B=%d)", kMaxBeams, B);
+  EPA_CHECK_ARG(n_bytes >= 0 && n_alloc >= n_bytes && n_alloc % 16 == 0 && (reinterpret_cast<uintptr_t>(bytes) & 15u) == 0,
+                "epa_raw3_unpack: the file buffer must be 16-byte aligned and padded to a multiple of 16 bytes "
+                "(n_bytes=%lld, n_alloc=%lld)", n_bytes, n_alloc);
+  // one geometry for both planes: heads and chunks are computed from the real plane's addresses
+  EPA_CHECK_ARG((reinterpret_cast<uintptr_t>(backscatter_r) & 15u) == 0 && (reinterpret_cast<uintptr_t>(backscatter_i) & 15u) == 0,
+                "epa_raw3_unpack: the output planes must be 16-byte aligned");
+  const long long rows = (long long)C * P;
+  EPA_CHECK_ARG((rows + kWaves - 1) / kWaves <= 0x7fffffffLL && (double)rows * (double)S * (double)B * 4.0 < 9.0e18,
+                "epa_raw3_unpack: %lld rows of %lld samples are more than one launch takes", rows, S);
+  for (long long r = 0; r < rows; ++r) {
+    const long long off = table_host[3 * r], count = table_host[3 * r + 1], brow = table_host[3 * r + 2];
+    EPA_CHECK_ARG(count >= 0 && count <= S, "epa_raw3_unpack: row %lld has count=%lld, 0 .. S=%lld are served", r, count, S);
+    EPA_CHECK_ARG(brow >= 0 && brow <= B, "epa_raw3_unpack: row %lld has %lld sectors, 0 .. B=%d are served", r, brow, B);
+    EPA_CHECK_ARG(off >= -1 && (off < 0 || (off <= n_bytes && 8 * count * brow <= n_bytes - off)),
+                  "epa_raw3_unpack: the complex block of row %lld (offset %lld, %lld samples of %lld sectors) leaves the "
+                  "%lld file bytes", r, off, count, brow, n_bytes);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((rows + kWaves - 1) / kWaves)), block(epa::kBlock);
+  const int xm = epa::xcd_map_enabled() ? 1 : 0;
+  hipLaunchKernelGGL(raw3_unpack_kernel, grid, block, 0, st, bytes, table, rows, S, B, reinterpret_cast<uint32_t*>(backscatter_r),
+                     reinterpret_cast<uint32_t*>(backscatter_i), xm);
+  return epa::check_launch("raw3_unpack_kernel");
+}
 
 extern "C" int epa_raw_index(const uint8_t* bytes_host, long long n_bytes, epa_raw_record* records_out, long long capacity,
                              long long* n_records, long long* n_bytes_consumed) {

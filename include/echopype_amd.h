@@ -1113,6 +1113,22 @@ int epa_raw0_unpack(const uint8_t* bytes, long long n_bytes, long long n_alloc, 
                     const int64_t* table, int C, long long P, long long S, int angle_type, float* power,
                     void* athwartship, void* alongship, epa_stream_t stream);
 
+/* convert.open_raw_ek80: the complex sample blocks of the RAW3 datagrams of an EK80 file (ek_raw_parsers.py:1745-1769,
+ * parse_base.py:304-314).  backscatter_r / backscatter_i [C][P][S][B] f32: for row (c, p), sample s < count and sector
+ * b < B_row, backscatter_r is the float32 at bytes[off + 8 (s B_row + b)] and backscatter_i the float32 4 bytes further on,
+ * both bit copies -- except that an imaginary part equal to 0.0 (-0.0 included) becomes NaN, which is the reference's rule
+ * (its NaN padding is a complex number whose imaginary part is 0, so it tests for 0).  Everything else is NaN (0x7FC00000):
+ * samples behind count, sectors >= B_row, rows with off == -1.  One launch; every output element is written exactly once,
+ * nothing is pre-filled.
+ * bytes / n_bytes / n_alloc: the file as for epa_raw0_unpack.  table [C * P][3] int64, row (c, p): off (-1: no block),
+ * count and B_row; table_host the same on the host, which the checks read.
+ * EPA_EINVAL (nothing is launched): a NULL array; C, P or S < 1; B outside 1 .. 8; a count outside 0 .. S; a B_row outside
+ * 0 .. B; a block (8 count B_row bytes) that leaves [0, n_bytes); a buffer or plane that is not 16-byte aligned; n_alloc not
+ * a multiple of 16 or below n_bytes. */
+int epa_raw3_unpack(const uint8_t* bytes, long long n_bytes, long long n_alloc, const int64_t* table_host,
+                    const int64_t* table, int C, long long P, long long S, int B, float* backscatter_r, float* backscatter_i,
+                    epa_stream_t stream);
+
 /* Positions from the NMEA sentences of the file's NME0 datagrams, parsed where they lie in HBM (set_groups_base.py:180-239,
  * which calls pynmea2.parse once per sentence on the host; the rules are restated in echopype_amd/convert/parse_nmea.py).
  * bytes / n_bytes / n_alloc: the file as for epa_raw0_unpack.  table [n][2] int64: byte offset and length of the text of
